@@ -2,6 +2,7 @@
 """bench.py -- Mrays/s fwd+bwd of the Lightplane Renderer / Splatter hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4|1080p_s128|cfg3|cfg5|small|refbench|refbench_splatter]
+                    [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
 
 Workloads (BASELINE.json `configs`); one step = forward + backward, inputs resident in HBM:
   cfg2        (default, the headline metric) Renderer, 256x256 rays per GPU (pinhole camera looking at the [-1,1]^3
@@ -27,10 +28,16 @@ With N > 1 GPUs (one process per GPU, RCCL) every rank works on its own camera (
 are replicated and the Renderer's grid + MLP gradients (the Splatter's un-normalised output + weight grid) are summed
 with an all-reduce INSIDE the timed step.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the workload (Renderer: the backward
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times K steps and prints the headline (`value`, `ms_per_step`,
+what ran); nothing else touches the GPU.  --dump-outputs DIR then writes what the last timed step computed -- the outputs and
+the gradients a caller of the op receives -- as DIR/<name>.npy (see dump_outputs), so that two builds can be compared on the
+same seeded inputs.
+
+--full adds everything beyond the headline, measured after the timed steps: `fwd_ms` / `bwd_ms` (HIP events), the
+reference-protocol peak memory and `roofline`, for the dominant kernel of the workload (Renderer: the backward
 kernel; Splatter: the forward walk): SURVEY.md 8(d)'s algorithmic bytes per launch divided by that kernel's mean
 launch time, measured with HIP events on the launch stream (torch's current stream is the stream the C ABI launches on).
-At N = 1 with the default workload the line also carries `extras`: the other configurations measured the same way
+At N = 1 with the default workload the --full line also carries `extras`: the other configurations measured the same way
 (short runs), so that every number quoted in DESIGN.md / README.md can be recomputed from the driver's BENCH file (at
 N > 1 `extras` holds north_star's reporting batches instead: 1920x1080 rays per GPU at S = 128 and the cfg 4 shard,
 through the same sharded step with its RCCL all-reduce, bounded by a watchdog), and
@@ -224,6 +231,12 @@ class RendererWorkload:
             self.loss(out).backward()
         else:
             torch.autograd.backward(list(out[:3]), self.up)
+        return out
+
+    def results(self, out):
+        """What a caller of the step receives: the op's outputs and the gradients of its inputs."""
+        return {"ray_length": out[0], "neg_log_t": out[1], "feature": out[2], "grad_grid": self.flat.grad,
+                "grad_mlp_params": self.params.grad, "grad_encoding": self.rays.encoding.grad}
 
     roofline_kernel = "renderer backward"
 
@@ -274,7 +287,12 @@ class SplatterWorkload:
 
     def step(self):
         self.zero_grads()
-        torch.autograd.backward([self.forward()], [self.up])  # upstream gradient handed over directly (no loss kernels)
+        out = self.forward()
+        torch.autograd.backward([out], [self.up])  # upstream gradient handed over directly (no loss kernels)
+        return out
+
+    def results(self, out):
+        return {"splat_grid": out, "grad_encoding": self.rays.encoding.grad}
 
     def roofline(self, fwd_ms, bwd_ms):
         fwd_b, bwd_b = self.algorithmic_bytes()
@@ -371,7 +389,7 @@ def _device_random_rays(gen, n, batch, enc_dim, dev):
     return lp.Rays(directions=directions, origins=origins, grid_idx=grid_idx, near=near, far=far, encoding=enc)
 
 
-def refbench_renderer(dev, sizes=None, kernel=_lib.LP_KERNEL_AUTO):
+def refbench_renderer(dev, sizes=None, kernel=_lib.LP_KERNEL_AUTO, n_reruns=5, n_warmup=2):
     """tests/renderer_speed_benchmark.py:228-285 on this implementation: grid [3,32,32,32,32] as a triplane (three batch entries),
     2/2/2 x 32 decoder with N(0, 0.01) parameters (tests/utils.py:349), 256 samples, random rays (tests/utils.py:230-268)."""
     from tests.synth import grid_sizes_for, random_decoder, random_grids, random_rays
@@ -399,19 +417,19 @@ def refbench_renderer(dev, sizes=None, kernel=_lib.LP_KERNEL_AUTO):
         saved = lp.config.check_inputs
         lp.config.check_inputs = True
         try:
-            r = _ref_protocol(make_inputs, run, dev)
+            r = _ref_protocol(make_inputs, run, dev, n_reruns, n_warmup)
         finally:
             lp.config.check_inputs = saved
         r.update(num_rays=n, image_size=int(n ** 0.5),
                  Mrays_per_s_fwd_bwd=round(n / (r["t_fw_kernel_ms"] + r["t_bw_kernel_ms"]) / 1e3, 4))
         rows.append(r)
     return {"benchmark": "reference tests/renderer_speed_benchmark.py:228-285: triplane [3,32,32,32,32], hidden 32, 2/2/2 layers, S=256, "
-                         "random rays; wall time incl. host side and output / gradient allocation, 2 warm-up + 5 reruns",
+                         f"random rays; wall time incl. host side and output / gradient allocation, {n_warmup} warm-up + {n_reruns} reruns",
             "published_reference": "SURVEY 6: 256^2 rays fwd ~28 ms / bwd ~0.32 s (figure in the reference's README, A100-class GPU, Triton)",
             "rows": rows}
 
 
-def refbench_splatter(dev, views=None):
+def refbench_splatter(dev, views=None, n_reruns=5, n_warmup=2):
     """tests/splatter_speed_benchmark.py:200-247: 128^2 x num_view random rays x 64 ch -> voxel [1,160,160,160,64], S = 96,
     mask_out_of_bounds_samples."""
     from tests.synth import random_rays
@@ -433,13 +451,14 @@ def refbench_splatter(dev, views=None):
         saved = lp.config.check_inputs  # (the reference's call path checks grid_idx with a device sync; "auto" march order rides on it)
         lp.config.check_inputs = True
         try:
-            r = _ref_protocol(make_inputs, run, dev)
+            r = _ref_protocol(make_inputs, run, dev, n_reruns, n_warmup)
         finally:
             lp.config.check_inputs = saved
         r.update(num_view=nv, num_rays=n, Mrays_per_s_fwd_bwd=round(n / (r["t_fw_kernel_ms"] + r["t_bw_kernel_ms"]) / 1e3, 4))
         rows.append(r)
     return {"benchmark": "reference tests/splatter_speed_benchmark.py:200-247: 128^2 x num_view random rays x 64 ch -> voxel "
-                         "[1,160,160,160,64] (1.05 GB), S=96, mask_out_of_bounds_samples; wall time, 2 warm-up + 5 reruns", "rows": rows}
+                         f"[1,160,160,160,64] (1.05 GB), S=96, mask_out_of_bounds_samples; wall time, {n_warmup} warm-up + {n_reruns} reruns",
+            "rows": rows}
 
 
 class JointWorkload:
@@ -499,7 +518,13 @@ class JointWorkload:
 
     def step(self):
         self.zero_grads()
-        self.loss(self.forward()).backward()
+        out = self.forward()
+        self.loss(out).backward()
+        return out
+
+    def results(self, out):
+        return {"ray_length": out[0], "neg_log_t": out[1], "feature": out[2], "grad_mlp_params": self.params.grad,
+                "grad_splat_encoding": self.splat_rays.encoding.grad}
 
     def roofline(self, fwd_ms, bwd_ms):
         ns, nr, S, C = self.splat_rays.n_rays, self.cam.n_rays, self.S, self.C
@@ -1089,6 +1114,31 @@ def run_extras(dev, kernel, legs=EXTRAS):
     return {key: soft(leg, dev, kernel) for key, leg in legs}
 
 
+DUMP_BYTES = 60 << 20  # all arrays of one --dump-outputs together (below 64 MB with the .npy headers)
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """Write every array as out_dir/<name>.npy, float32 (float64 stays float64).  Smallest first, each array is written whole if
+    it fits its share of what is left of the budget (the rest split evenly over the arrays still to come); a larger one is written
+    as a fixed sample of its flattened elements: `share` indices drawn with seed 0, sorted -- the same for every run with the same
+    arguments, so two builds are compared element for element.  Returns {name: (shape, elements written)}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, v.detach()) for k, v in arrays.items()), key=lambda kv: kv[1].numel())
+    written = {}
+    for i, (name, t) in enumerate(items):
+        t = t if t.dtype == torch.float64 else t.float()
+        share = budget // (len(items) - i) // t.element_size()
+        if t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        budget -= t.numel() * t.element_size()
+        written[name] = (list(arrays[name].shape), t.numel())
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1099,14 +1149,22 @@ def main():
     ap.add_argument("--refbench-max", type=float, default=None, help="refbench: largest image size (default 2048) / refbench_splatter: "
                                                                       "largest num_view (default 256)")
     ap.add_argument("--kernel", type=int, default=_lib.LP_KERNEL_AUTO)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short runs of the other configurations (N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure fwd / bwd times, peak memory, roofline "
+                                                        "and binding blocks, the other configurations (`extras`) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the runs of the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs and input gradients of the last timed step "
+                                                                         "(rank 0) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to exercise the "
                                                        "multi-rank code path with several ranks on one GPU)")
     args = ap.parse_args()
     big = args.workload in ("cfg4", "1080p_s128", "h64_example_112", "h64_222", "refbench256", "cfg5_render")
     steps = args.steps if args.steps is not None else (2 if args.workload == "cfg5" else 10 if big else 200)
     warmup = args.warmup if args.warmup is not None else (1 if args.workload == "cfg5" else 2 if big else 10)
+    if steps < 1 or warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload in ("refbench", "refbench_splatter"):
+        ap.error("--dump-outputs: the refbench tables draw fresh inputs per rerun and keep no outputs; use a timed-step workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as a plain process: re-launch as N ranks (one per GPU) through torch.distributed.run
@@ -1145,15 +1203,17 @@ def main():
     lp.config.check_inputs = False  # the grid_idx range check is a host sync, not part of the op
     if args.workload in ("refbench", "refbench_splatter"):  # the reference's own benchmark tables (single GPU, its protocol; no timed-step loop)
         assert world == 1, "refbench is a single-GPU table"
+        steps = args.steps if args.steps is not None else 5  # reruns per row (the reference's protocol: 2 warm-up + 5)
+        warmup = args.warmup if args.warmup is not None else 2
         if args.workload == "refbench":
-            tab = refbench_renderer(dev, [x for x in REFBENCH_SIZES if x <= (args.refbench_max or 2048) + 1e-6], args.kernel)
+            tab = refbench_renderer(dev, [x for x in REFBENCH_SIZES if x <= (args.refbench_max or 2048) + 1e-6], args.kernel, steps, warmup)
             r = next((x for x in tab["rows"] if x["image_size"] == 256), tab["rows"][-1])
         else:
-            tab = refbench_splatter(dev, [v for v in REFBENCH_VIEWS if v <= (args.refbench_max or 256)])
+            tab = refbench_splatter(dev, [v for v in REFBENCH_VIEWS if v <= (args.refbench_max or 256)], steps, warmup)
             r = tab["rows"][0]
         print(json.dumps({"metric": f"Mrays/sec fwd+bwd ({args.workload}: the reference's speed benchmark, row image_size / num_view = "
                                     f"{r.get('image_size', r.get('num_view'))}); peak bwd mem (MB)",
-                          "value": r["Mrays_per_s_fwd_bwd"], "unit": "Mrays/s", "n_gpus": 1, "steps": 5, "warmup": 2,
+                          "value": r["Mrays_per_s_fwd_bwd"], "unit": "Mrays/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
                           "ms_per_step": round(r["t_fw_kernel_ms"] + r["t_bw_kernel_ms"], 4), "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "f32", "arithmetic": ARITHMETIC, "data": "synthetic",
                           "config": {"workload": tab["benchmark"]}, "peak_bwd_mem_mb": r["max_mem_bw_kernel_mb"], "table": tab}), flush=True)
@@ -1170,17 +1230,37 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        wl.step()
+        out = wl.step()
     sync()
     dt = time.perf_counter() - t0
-    peak_mb = reference_protocol_peak_mb(wl, dev)  # outside the timed region; the reference's max_mem_bw protocol
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / steps * 1e3
     value = wl.n_rays * world / (ms_per_step * 1e-3) / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.results(out), args.dump_outputs)
+    del out
 
+    metric = ("Mrays/sec fwd+bwd, 64^3x16ch triplane @128 samples; peak bwd mem (MB)" if args.workload == "cfg2"
+              else f"Mrays/sec fwd+bwd ({args.workload}); peak bwd mem (MB)")
+    line = {"metric": metric, "value": round(value, 4), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "arithmetic": ARITHMETIC, "build": soft(build_record), "step_protocol": STEP_PROTOCOL, "data": "synthetic",
+            "config": {"workload": wl.desc, "rays_per_gpu": wl.n_rays,
+                       "parallelism": f"ray-shard dp{world}, grid replicated, "
+                                      + ("un-normalised splat + weights all-reduced" if args.workload == "cfg3" else
+                                         "splat grids summed (reduce-scatter + all-gather), render-grad all-reduce" if args.workload == "cfg5"
+                                         else "grad all-reduce")}}
+    if not args.full:  # the headline alone: nothing else runs on the GPU
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+
+    peak_mb = reference_protocol_peak_mb(wl, dev)  # outside the timed region; the reference's max_mem_bw protocol
     fwd_ms, bwd_ms = event_times(wl, max(5, min(steps, 20)))
     observed = soft(observed_kernels, wl, 3) if rank == 0 and not isinstance(wl, JointWorkload) else {}
     if "error" in observed:  # (the profiler pass only names the kernels; the timed numbers do not depend on it)
@@ -1191,7 +1271,7 @@ def main():
     # prints the headline line without it and every rank exits (a stuck collective cannot take the run with it).
     sharded = None
     watchdog_fired = []
-    if world > 1 and args.workload == "cfg2" and not args.no_extras:
+    if world > 1 and args.workload == "cfg2" and not args.no_extras:  # (--full only)
         import threading
         done = threading.Event()
         line_ready = {}
@@ -1233,30 +1313,20 @@ def main():
             roof["note"] = "effective bandwidth: the 786 KB grid is L2 resident, compulsory HBM bytes are ~0.5 KB/ray"
         if isinstance(wl, RendererWorkload):
             roof["grid_tile_staging"] = GRID_TILE_STAGING
-        res = {
-            "metric": ("Mrays/sec fwd+bwd, 64^3x16ch triplane @128 samples; peak bwd mem (MB)" if args.workload == "cfg2"
-                       else f"Mrays/sec fwd+bwd ({args.workload}); peak bwd mem (MB)"),
-            "value": round(value, 4), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "arithmetic": ARITHMETIC, "build": soft(build_record), "step_protocol": STEP_PROTOCOL, "data": "synthetic",
-            "config": {"workload": wl.desc, "rays_per_gpu": wl.n_rays,
-                       "parallelism": f"ray-shard dp{world}, grid replicated, "
-                                      + ("un-normalised splat + weights all-reduced" if args.workload == "cfg3" else
-                                         "splat grids summed (reduce-scatter + all-gather), render-grad all-reduce" if args.workload == "cfg5"
-                                         else "grad all-reduce")},
+        res = dict(line)
+        res.update({
             "peak_bwd_mem_mb": round(peak_mb, 2),
             "peak_bwd_mem_protocol": "reference max_mem_bw_kernel (tests/utils.py:33-57): inputs resident, no gradient buffers yet; "
                                      "peak over forward + loss + backward (outputs, saved state and gradient buffers count)",
             "fwd_ms": round(fwd_ms, 4), "bwd_ms": round(bwd_ms, 4),
             "roofline": roof,
-        }
+        })
         if isinstance(wl, RendererWorkload):
             res["mlp_fp32_frac_of_peak"] = round(wl.mlp_flops_fwdbwd() / ((fwd_ms + bwd_ms) * 1e-3) / FP32_PEAK, 5)
         return res
 
     def minimal_line(err):
-        return {"metric": ("Mrays/sec fwd+bwd, 64^3x16ch triplane @128 samples; peak bwd mem (MB)" if args.workload == "cfg2"
-                           else f"Mrays/sec fwd+bwd ({args.workload}); peak bwd mem (MB)"),
+        return {"metric": metric,
                 "value": round(value, 4), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
                 "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": "f32", "arithmetic": ARITHMETIC, "data": "synthetic",

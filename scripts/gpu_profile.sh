@@ -11,7 +11,7 @@ for w in $WL; do rm -rf $R/gpurun_out/prof_$w $R/gpurun_out/prof_$w.txt $R/gpuru
 unset LP_LOOP
 run() {  # workload, steps (trace), steps (pmc)
   w=$1
-  B="python $R/bench.py --workload $w --no-cpu-baseline --no-extras"
+  B="python $R/bench.py --workload $w --full --no-cpu-baseline --no-extras"
   rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$w -o bench -- $B --steps $2 --warmup 3 > $R/gpurun_out/prof_$w.txt 2>&1
   tail -1 $R/gpurun_out/prof_$w.txt | cut -c1-300
   P="$B --steps $3 --warmup 1"
@@ -36,7 +36,7 @@ for w in $WL; do
     loop)  # the headline workload through the layer-looped family (LP_LOOP=1: shallow two-waves-per-SIMD backward)
       export LP_LOOP=1
       rm -rf $R/gpurun_out/prof_loop $R/gpurun_out/pmc[1-4]_loop
-      B="python $R/bench.py --workload cfg2 --no-cpu-baseline --no-extras"
+      B="python $R/bench.py --workload cfg2 --full --no-cpu-baseline --no-extras"
       rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_loop -o bench -- $B --steps 200 --warmup 3 > $R/gpurun_out/prof_loop.txt 2>&1
       tail -1 $R/gpurun_out/prof_loop.txt | cut -c1-300
       P="$B --steps 3 --warmup 1"

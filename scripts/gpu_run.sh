@@ -34,7 +34,7 @@ for step in "$@"; do
     testfile) timeout 1500 python -m pytest $arg -m gpu -q -x --tb=short -p no:cacheprovider > "$log" 2>&1; echo "rc=$?" >> "$log" ;;
     bench) timeout 900 python bench.py $arg > "$log" 2>&1; echo "rc=$?" >> "$log" ;;
     ab) for round in 1 2; do for f in ab/lib*.so; do
-          echo "$(basename $f): $(LIGHTPLANE_AMD_LIB=$PWD/$f timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras $arg 2>&1 | tail -1 |
+          echo "$(basename $f): $(LIGHTPLANE_AMD_LIB=$PWD/$f timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras $arg 2>&1 | tail -1 |
             python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], "Mrays/s fwd", d["fwd_ms"], "bwd", d["bwd_ms"])' 2>&1 | tail -1)"
         done; done > "$log" 2>&1 ;;
     profile) bash scripts/gpu_profile.sh ${arg//,/ } > "$log" 2>&1; python scripts/summarize_profiles.py ${LP_ROUND:-r06} ${arg:-cfg2,cfg3,cfg4} >> "$log" 2>&1 ;;  # (only the workloads profiled here: the round's other entries stay)

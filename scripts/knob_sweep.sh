@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-$PWD}
 one() {  # label, workload, env...
   local label=$1 w=$2; shift 2
-  echo "$label $(env "$@" python bench.py --workload $w --no-extras --no-cpu-baseline --steps 60 --warmup 5 2>&1 | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], "fwd", d["fwd_ms"], "bwd", d["bwd_ms"])')"
+  echo "$label $(env "$@" python bench.py --workload $w --full --no-extras --no-cpu-baseline --steps 60 --warmup 5 2>&1 | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], "fwd", d["fwd_ms"], "bwd", d["bwd_ms"])')"
 }
 for s in 1 2 3 4 6; do one "cfg3 LP_SPLAT_SEGMENTS=$s" cfg3 LP_SPLAT_SEGMENTS=$s; done
 one "cfg3 default" cfg3 LP_DUMMY=1

@@ -15,17 +15,17 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(REPO, "gpurun_out")
 P = os.path.join(REPO, "profiles")
 os.makedirs(P, exist_ok=True)
-CMD = {"cfg2": "python bench.py --workload cfg2 --no-cpu-baseline --no-extras --steps 200 --warmup 3",
-       "cfg3": "python bench.py --workload cfg3 --no-cpu-baseline --no-extras --steps 50 --warmup 3",
-       "cfg4": "python bench.py --workload cfg4 --no-cpu-baseline --no-extras --steps 5 --warmup 3",
-       "small": "python bench.py --workload small --no-cpu-baseline --no-extras --steps 200 --warmup 3",
-       "1080p_s128": "python bench.py --workload 1080p_s128 --no-cpu-baseline --no-extras --steps 5 --warmup 3",
-       "cfg5": "python bench.py --workload cfg5 --no-cpu-baseline --no-extras --steps 3 --warmup 3",
-       "refbench256": "python bench.py --workload refbench256 --no-cpu-baseline --no-extras --steps 20 --warmup 3",
-       "cfg5_render": "python bench.py --workload cfg5_render --no-cpu-baseline --no-extras --steps 5 --warmup 3",
-       "loop": "LP_LOOP=1 python bench.py --workload cfg2 --no-cpu-baseline --no-extras --steps 200 --warmup 3",
-       "h64_222": "python bench.py --workload h64_222 --no-cpu-baseline --no-extras --steps 20 --warmup 3",
-       "h64_example_112": "python bench.py --workload h64_example_112 --no-cpu-baseline --no-extras --steps 20 --warmup 3"}
+CMD = {"cfg2": "python bench.py --workload cfg2 --full --no-cpu-baseline --no-extras --steps 200 --warmup 3",
+       "cfg3": "python bench.py --workload cfg3 --full --no-cpu-baseline --no-extras --steps 50 --warmup 3",
+       "cfg4": "python bench.py --workload cfg4 --full --no-cpu-baseline --no-extras --steps 5 --warmup 3",
+       "small": "python bench.py --workload small --full --no-cpu-baseline --no-extras --steps 200 --warmup 3",
+       "1080p_s128": "python bench.py --workload 1080p_s128 --full --no-cpu-baseline --no-extras --steps 5 --warmup 3",
+       "cfg5": "python bench.py --workload cfg5 --full --no-cpu-baseline --no-extras --steps 3 --warmup 3",
+       "refbench256": "python bench.py --workload refbench256 --full --no-cpu-baseline --no-extras --steps 20 --warmup 3",
+       "cfg5_render": "python bench.py --workload cfg5_render --full --no-cpu-baseline --no-extras --steps 5 --warmup 3",
+       "loop": "LP_LOOP=1 python bench.py --workload cfg2 --full --no-cpu-baseline --no-extras --steps 200 --warmup 3",
+       "h64_222": "python bench.py --workload h64_222 --full --no-cpu-baseline --no-extras --steps 20 --warmup 3",
+       "h64_example_112": "python bench.py --workload h64_example_112 --full --no-cpu-baseline --no-extras --steps 20 --warmup 3"}
 out = {}
 summary_path = os.path.join(P, f"{ROUND}_pmc_summary.json")
 if ONLY and os.path.exists(summary_path):  # a partial re-profile keeps the other workloads' entries of this round

@@ -311,15 +311,15 @@ def test_bench_cfg5_two_ranks_on_one_gpu():
 
 
 def test_bench_default_command_two_ranks_on_one_gpu():
-    """The driver's multi-GPU command -- `torch.distributed.run ... bench.py --gpus N --steps K --warmup W`, default workload -- with
-    two gloo ranks on this GPU: the headline line with the sharded 1080p legs in `extras` (barrier + max over ranks), the
-    roofline / binding blocks looked up by rank 0 without a collective (the other rank must not wait for it forever)."""
+    """The multi-GPU command with every leg -- `torch.distributed.run ... bench.py --gpus N --steps K --warmup W --full`, default
+    workload -- with two gloo ranks on this GPU: the headline line with the sharded 1080p legs in `extras` (barrier + max over ranks),
+    the roofline / binding blocks looked up by rank 0 without a collective (the other rank must not wait for it forever)."""
     import json
     port = 29800 + (os.getpid() % 90)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LP_BENCH_EXTRAS_TIMEOUT="400")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5",
-                        "--warmup", "2"],
+                        "--warmup", "2", "--full"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = r.stdout.decode()
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -346,6 +346,42 @@ def test_bench_gpus_2_as_a_plain_process():
     res = json.loads(lines[-1])
     assert res["n_gpus"] == 2 and res["value"] > 0 and res["steps"] == 3 and "error" not in res
     assert res["config"]["rays_per_gpu"] == 65536 and "dp2" in res["config"]["parallelism"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: the line is the headline alone (K timed steps, ms_per_step, no --full
+    block), and DIR holds the outputs and input gradients of the cfg-2 step as float32 .npy files that equal one step of the same
+    seeded workload rebuilt here."""
+    import importlib.util
+    import json
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = r.stdout.decode()
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, out[-4000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["unit"] == "Mrays/s" and res["dtype"] == "f32"
+    assert abs(res["value"] - 65536 / res["ms_per_step"] / 1e3) <= 1e-3 * res["value"] + 1e-3
+    assert not {"fwd_ms", "bwd_ms", "roofline", "peak_bwd_mem_mb", "extras", "cpu_baseline"} & set(res), sorted(res)
+
+    spec = importlib.util.spec_from_file_location("lp_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    old = lp.config.check_inputs
+    lp.config.check_inputs = False
+    try:
+        wl = bench.RendererWorkload("cfg2", 0, torch.device("cuda:0"), None, _lib.LP_KERNEL_AUTO)
+        want = {k: v.detach().cpu().numpy() for k, v in wl.results(wl.step()).items()}
+    finally:
+        lp.config.check_inputs = old
+    assert sorted(p.name for p in d.iterdir()) == sorted(k + ".npy" for k in want)
+    assert sum(p.stat().st_size for p in d.iterdir()) <= 64e6
+    for k, w in want.items():
+        got = np.load(d / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == w.shape, (k, got.dtype, got.shape)
+        scale = float(np.abs(w).max()) + 1e-30
+        assert float(np.abs(got - w).max()) <= 1e-5 * scale, k  # (grid-gradient atomics: summation order may differ per run)
 
 
 def test_backward_with_offloaded_saved_tensors():

@@ -788,6 +788,31 @@ def test_bench_extras_fail_soft_and_cover_every_leg():
     assert "assert self.hidden" not in src
 
 
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: arrays that fit are written whole (float64 kept, everything else float32), a larger one as a fixed
+    seeded sample, all of them within the byte budget; the same arrays give the same files."""
+    import numpy as np
+    bench, _ = _load_bench()
+    assert bench.DUMP_BYTES <= 63_000_000  # the 64 MB bound, .npy headers included
+    g = torch.Generator().manual_seed(0)
+    arrays = {"small": torch.randn(10, 3, generator=g), "f64": torch.randn(7, dtype=torch.float64, generator=g),
+              "half": torch.randn(300, generator=g).half(), "big": torch.randn(5000, 4, generator=g)}
+    written = bench.dump_outputs(arrays, str(tmp_path / "a"), budget=16384)
+    bench.dump_outputs(arrays, str(tmp_path / "b"), budget=16384)
+    total = 0
+    for k, t in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b) and a.dtype == (np.float64 if k == "f64" else np.float32), k
+        assert written[k] == (list(t.shape), a.size)
+        total += a.nbytes
+        if k != "big":
+            assert np.array_equal(a, t.double().numpy() if k == "f64" else t.float().numpy())
+    big = arrays["big"].reshape(-1).numpy()
+    sample = np.load(tmp_path / "a" / "big.npy")
+    assert sample.ndim == 1 and 0 < sample.size < big.size and np.isin(sample, big).all()
+    assert total <= 16384
+
+
 def test_graphed_renderer_refuses_to_freeze_the_noise_seed():
     """The opacity-noise seed is a host scalar: captured into a HIP graph it would repeat one noise pattern at every replay
     (ADVICE round 3).  graphed_renderer refuses, before it touches the GPU."""
