@@ -59,13 +59,13 @@ extern "C" {
                                   widths 16 / 32 / 64), 64-channel Splatter walks
                            0.2.3: no struct change; 64-channel Renderer grid-lists on family 3; the Renderer's family 1 is the tuned
                                   default decoder shape only (every other shallow shape reports 3), lp_splatter_kernel_family() no
-                                  longer returns 2; lp_version() is NEGATIVE for a library built with -DLP_EXPERIMENTS
+                                  longer returns 2; lp_version() was negative for a library built with experiment switches (since
+                                  retired: every build returns LP_VERSION)
                            0.2.4: no struct change; lp_renderer_kernel_family() no longer returns 2 (2/2/2 x 64 decoders run the
                                   layer-looped family's two-block kernels and report 3); family 3 takes up to 256 beyond-far samples
                                   and two-grid decoders of hidden width 64 (heads of at most 2 layers, 16 / 32 grid channels)
                            0.2.5: no struct change; new test hook lp_renderer_backward_relu_dump(); the dX chains of the MFMA
-                                  backwards take the gradient operand as two bf16 limbs (-DLP_DX_LIMBS=3 restores
-                                  three)
+                                  backwards take the gradient operand as two bf16 limbs
                            0.2.6: LpRendererArgs.arithmetic (LP_ARITH_FP32: every product of the backward fp32-equivalent, selectable
                                   per call); lp_build_info(); lp_renderer_relu_dump_words() and dump twins for the layer-looped
                                   family (the dump of family 1 keeps its five words per sample); LpRendererArgs.march_order
@@ -296,7 +296,7 @@ typedef struct LpRayEmbedArgs {
   float* grad_bias;         /* [E] */
 } LpRayEmbedArgs;
 
-int lp_version(void); /* LP_VERSION; negative = built with -DLP_EXPERIMENTS (A/B timing switches), not a product build */
+int lp_version(void); /* LP_VERSION */
 /* What this binary was built from, as one JSON object (static storage): "version", "src_hash" (sha256 over csrc/ *.hip, *.h,
  * build.py and this header, as lightplane_amd/csrc/build.py source_hash() computes it -- compare with the tree), "flags" (global
  * + per-file compiler flags), and per kernel family the limb counts / matrix instructions its backward was compiled with

@@ -224,11 +224,7 @@ using namespace lp;
 
 extern "C" {
 
-#ifdef LP_EXPERIMENTS  // a build with experiment switches (LP_X_*) identifies itself: negative version, refused by the binding
-int lp_version(void) { return -LP_VERSION; }
-#else
 int lp_version(void) { return LP_VERSION; }
-#endif
 
 const char* lp_last_error(void) { return g_err; }
 
@@ -453,10 +449,6 @@ int lp_splatter_backward(const LpSplatterArgs* args_, void* stream) {
  * "tuned family, rays per wavefront", "tuned family, samples per wavefront (transposed march)", "layer-looped family",
  * "shape-generic kernels" (static strings) */
 const char* lp_debug_last_renderer_backward(void) { return g_last_backward; }
-
-/* developer hook (not part of include/lightplane_hip.h): per-phase cycle totals of the MFMA backward,
- * only in builds with -DLP_PHASE_TIMING (returns -1 otherwise) */
-int lp_debug_phase_cycles(unsigned long long* out16) { return debug_phase_cycles(out16); }
 
 static int check_ray_embed(const LpRayEmbedArgs& a, bool backward) {
   if (a.n_rays < 0) return set_error(LP_EINVAL, "n_rays %lld < 0", (long long)a.n_rays);

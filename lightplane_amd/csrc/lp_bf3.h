@@ -196,7 +196,7 @@ LP_DEV f32x16 layer_bf3v(const A& a, int lane, const float (&v)[8 * NCH], f32x16
   }
   return acc;
 }
-// ---- two-limb gradient operand of the dX chains (default; -DLP_DX_LIMBS=3 restores three limbs) ---------------------------
+// ---- two-limb gradient operand of the dX chains (default; layer_dxv<NCH, 3> keeps three limbs) -----------------------------
 // dX = W dY back-propagates a GRADIENT: dY is split into two limbs (16 significand bits, relative error 2^-17 per value), the
 // weights keep theirs; products kept: w1 y1, w2 y1, w1 y2 (dropped terms <= ~3 * 2^-17 |w y|, random in sign).  Half the MFMAs
 // of the dX chains and 24 instead of 44 split instructions per chunk: the tuned backward 2.03 -> 1.88 ms at cfg 2, 125.5 ->
@@ -209,9 +209,6 @@ LP_DEV f32x16 layer_bf3v(const A& a, int lane, const float (&v)[8 * NCH], f32x16
 // three limb products; measured on the same launch: 1.05e-5, profiles/r05_dw_bf16_ab.txt); the two-waves-per-SIMD shallow looped
 // kernels keep fp32 quadrants (v_mfma_f32_16x16x4_f32).  LpRendererArgs.arithmetic = LP_ARITH_FP32 selects, per call, instantiations
 // with three limbs in the dX chains and fp32 quadrants (the reference's arithmetic); lp_build_info() reports what was compiled.
-#ifndef LP_DX_LIMBS
-#define LP_DX_LIMBS 2
-#endif
 LP_DEV void split2_chunk(const float* v, u32x4_t& l1, u32x4_t& l2) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -291,7 +288,7 @@ LP_DEV f32x16 dx_chunk(const A& a, int c, int lane, const u32x4_t& l1, const u32
   if constexpr (DXL == 2) return chunk_bf2(a, c, lane, l1, l2, acc);
   else return chunk_bf3(a, c, lane, l1, l2, l3, acc);
 }
-template <int NCH, int DXL = LP_DX_LIMBS, class A>
+template <int NCH, int DXL = 2, class A>
 LP_DEV f32x16 layer_dxv(const A& a, int lane, const float (&v)[8 * NCH], f32x16 acc, char* trow = nullptr) {
   if constexpr (DXL == 2) return layer_bf2v<NCH>(a, lane, v, acc, trow);
   else return layer_bf3v<NCH>(a, lane, v, acc);

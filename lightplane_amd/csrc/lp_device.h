@@ -429,11 +429,6 @@ LP_DEV float scaffold_lookup(const float* scaffold, const LpGrid& s, int b, floa
 
 // softplus (torch: beta 1, linear above 20).  log1p(e) through the hardware log for e >= 2^-6 and
 // through its series below (|error| < 3e-8 there): a handful of VALU ops instead of libm's log1pf.
-#if defined(LP_X_RELU_F) || defined(LP_X_MASK_BIT_INT) || defined(LP_X_MASK_APPLY)
-#ifndef LP_EXPERIMENTS
-#error "LP_X_* are A/B timing switches: build them with -DLP_EXPERIMENTS (LP_BUILD_FLAGS), which makes lp_version() negative so that the binding refuses the library unless LIGHTPLANE_AMD_ALLOW_EXPERIMENTAL=1"
-#endif
-#endif
 LP_DEV float softplus_f(float x) {
   const float e = __expf(x);
   const float series = e * fmaf(e, fmaf(e, 0.333333343f, -0.5f), 1.0f);
@@ -451,33 +446,20 @@ LP_DEV float softplus_f(float x) {
 // -- the reference asserts isfinite on its gradients after every backward (lightplane_renderer.py:713-722) -- the kernels only
 // promise not to fault on them.  The shape-generic kernels use fmaxf (both NaNs -> 0).
 LP_DEV float relu_f(float x) {
-#ifdef LP_X_RELU_F
-  return fmaxf(x, 0.0f);
-#else
   const int i = __builtin_bit_cast(int, x);
   return __builtin_bit_cast(float, i > 0 ? i : 0);
-#endif
 }
 
 // ReLU masks as bits of one register (the backward keeps 16 activations' masks in 16 bits instead of 16 registers).
 // mask_bit: post-ReLU value -> bit q.  mask_apply: v if bit q is set else 0: v_bfe_i32 (sign-extends the bit to all ones) +
-// v_and_b32 instead of and + compare + select.
+// v_and_b32 instead of and + compare + select.  (mask_bit as two integer ops -- v_min_i32, v_lshl_or_b32 -- made the allocator of the
+// dominant backward kernel spill 19 values inside the sample loop instead of 2: scripts/isa_loop_scratch.py.)
 LP_DEV unsigned mask_bit(unsigned m, float relu_value, int q) {
-#ifdef LP_X_MASK_BIT_INT  // two integer ops (v_min_i32, v_lshl_or_b32) -- but with it the allocator of the dominant backward
-  // kernel spills 19 values inside the sample loop instead of 2 (scripts/isa_loop_scratch.py): off
-  const int i = __builtin_bit_cast(int, relu_value);
-  return m | ((unsigned)(i < 1 ? i : 1) << q);
-#else
   return m | ((relu_value > 0.0f) ? (1u << q) : 0u);
-#endif
 }
 LP_DEV float mask_apply(unsigned m, int q, float v) {
-#ifdef LP_X_MASK_APPLY
-  return (m & (1u << q)) ? v : 0.0f;
-#else
   const int all = ((int)(m << (31 - q))) >> 31;
   return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & all);
-#endif
 }
 
 // 1 / (1 + e^-x) with the hardware reciprocal (v_rcp_f32, 1 ulp) instead of an IEEE division (ten instructions):

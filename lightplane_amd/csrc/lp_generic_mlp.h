@@ -480,11 +480,7 @@ LP_DEV void accum(float* target, float v) {
   if (LDS_ACC)
     *target += v;  // each (i,o) entry is owned by exactly one lane
   else
-#ifdef LP_TIMING_GEN_NO_DW_ATOMICS  // timing experiment (wrong gradients): what the weight-gradient atomics to global memory cost
-    { if (v == 12345.678f) atomic_add_f32(target, v); }
-#else
     atomic_add_f32(target, v);
-#endif
 }
 
 // dW += X^T dY over the wave's 64 rays on the fp32 matrix cores: one v_mfma_f32_32x32x2_f32 per pair of rays and 32 x 32 block of

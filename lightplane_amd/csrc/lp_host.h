@@ -44,10 +44,7 @@ inline bool grid_list_rows_ok(const LpGridList& gl) {
 //    reference example's decoder (2/2/2 x 64) on 1 024 random rays 0.89 -> 0.56 ms per training step, 2/2/2 x 32 0.50 -> 0.35 ms; on
 //    4 096 rays, where 16-sample segments already give every CU a workgroup, 8-sample ones were 18 % SLOWER (0.73 -> 0.86 ms:
 //    profiles/r06_train_step.txt).
-// LP_SEG_BLOCKS (developer knob) forces the number of blocks.
 inline int seg_blocks_for(unsigned ray_blocks, int n_rec, unsigned resident) {
-  static const int forced = getenv("LP_SEG_BLOCKS") ? atoi(getenv("LP_SEG_BLOCKS")) : 0;
-  if (forced > 0) return forced < n_rec ? forced : n_rec;
   if (n_rec <= 1 || (uint64_t)ray_blocks * (uint64_t)n_rec <= 256u) return 1;
   int m = 2;
   while (m < n_rec && (uint64_t)ray_blocks * (uint64_t)((n_rec + m - 1) / m) > resident) m += 2;

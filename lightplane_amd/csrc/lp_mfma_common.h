@@ -42,7 +42,6 @@ struct MfmaParams {
   int64_t w_o1, w_o2, b_o1, b_o2;  // opacity
   int64_t w_c1, w_c2, b_c1, b_c2;  // colour
   int ldc2;                        // row stride of w_c2 (padded colour width)
-  int dbg;                         // LP_MFMA_DEBUG bits (timing experiments only)
   // shape flexibility of the width-32 family: actual hidden width (16 or 32; staged zero-padded to 32),
   // second trunk layer present, hidden layer of the opacity / colour head present
   int hid, t2, oh, ch;
@@ -321,11 +320,10 @@ LP_DEV void fetch_sample(const LpRendererArgs& a, const float* lds, const Ray& r
 constexpr int DX_LD = 36;  // row stride of the transposed dx0 tile [channel][ray]
 
 template <int C>
-LP_DEV void flush_run(float* gg, int s_row, unsigned s_ok, int koff, unsigned kbit, int sub, const float (&run)[C / 16],
-                      int dbg) {
+LP_DEV void flush_run(float* gg, int s_row, unsigned s_ok, int koff, unsigned kbit, int sub, const float (&run)[C / 16]) {
   // the run's row goes into the scalar base (64-bit: grid-lists of any size below 2^31 rows), the lane part -- this slot's corner
   // offset inside the cell, this lane's channel -- stays a 32-bit byte offset (a corner is at most one z-slice + one line away)
-  if ((s_ok & kbit) && !(dbg & 1)) {
+  if (s_ok & kbit) {
     char* const rb = reinterpret_cast<char*>(gg) + (int64_t)s_row * (C * 4);
     const unsigned lane_off = (unsigned)koff * (unsigned)(C * 4) + (unsigned)(sub * 4);
 #pragma unroll
@@ -346,7 +344,7 @@ LP_DEV void flush_run(float* gg, int s_row, unsigned s_ok, int koff, unsigned kb
 // instructions; starting a run with a multiply instead of zero + fma was 6 % SLOWER.)
 template <int C>
 LP_DEV void scatter_plane_ax(float* gg, int base, int U, AxisTap u, AxisTap v, bool live, int lane, const float* dxT,
-                             float* wT, int dbg) {
+                             float* wT) {
   constexpr int CPL = C / 16;
   const int h = lane >> 5, r = lane & 31, sub = lane & 15, grp = lane >> 4;
   int iu = u.i0, iv = v.i0;
@@ -373,7 +371,7 @@ LP_DEV void scatter_plane_ax(float* gg, int base, int U, AxisTap u, AxisTap v, b
   float run[CPL];
   int s_row = __builtin_amdgcn_readlane(row0, 0);
   auto flush = [&](int row) {
-    if (row >= 0 && !(dbg & 1)) {
+    if (row >= 0) {
       char* base = reinterpret_cast<char*>(gg) + (int64_t)row * (C * 4);  // scalar
 #pragma unroll
       for (int j = 0; j < CPL; ++j) atomic_add_f32(reinterpret_cast<float*>(base + lane_off + 64 * j), run[j]);
@@ -432,7 +430,7 @@ LP_DEV void scatter_plane_ax(float* gg, int base, int U, AxisTap u, AxisTap v, b
 // three planes here as well means three inlined copies of the walk instead of a loop: measured 2.5 % slower.
 template <int C>
 LP_DEV void scatter_plane(float* gg, const LpGrid& g, int b, float x, float y, float z, bool live, int lane,
-                          const float* dxT, float* wT, int dbg) {
+                          const float* dxT, float* wT) {
   const bool xy = g.D == 1, xz = g.H == 1;
   const float cu = (xy || xz) ? x : y;
   const float cv = xy ? y : z;
@@ -441,7 +439,7 @@ LP_DEV void scatter_plane(float* gg, const LpGrid& g, int b, float x, float y, f
   AxisTap u, v;
   axis_taps<false>(cu, U, u.i0, u.w, u.ok);
   axis_taps<false>(cv, V, v.i0, v.w, v.ok);
-  scatter_plane_ax<C>(gg, (int)g.row_offset + b * (U * V), U, u, v, live, lane, dxT, wT, dbg);
+  scatter_plane_ax<C>(gg, (int)g.row_offset + b * (U * V), U, u, v, live, lane, dxT, wT);
 }
 
 // Canonical triplane (GM_TRIPLANE), all three planes in one call.  What the per-plane walk above spent per plane BEFORE its ray
@@ -470,7 +468,7 @@ LP_DEV AxisNorm axis_norm(float c, int size) {
 }
 template <int C>
 LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b, float x, float y, float z, bool live, int lane,
-                             const float* dxT, float* wT, int dbg) {
+                             const float* dxT, float* wT) {
   constexpr int CPL = C / 16;
   const int h = lane >> 5, r = lane & 31, sub = lane & 15, grp = lane >> 4;
   const int W = gl.grids[0].W, H = gl.grids[0].H, D = gl.grids[1].D;
@@ -508,7 +506,7 @@ LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b,
     float run[CPL];
     int s_row = __builtin_amdgcn_readlane(row0, 0);
     auto flush = [&](int row) {
-      if (row >= 0 && !(dbg & 1)) {
+      if (row >= 0) {
         char* rb = reinterpret_cast<char*>(gg) + (int64_t)row * (C * 4);  // scalar
 #pragma unroll
         for (int j = 0; j < CPL; ++j) atomic_add_f32(reinterpret_cast<float*>(rb + lane_off + 64 * j), run[j]);
@@ -568,16 +566,16 @@ LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b,
 // footprint of its own, is 7 % faster with it)
 template <int C, int GMS = GM_GENERIC, bool COLS = true>
 LP_DEV void scatter_grid(float* gg, const LpGrid& g, int b, float x, float y, float z, bool live, int lane,
-                         const float* dxT, float* wT, int dbg) {
+                         const float* dxT, float* wT) {
   constexpr int CPL = C / 16;  // channels per lane
-  if (GMS == GM_TRIPLANE && !(dbg & 8)) {
-    scatter_plane<C>(gg, g, b, x, y, z, live, lane, dxT, wT, dbg);
+  if (GMS == GM_TRIPLANE) {
+    scatter_plane<C>(gg, g, b, x, y, z, live, lane, dxT, wT);
     return;
   }
-  if (COLS && GMS != GM_TRIPLANE && (GMS == GM_VOXEL || (g.D > 1 && g.H > 1 && g.W > 1)) && !(dbg & 4)) {
+  if (COLS && GMS != GM_TRIPLANE && (GMS == GM_VOXEL || (g.D > 1 && g.H > 1 && g.W > 1))) {
     // voxel grids: the column walk of lp_splat_walk.h (two columns per corner pair, one pass, half the atomics)
     splat_walk_vox<C, 32, SplatSrcLds, false>(gg, nullptr, g, b, x, y, z, live, lane, SplatSrcLds{dxT, DX_LD, lane & 15},
-                                              wT, dbg);
+                                              wT);
     return;
   }
   const int h = lane >> 5, r = lane & 31, sub = lane & 15, grp = lane >> 4;
@@ -626,7 +624,7 @@ LP_DEV void scatter_grid(float* gg, const LpGrid& g, int b, float x, float y, fl
           run[j] = fmaf(w.w, d.w, run[j]);
         }
       }
-      flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run, dbg);
+      flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run);
       continue;
     }
 #pragma unroll
@@ -644,7 +642,7 @@ LP_DEV void scatter_grid(float* gg, const LpGrid& g, int b, float x, float y, fl
       for (int i = 0; i < 8; ++i) {
         const int rr = 8 * c8 + i;
         if (rr > 0 && ((mask >> rr) & 1u)) {
-          flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run, dbg);
+          flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run);
 #pragma unroll
           for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
           s_row = __builtin_amdgcn_readlane(row0, rr);
@@ -655,7 +653,7 @@ LP_DEV void scatter_grid(float* gg, const LpGrid& g, int b, float x, float y, fl
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run, dbg);
+    flush_run<C>(gg, s_row, s_ok, koff, kbit, sub, run);
   }
 }
 
@@ -670,6 +668,5 @@ inline bool is_canonical_triplane(const LpGridList& gl) {
 
 // second-generation backward (lp_renderer_mfma_bwd.hip); gm = GM_* grid-list shape
 int renderer_backward_mfma2(const LpRendererArgs& a, const MfmaParams& mp, int gm, hipStream_t stream);
-int debug_phase_cycles(unsigned long long* out);  // developer builds with -DLP_PHASE_TIMING, else -1
 
 }  // namespace lp

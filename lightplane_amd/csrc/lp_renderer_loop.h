@@ -36,7 +36,6 @@ struct LoopParams {
   int ho_w, hc_w;                   // input widths of the two output layers
   int wo2, wc2, hb, inf;            // float offsets inside the small block
   int img_end;                      // bytes before the per-wave tiles
-  int dbg;
   // segment-parallel march of a small batch (LpRendererArgs.seg_prefix): LP_SEG_LEN-sample blocks per workgroup;
   // seg_fwd: this forward launch marches segments (segment-local state records, chained by renderer_fwd_combine)
   int seg_blocks, seg_fwd;
@@ -341,7 +340,7 @@ __global__ void __launch_bounds__(256, (NB == 1 && MT <= 2 && MH <= 1 && !WC) ? 
   // gradient operand of the dX chains: two limbs (lp_bf3.h) where the chain is short -- at most two trunk layers and one hidden
   // layer per head, i.e. the shallow and the two-block (hidden 64) instantiations; deep decoders keep three: the per-layer error
   // compounds along a 7-layer chain (4/2/3 x 32 on 70 rays x 15 samples: grad_mlp_params 1.05e-4 with two limbs)
-  constexpr int DXL = (MT <= 2 && MH <= 1) ? LP_DX_LIMBS : 3;
+  constexpr int DXL = (MT <= 2 && MH <= 1) ? 2 : 3;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   loop_stage<NB>(a, lp, lds);
   const float* const geo = lds + lp.inf - Lds::INF;
@@ -752,14 +751,14 @@ __global__ void __launch_bounds__(256, (NB == 1 && MT <= 2 && MH <= 1 && !WC) ? 
     if (TG) {
       // two-grid decoder: scatter d relu(colour feature) into the colour grid-list now, while the wave's tiles are idle
       // between two layer phases; the opacity branch then starts from zero
-      if (ggc && !(lp.dbg & 2)) {
+      if (ggc) {
         __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int q = 0; q < C / 2; ++q) xt[featq(q, h) * DX_LD + r] = (xc[q] > 0.0f) ? g[0][q] : 0.0f;
         const bool live_c = valid && on && !(a.march.mask_out_of_bounds && !point_in_bounds(x, y, z));
 #pragma unroll 1
         for (int gi = 0; gi < a.color_grid.n_grids; ++gi)
-          scatter_grid<C>(a.grad_color_grid_list[gi], a.color_grid.grids[gi], ray.b, x, y, z, live_c, lane, xt, yt, lp.dbg);
+          scatter_grid<C>(a.grad_color_grid_list[gi], a.color_grid.grids[gi], ray.b, x, y, z, live_c, lane, xt, yt);
         __builtin_amdgcn_s_setprio(1);
       }
 #pragma unroll
@@ -848,15 +847,15 @@ __global__ void __launch_bounds__(256, (NB == 1 && MT <= 2 && MH <= 1 && !WC) ? 
     const bool live = valid && on && !(a.march.mask_out_of_bounds && !point_in_bounds(x, y, z));
     if (s > s_lo) fetch_sample<C, GM, true>(a, geo, ray, s - 1, h, nx);
     LP_SCHED_FENCE();
-    if (gg && !(lp.dbg & 2)) {
+    if (gg) {
       const int ng = (GM == GM_TRIPLANE) ? 3 : a.grid.n_grids;
       float* const wtab = (C == 64) ? wv + T::WT : yt;
       if constexpr (GM == GM_TRIPLANE && C != 64) {  // all three planes in one call (its weight table needs 3 x 128 floats: the dY tile)
-        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, wtab, lp.dbg);
+        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, wtab);
       } else {
 #pragma unroll 1
         for (int gi = 0; gi < ng; ++gi)
-          scatter_grid<C, GM>(a.grad_grid_list[gi], a.grid.grids[gi], ray.b, x, y, z, live, lane, xt, wtab, lp.dbg);
+          scatter_grid<C, GM>(a.grad_grid_list[gi], a.grid.grids[gi], ray.b, x, y, z, live, lane, xt, wtab);
       }
     }
   }
@@ -948,8 +947,7 @@ static int launch_fwd_loop(const LpRendererArgs& a, const LoopParams& p, unsigne
   int rc;
   if constexpr (NB == 2 && !TG && !WC) {
     // images that exclude a second four-wave workgroup per CU (> 80 KB): eight-wave workgroups, one per CU, two waves per SIMD
-    static const bool no_nw8 = getenv("LP_LOOP_FWD_NW4") != nullptr;  // A/B
-    if (lds > 80 * 1024 && !no_nw8 && !p.seg_fwd) {
+    if (lds > 80 * 1024 && !p.seg_fwd) {
       const unsigned nb8 = (unsigned)((a.rays.n_rays + 8 * RAYS_PER_WAVE - 1) / (8 * RAYS_PER_WAVE));
       if constexpr (C <= 32) {
         if (tri) {

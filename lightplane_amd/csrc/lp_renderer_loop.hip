@@ -123,17 +123,14 @@ static LoopParams loop_params(const LpRendererArgs& a) {
   for (int l = 0; l < p.n_c; ++l) p.c[l].img += small_bytes;
   p.co.img += small_bytes;
   p.img_end = small_bytes + img;
-  static const int dbg = getenv("LP_MFMA_DEBUG") ? atoi(getenv("LP_MFMA_DEBUG")) : 0;
-  p.dbg = dbg;
   p.seg_blocks = 1;
   p.seg_fwd = 0;
   p.relu_dump = g_relu_dump;  // test hook (NULL in every product call)
   p.dump_words = NB * ((tg ? 2 : p.n_t) + p.n_o + p.n_c) + 1;
-  // the two-block backward's third tile (loop_layer_bwd): when the images leave the room  (LP_LOOP_NO_ZTILE: A/B)
-  static const bool no_z = getenv("LP_LOOP_NO_ZTILE") != nullptr;
+  // the two-block backward's third tile (loop_layer_bwd): when the images leave the room
   p.tile_stride = LoopTile::PER_WAVE;
   p.z_delta = 0;
-  if (NB == 2 && !no_z && (size_t)p.img_end + (size_t)WAVES * (LoopTile::PER_WAVE + LoopTile::Z_EXTRA) * 4 <= 160 * 1024) {
+  if (NB == 2 && (size_t)p.img_end + (size_t)WAVES * (LoopTile::PER_WAVE + LoopTile::Z_EXTRA) * 4 <= 160 * 1024) {
     p.tile_stride = LoopTile::PER_WAVE + LoopTile::Z_EXTRA;
     p.z_delta = (LoopTile::ZT - LoopTile::YT) * 4;
   }
@@ -148,17 +145,16 @@ int renderer_loop_dump_words(const LpRendererArgs& a) { return loop_params(a).du
 // (128 rays, segment) fills it.  Not with 5..32 colour channels (the state records hold four colour sums).
 // (A shallow decoder's backward -- lp_renderer_loop_shallow.hip -- runs two workgroups per CU like the tuned family's: 512
 // workgroups = 65 536 rays fill the chip, and the tuned family's threshold of 32 768 rays applies.)
-static bool loop_is_shallow(const LpRendererArgs& a) {
+// LP_LOOP_NO_SHALLOW (tests): the deep one-wave-per-SIMD instantiations for every shape.
+static bool loop_is_shallow(const LpRendererArgs& a, const LoopParams& p) {
   static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;
-  const LoopParams p = loop_params(a);
   return loop_nb(p.hid, a.grid.channels) == 1 && a.color_chn <= 4 && p.n_t <= 2 && p.n_o <= 1 && p.n_c <= 1 && !no_shallow;
 }
 int renderer_loop_segments(const LpRendererArgs& a) {
-  static const int forced = getenv("LP_SEGMENTS") ? atoi(getenv("LP_SEGMENTS")) : -1;
-  if (forced == 0 || a.march.num_samples_inf != 0 || a.stop_neg_log_t > 0.0f || a.color_chn > 4) return 1;
+  if (a.march.num_samples_inf != 0 || a.stop_neg_log_t > 0.0f || a.color_chn > 4) return 1;
   const int n_seg = (a.march.num_samples + LP_SEG_LEN - 1) / LP_SEG_LEN;
   if (n_seg < 2) return 1;
-  if (forced < 0 && a.rays.n_rays > (loop_is_shallow(a) ? 32768 : 24576)) return 1;
+  if (a.rays.n_rays > (loop_is_shallow(a, loop_params(a)) ? 32768 : 24576)) return 1;
   return n_seg;
 }
 
@@ -177,10 +173,6 @@ bool renderer_loop_fits(const LpRendererArgs& a) {
   return loop_lds_bytes(loop_params(a), true) <= 160 * 1024;
 }
 
-static bool loop_triplane(const LpRendererArgs& a) {
-  static const bool generic_grids = getenv("LP_MFMA_GENERIC_GRIDS") != nullptr;  // debugging aid
-  return !generic_grids && is_canonical_triplane(a.grid);
-}
 
 int renderer_forward_loop(const LpRendererArgs& a, hipStream_t stream) {
   unsigned nb = loop_blocks(a);
@@ -195,7 +187,7 @@ int renderer_forward_loop(const LpRendererArgs& a, hipStream_t stream) {
     nb *= (unsigned)((n_rec + p.seg_blocks - 1) / p.seg_blocks);
   }
   const size_t lds = loop_lds_bytes(p, false);
-  const bool tg = a.color_grid.n_grids > 0, wc = a.color_chn > 4, tri = loop_triplane(a);
+  const bool tg = a.color_grid.n_grids > 0, wc = a.color_chn > 4, tri = is_canonical_triplane(a.grid);
   const int NB = loop_nb(p.hid, a.grid.channels);
   int rc = LP_OK;
 #define LP_LOOP_FWD(CV, NBV, TGV, WCV) rc = launch_fwd_loop<CV, NBV, TGV, WCV>(a, p, nb, lds, tri, stream)
@@ -228,20 +220,18 @@ int renderer_backward_loop(const LpRendererArgs& a, hipStream_t stream) {
   LoopParams p = loop_params(a);
   if (a.seg_prefix && a.color_chn <= 4) {  // small batch: one workgroup per (128 rays, segment)
     const int n_rec = (a.march.num_samples + LP_SEG_LEN - 1) / LP_SEG_LEN;
-    p.seg_blocks = loop_seg_blocks(a, nb, loop_is_shallow(a) ? 512u : 256u);
+    p.seg_blocks = loop_seg_blocks(a, nb, loop_is_shallow(a, p) ? 512u : 256u);
     nb *= (unsigned)((n_rec + p.seg_blocks - 1) / p.seg_blocks);
   }
   const size_t lds = loop_lds_bytes(p, true);
-  const bool tg = a.color_grid.n_grids > 0, wc = a.color_chn > 4, tri = loop_triplane(a);
+  const bool tri = is_canonical_triplane(a.grid);
   const int NB = loop_nb(p.hid, a.grid.channels);
   int rc = LP_OK;
-  static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;  // A/B: the deep one-wave-per-SIMD instantiations for every shape
-  if (NB == 1 && !wc && p.n_t <= 2 && p.n_o <= 1 && p.n_c <= 1 && !no_shallow) {
+  if (loop_is_shallow(a, p)) {
     rc = p.relu_dump ? renderer_backward_loop_shallow_dump(a, p, nb, lds, tri, stream) : renderer_backward_loop_shallow(a, p, nb, lds, tri, stream);
     if (rc) return rc;
     return check_launch("renderer_bwd_loop (shallow)");
   }
-  (void)tg;
   rc = p.relu_dump ? renderer_backward_loop_deep_dump(a, p, NB, nb, lds, tri, stream) : loop_bwd_table_deep<false>(a, p, NB, nb, lds, tri, stream);
   if (rc) return rc;
   return check_launch("renderer_bwd_loop");
@@ -249,9 +239,7 @@ int renderer_backward_loop(const LpRendererArgs& a, hipStream_t stream) {
 
 // what this translation unit's backward computes in (lp_build_info)
 const char* build_info_loop_deep() {
-#define LP_STR2(x) #x
-#define LP_STR(x) LP_STR2(x)
-  return "{\"dx_limbs\": \"" LP_STR(LP_DX_LIMBS) " (two-block / <= 2 trunk + 1 hidden head layers), 3 (deeper chains)\", \"dw\": "
+  return "{\"dx_limbs\": \"2 (two-block / <= 2 trunk + 1 hidden head layers), 3 (deeper chains)\", \"dw\": "
 #if LP_LOOP_DW_BF16
          "\"two-limb bf16 operands, v_mfma_f32_16x16x32_bf16\"}";
 #else

@@ -21,9 +21,7 @@ int renderer_backward_loop_shallow(const LpRendererArgs& a, const LoopParams& p,
 
 // what this translation unit's backward computes in (lp_build_info)
 const char* build_info_loop_shallow() {
-#define LP_STR2(x) #x
-#define LP_STR(x) LP_STR2(x)
-  return "{\"dx_limbs\": " LP_STR(LP_DX_LIMBS) ", \"dw\": "
+  return "{\"dx_limbs\": 2, \"dw\": "
 #if LP_LOOP_DW_BF16
          "\"two-limb bf16 operands, v_mfma_f32_16x16x32_bf16\"}";
 #else

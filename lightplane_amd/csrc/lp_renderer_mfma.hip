@@ -252,18 +252,15 @@ __global__ void __launch_bounds__(256, 3) renderer_fwd_bf3_tm(const LpRendererAr
 
 // forward + backward of these arguments may march samples per wavefront
 bool renderer_tm_eligible(const LpRendererArgs& a) {
-  static const bool off = getenv("LP_TM_OFF") != nullptr;  // A/B
-  return !off && a.march_order == LP_MARCH_SAMPLES_PER_WAVE && a.march.num_samples_inf == 0 && !(a.stop_neg_log_t > 0.0f) &&
+  return a.march_order == LP_MARCH_SAMPLES_PER_WAVE && a.march.num_samples_inf == 0 && !(a.stop_neg_log_t > 0.0f) &&
          a.march.num_samples >= 32;
 }
 
 // rays per wave of the transposed march: 32 once the batch fills one round of resident workgroups; a smaller batch is spread over
 // the chip (measured on 65 536 random rays, fwd + bwd: 32 rays per wave 7.15 ms, 16: 7.52, 8: 7.78, 4: 8.86 -- profiles/r06_transposed_march.txt)
 int renderer_tm_rays_per_wave(const LpRendererArgs& a, int resident_workgroups) {
-  static const int forced = getenv("LP_TM_RPW") ? atoi(getenv("LP_TM_RPW")) : 0;
   int rpw = RAYS_PER_WAVE;
   while (rpw > 1 && (a.rays.n_rays + WAVES * rpw - 1) / (WAVES * rpw) < resident_workgroups) rpw >>= 1;
-  if (forced >= 1 && forced <= RAYS_PER_WAVE) rpw = forced;
   return rpw;
 }
 
@@ -341,8 +338,6 @@ static MfmaParams make_params(const LpRendererArgs& a) {
   p.w_c2 = p.w_c1 + (p.ch ? p.hin * H : 0);
   p.b_c1 = p.w_c2 + (int64_t)(p.ch ? H : p.hin) * p.ldc2;
   p.b_c2 = p.b_c1 + (p.ch ? H : 0);
-  static const int dbg = getenv("LP_MFMA_DEBUG") ? atoi(getenv("LP_MFMA_DEBUG")) : 0;
-  p.dbg = dbg;
   p.seg_blocks = 1;
   p.seg_fwd = 0;
   p.relu_dump = g_relu_dump;
@@ -356,7 +351,6 @@ static MfmaParams make_params(const LpRendererArgs& a) {
 // idle (a 4-wave workgroup per 128 rays, two workgroups per CU: 65 536 rays fill the chip once).  Measured on MI355X
 // (scripts/bench_small_batch.py, S = 128, backward kernel): 4 096 rays 1.80 -> 0.51 ms, 16 384 rays 1.80 -> 0.88 ms,
 // 32 768 rays 1.75 -> 1.53 ms, 49 152 rays 2.12 -> 2.22 ms: on up to 32 768 rays.
-// LP_SEGMENTS=0 / 1 switches it off / on regardless of the batch size (A/B, tests).
 // LP_ARITH_FP32 instantiations exist for four-wave workgroups (<= 64 beyond-far samples), one sweep per ray
 bool renderer_mfma_f32_supported(const LpRendererArgs& a) {
   const char* why = "";
@@ -364,20 +358,17 @@ bool renderer_mfma_f32_supported(const LpRendererArgs& a) {
 }
 
 int renderer_mfma_segments(const LpRendererArgs& a) {
-  static const int forced = getenv("LP_SEGMENTS") ? atoi(getenv("LP_SEGMENTS")) : -1;
-  if (forced == 0 || a.arithmetic != LP_ARITH_DEFAULT) return 1;
+  if (a.arithmetic != LP_ARITH_DEFAULT) return 1;
   if (renderer_tm_eligible(a)) return 1;  // the transposed march deals a small batch over the chip by rays per wave: no segments
   if (a.march.num_samples_inf != 0 || a.stop_neg_log_t > 0.0f) return 1;
   const int n_seg = (a.march.num_samples + LP_SEG_LEN - 1) / LP_SEG_LEN;
   if (n_seg < 2) return 1;
-  if (forced < 0 && a.rays.n_rays > 32768) return 1;
+  if (a.rays.n_rays > 32768) return 1;
   return n_seg;
 }
 
 static int grid_mode(const LpRendererArgs& a) {
   auto is_voxel = [](const LpGrid& g) { return g.D > 1 && g.H > 1 && g.W > 1; };
-  static const bool force_generic = getenv("LP_MFMA_GENERIC_GRIDS") != nullptr;  // debugging aid
-  if (force_generic) return GM_GENERIC;
   if (a.grid.n_grids == 1 && is_voxel(a.grid.grids[0])) return GM_VOXEL;
   if (is_canonical_triplane(a.grid)) return GM_TRIPLANE;
   return GM_GENERIC;
@@ -397,14 +388,13 @@ static unsigned n_blocks(const LpRendererArgs& a) {
 template <int C, int GM>
 static int launch_fwd(const LpRendererArgs& a, const MfmaParams& mp, hipStream_t stream) {
   int rc;
-  static const bool no_nc3 = getenv("LP_MFMA_NO_NC3") != nullptr;  // A/B knob
-  static const bool tm_fwd_off = getenv("LP_TM_FWD_OFF") != nullptr;  // A/B: transposed backward, rays-per-wavefront forward
-  if (renderer_tm_eligible(a) && !tm_fwd_off) {  // samples per wavefront (batches of unrelated rays)
+  const bool nc3 = a.color_chn <= 3;
+  if (renderer_tm_eligible(a)) {  // samples per wavefront (batches of unrelated rays)
     MfmaParams mt = mp;
     mt.tm_rpw = renderer_tm_rays_per_wave(a, 768);  // (three workgroups per CU)
     const size_t lds3 = (size_t)LdsBf3<C>::FWD_END;
     const unsigned nb = (unsigned)((a.rays.n_rays + WAVES * mt.tm_rpw - 1) / (WAVES * mt.tm_rpw));
-    if (a.color_chn <= 3 && !no_nc3) {
+    if (nc3) {
       if ((rc = set_lds(renderer_fwd_bf3_tm<C, GM, 3>, lds3))) return rc;
       hipLaunchKernelGGL((renderer_fwd_bf3_tm<C, GM, 3>), dim3(nb), dim3(256), lds3, stream, a, mt);
     } else {
@@ -427,7 +417,7 @@ static int launch_fwd(const LpRendererArgs& a, const MfmaParams& mp, hipStream_t
       const int m = seg_blocks_for(n_blocks(a), n_rec, 512u);
       ms.seg_blocks = m;
       const unsigned nb = n_blocks(a) * (unsigned)((n_rec + m - 1) / m);
-      if (a.color_chn <= 3 && !no_nc3) {
+      if (nc3) {
         if ((rc = set_lds(renderer_fwd_bf3<C, GM, 2, 3, true>, lds3))) return rc;
         hipLaunchKernelGGL((renderer_fwd_bf3<C, GM, 2, 3, true>), dim3(nb), dim3(256), lds3, stream, a, ms);
       } else {
@@ -442,9 +432,7 @@ static int launch_fwd(const LpRendererArgs& a, const MfmaParams& mp, hipStream_t
       if ((rc = set_lds(renderer_fwd_bf3<C, GM, OCCV, NCV>, lds3))) return rc;                                   \
       hipLaunchKernelGGL((renderer_fwd_bf3<C, GM, OCCV, NCV>), dim3(n_blocks(a)), dim3(256), lds3, stream, a, mp); \
     } while (0)
-    const bool nc3 = a.color_chn <= 3 && !no_nc3;
-    if (occ >= 4 && C == 16) { if (nc3) LP_BF3_LAUNCH(4, 3); else LP_BF3_LAUNCH(4, 4); }
-    else if (occ == 3 || occ >= 4) { if (nc3) LP_BF3_LAUNCH(3, 3); else LP_BF3_LAUNCH(3, 4); }
+    if (occ >= 3) { if (nc3) LP_BF3_LAUNCH(3, 3); else LP_BF3_LAUNCH(3, 4); }
     else { if (nc3) LP_BF3_LAUNCH(2, 3); else LP_BF3_LAUNCH(2, 4); }
 #undef LP_BF3_LAUNCH
     return LP_OK;

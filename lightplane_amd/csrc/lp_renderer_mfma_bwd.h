@@ -27,23 +27,6 @@ namespace lp {
 
 #ifdef LP_ASM_MARKS
 #define LP_MARK(n) asm volatile("; LPMARK " n)
-#elif defined(LP_PHASE_TIMING)
-// developer build (-DLP_PHASE_TIMING): per-phase shader-clock totals of the sample loop, summed over
-// all waves into g_phase[] (read with lp_debug_phase_cycles)
-static __device__ unsigned long long g_phase[16];  // (one copy per translation unit: lp_debug_phase_cycles reads the C = 16 unit's)
-__device__ constexpr int phase_id(const char* n) {
-  return n[0] == 'f' && n[1] == 'w' ? 0 : n[0] == 'c' && n[1] == 'o' ? 1 : n[0] == 'h' ? 2 : n[0] == 'c' ? 3
-       : n[0] == 'o' ? 4 : n[0] == 't' && n[1] == '2' ? 5 : n[0] == 't' ? 6 : n[0] == 'f' ? 7 : n[0] == 's' ? 8 : 9;
-}
-#define LP_MARK(n)                                                     \
-  {                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                 \
-    const unsigned long long t_now = __builtin_readcyclecounter();     \
-    ph[ph_cur] += t_now - t_last;                                      \
-    t_last = t_now;                                                    \
-    ph_cur = phase_id(n);                                              \
-    __builtin_amdgcn_sched_barrier(0);                                 \
-  }
 #else
 #define LP_MARK(n)
 #endif
@@ -93,7 +76,7 @@ LP_DEV f32x4 dw_quadrant(const float* wave0, int a_off, int b_off, int v0, int v
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Weight gradients on the bf16 pipe (round 5; default with LP_DX_LIMBS == 2, -DLP_DW_FP32 keeps the fp32 quadrants above).
+// Weight gradients on the bf16 pipe (round 5; the F32 instantiations keep the fp32 quadrants above).
 // The fp32 16x16x4 products are 32 cycles each that no VALU instruction overlaps (112 per wave-sample = 22 % of the SIMD's
 // time).  Here the PRODUCER lanes publish two-limb bf16 tiles [ray][feature] -- the dY limbs are the ones the dX chain forms
 // anyway (layer_bf2v's `trow`), the X limbs cost one two-limb split per activation (limb_tile_store, 24 VALU per chunk) -- and
@@ -140,11 +123,6 @@ LP_DEV f32x4 dw_quadrant_bf(const char* wave0b, int x_off, int y_off, int v0, in
   }
   return acc;
 }
-#if LP_DX_LIMBS == 2 && !defined(LP_DW_FP32)
-#define LP_DW_BF16 1
-#else
-#define LP_DW_BF16 0
-#endif
 
 // =======================================================================================
 // Backward of the default shape with the recompute and the dX chains as bf16x3 on the bf16 matrix cores (lp_bf3.h).
@@ -187,11 +165,11 @@ struct Bf3Lds {
 // written to mp.relu_dump -- the same instruction sequence computes them, only the stores are added.
 // F32 (LpRendererArgs.arithmetic == LP_ARITH_FP32): three limbs for the gradient operand of the dX chains and fp32 weight-gradient
 // quadrants (v_mfma_f32_16x16x4_f32 on fp32 tiles) -- the reference's arithmetic, selectable per call; the default instantiations
-// take two limbs in both (LP_DX_LIMBS, LP_DW_BF16).
+// take two limbs in both.
 template <int C, int GM, bool PLAIN, int NC, int NW, bool SEG = false, bool DUMP = false, bool F32 = false>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(const LpRendererArgs a, const MfmaParams mp) {
-  constexpr int DXL = F32 ? 3 : LP_DX_LIMBS;          // limbs of the gradient operand of the dX chains
-  constexpr bool DWB = !F32 && (LP_DW_BF16 != 0);     // weight gradients on the bf16 pipe (two-limb tiles)
+  constexpr int DXL = F32 ? 3 : 2;  // limbs of the gradient operand of the dX chains
+  constexpr bool DWB = !F32;        // weight gradients on the bf16 pipe (two-limb tiles)
   using M = Lds;
   using L = LdsBf3<C>;
   using R = LdsBf3Rm<C>;
@@ -288,7 +266,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
   const int m16 = lane & 15, ka = lane >> 4;
   const int a_off = B::XT + (16 * mi + pi16(m16)) * T_LD + 8 * ka;
   const int b_off = B::YT + (16 * ni + pi16(m16)) * T_LD + 8 * ka;
-  // bf16 dW (LP_DW_BF16): the limb tiles [ray][feature] alias the X / dY tile areas; this lane publishes row rho(r) of its wave's
+  // bf16 dW (DWB): the limb tiles [ray][feature] alias the X / dY tile areas; this lane publishes row rho(r) of its wave's
   // tiles, and as MFMA lane (m16, ka) it supplies rows rho(8 ka + (m16 >> 2)) [+ 4], columns f0 + 4 (m16 & 3) .. +3 of a source wave's
   // (rho: see dw_quadrant_bf -- with rows in ray order every limb-tile write was a 2-way bank conflict, 128 LDS cycles per sample)
   auto rho = [](int k) { return (k & 0x15) | ((k & 2) << 2) | ((k & 8) >> 2); };
@@ -308,11 +286,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
   float dbo2 = 0.0f, dbc2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   const bool gg = a.grad_grid_list[0] != nullptr;
 
-#ifdef LP_PHASE_TIMING
-  unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t_last = __builtin_readcyclecounter();
-  int ph_cur = 9;
-#endif
   float nlt = a.neg_log_t[rid];
   // d loss / d (opacity delta)_s = T_s p_s - sum_{i > s} w_i p_i, p_i = g_len depth_i + sum_c g_c colour_ic: the running
   // `suffix` carries the second term; a segment starts it from the sums the forward saved behind its last sample
@@ -637,28 +610,20 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     if (s > s_lo) fetch_sample<C, GM, true, PLAIN>(a, sm, ray, s - 1, h, nx);
     LP_SCHED_FENCE();
     LP_MARK("scatter");
-    if (gg && !(mp.dbg & 2)) {
-#ifndef LP_SCATTER_V1
+    if (gg) {
       if constexpr (GM == GM_TRIPLANE) {
-        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, yt, mp.dbg);
-      } else
-#endif
-      {
-        const int ng = (GM == GM_TRIPLANE) ? 3 : (GM == GM_VOXEL) ? 1 : a.grid.n_grids;
+        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, yt);
+      } else {
+        const int ng = (GM == GM_VOXEL) ? 1 : a.grid.n_grids;
 #pragma unroll 1
         for (int g = 0; g < ng; ++g)
-          scatter_grid<C, GM>(a.grad_grid_list[g], a.grid.grids[g], ray.b, x, y, z, live, lane, xt, yt, mp.dbg);
+          scatter_grid<C, GM>(a.grad_grid_list[g], a.grid.grids[g], ray.b, x, y, z, live, lane, xt, yt);
       }
     }
   }
 
   // ---------------- epilogue ----------------
   LP_MARK("epilogue");
-#ifdef LP_PHASE_TIMING
-  if (lane == 0) {
-    for (int i = 0; i < 10; ++i) atomicAdd(&g_phase[i], ph[i]);
-  }
-#endif
   // d enc = W_c1 D ; dW_c1 += enc (x) D   (one product each, after the sweep)
   {
     f32x16 acc;
@@ -784,7 +749,7 @@ template <int C, int GM, bool PLAIN, int NC>
 static int launch_bwd3(const LpRendererArgs& a, const MfmaParams& mp, hipStream_t stream) {
   // segment-parallel sweep of a small batch (seg_prefix survives lp_api.hip only where renderer_mfma_segments() > 1)
   if (a.seg_prefix) return launch_bwd3w<C, GM, PLAIN, NC, 4, true>(a, mp, stream);
-  // four-wave workgroups (two per CU) unless the beyond-far table does not fit their small block; LP_BF3_NW=8 for A/B
+  // four-wave workgroups (two per CU) unless the beyond-far table does not fit their small block; LP_BF3_NW=4 / 8 (tests) forces one
   static const int forced = getenv("LP_BF3_NW") ? atoi(getenv("LP_BF3_NW")) : 0;
   const bool nw4 = forced ? forced == 4 : a.march.num_samples_inf <= LdsBf3Rm<C>::N_INF;
   return nw4 ? launch_bwd3w<C, GM, PLAIN, NC, 4>(a, mp, stream) : launch_bwd3w<C, GM, PLAIN, NC, 8>(a, mp, stream);
@@ -799,8 +764,7 @@ static int launch_bwd2(const LpRendererArgs& a, const MfmaParams& mp, hipStream_
                    // e.g. scripts/kernel_resources.py lp_renderer_mfma_bwd.hip -DLP_DEV_ONE
   return launch_bwd3w<C, GM, true, 3, 4>(a, mp, stream);
 #else
-  static const bool no_nc3 = getenv("LP_MFMA_NO_NC3") != nullptr;  // A/B knob
-  if (a.color_chn <= 3 && !no_nc3)  // RGB: the padding column of the colour path is compiled out
+  if (a.color_chn <= 3)  // RGB: the padding column of the colour path is compiled out
     return plain ? launch_bwd3<C, GM, true, 3>(a, mp, stream) : launch_bwd3<C, GM, false, 3>(a, mp, stream);
   return plain ? launch_bwd3<C, GM, true, 4>(a, mp, stream) : launch_bwd3<C, GM, false, 4>(a, mp, stream);
 #endif
@@ -827,6 +791,5 @@ int renderer_bwd_bf3_dump(const LpRendererArgs& a, const MfmaParams& mp, int gm,
 // transposed march (LP_MARCH_SAMPLES_PER_WAVE): lp_renderer_mfma_bwd_tm.hip
 bool renderer_bwd_tm_supported(const LpRendererArgs& a);
 int renderer_bwd_bf3_tm_launch(const LpRendererArgs& a, const MfmaParams& mp, int gm, hipStream_t stream);
-int debug_phase_cycles_c32(unsigned long long* out);  // developer builds with -DLP_PHASE_TIMING (the 32-channel unit's g_phase), else -1
 
 }  // namespace lp

@@ -30,34 +30,9 @@ int renderer_backward_mfma2(const LpRendererArgs& a, const MfmaParams& mp, int g
 
 // what the tuned backward of this binary computes in (lp_build_info)
 const char* build_info_tuned_bwd() {
-#define LP_STR2(x) #x
-#define LP_STR(x) LP_STR2(x)
-  return "{\"dx_limbs\": " LP_STR(LP_DX_LIMBS) ", \"dw\": "
-#if LP_DW_BF16
-         "\"two-limb bf16 operands, v_mfma_f32_16x16x32_bf16, three limb products\""
-#else
-         "\"fp32 operands, v_mfma_f32_16x16x4_f32\""
-#endif
+  return "{\"dx_limbs\": 2, \"dw\": \"two-limb bf16 operands, v_mfma_f32_16x16x32_bf16, three limb products\""
          ", \"recompute\": \"bf16x3, v_mfma_f32_32x32x16_bf16, six limb products\", \"arith_fp32\": \"dx_limbs 3, dw fp32 "
          "v_mfma_f32_16x16x4_f32 (four-wave workgroups, <= 64 beyond-far samples)\"}";
 }
-
-#ifdef LP_PHASE_TIMING
-int debug_phase_cycles(unsigned long long* out) {
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return set_error((int)e, "sync: %s", hipGetErrorString(e));
-  e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16);
-  if (e != hipSuccess) return set_error((int)e, "from symbol: %s", hipGetErrorString(e));
-  unsigned long long z[16] = {0};
-  e = hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z));
-  if (e != hipSuccess) return set_error((int)e, "to symbol: %s", hipGetErrorString(e));
-  unsigned long long c32[16];  // (g_phase exists once per translation unit: add the 32-channel unit's totals)
-  if (debug_phase_cycles_c32(c32) == 0)
-    for (int i = 0; i < 16; ++i) out[i] += c32[i];
-  return 0;
-}
-#else
-int debug_phase_cycles(unsigned long long*) { return -1; }
-#endif
 
 }  // namespace lp

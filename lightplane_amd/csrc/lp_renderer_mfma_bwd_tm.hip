@@ -424,14 +424,14 @@ __global__ void __launch_bounds__(256, 2) renderer_bwd_bf3_tm(const LpRendererAr
     // ---------------- next iteration's samples + grid gradient of this one ----------------
     if (it + 1 < n_it) fetch_sample<C, GM, true, PLAIN>(a, sm, ray, sample_of(bs), h, nx);
     LP_SCHED_FENCE();
-    if (gg && !(mp.dbg & 2)) {
+    if (gg) {
       if constexpr (GM == GM_TRIPLANE) {
-        scatter_triplane<C>(a.grad_grid_list, a.grid, b_cur, x, y, z, live, lane, xt, yt, mp.dbg);
+        scatter_triplane<C>(a.grad_grid_list, a.grid, b_cur, x, y, z, live, lane, xt, yt);
       } else {
         const int ng = (GM == GM_VOXEL) ? 1 : a.grid.n_grids;
 #pragma unroll 1
         for (int g = 0; g < ng; ++g)
-          scatter_grid<C, GM>(a.grad_grid_list[g], a.grid.grids[g], b_cur, x, y, z, live, lane, xt, yt, mp.dbg);
+          scatter_grid<C, GM>(a.grad_grid_list[g], a.grid.grids[g], b_cur, x, y, z, live, lane, xt, yt);
       }
     }
   }

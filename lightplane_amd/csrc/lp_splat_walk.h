@@ -40,7 +40,7 @@ struct SplatSrcLds {  // tile [channel][ld] in LDS
 // per run (about eight runs per 16 rays).  row0 / iu: per-lane values of the wave's rays (lane r = ray r), mask: run heads.
 template <int RPW, int WLD>
 LP_DEV void splat_walk_vox_weights(float* wgt, const LpGrid& g, int row0, int iu, int sv_, int st_, unsigned mask, int lane,
-                                   const float* wT, int dbg) {
+                                   const float* wT) {
   const int sub = lane & 15, grp = lane >> 4;
   struct { int sv, st; } tp = {sv_, st_};
   {
@@ -58,7 +58,6 @@ LP_DEV void splat_walk_vox_weights(float* wgt, const LpGrid& g, int row0, int iu
     int wb = ((s_iu & 15) == 15) ? s_iu : (s_iu & ~15);  // window base (x of lane sub == 0)
     int rowb = s_row - s_iu;                              // row of x = 0 in the (y0, z0) line of the window
     bool m0 = (wb + sub) == s_iu, m1 = (wb + sub) == s_iu + 1;
-    const bool on = !(dbg & 2);
 #pragma unroll
     for (int c8 = 0; c8 < RPW / 8; ++c8) {
       const float4 a0 = wlo[2 * c8], a1 = wlo[2 * c8 + 1], b0 = whi[2 * c8], b1 = whi[2 * c8 + 1];
@@ -86,12 +85,12 @@ LP_DEV void splat_walk_vox_weights(float* wgt, const LpGrid& g, int row0, int iu
               const bool along_y = dl == tp.sv || dl == -tp.sv;
               const int side = along_y ? (grp & 1) : (grp >> 1);      // this lane's corner bit along the stepping axis
               const bool behind = side == (dl > 0 ? 0 : 1);
-              if (behind && acc != 0.0f && xl >= 0 && xl < W && on) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
+              if (behind && acc != 0.0f && xl >= 0 && xl < W) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
               const float other = __shfl_xor(acc, along_y ? 16 : 32);
               acc = behind ? other : 0.0f;                            // (the lanes left behind take over the line that stays)
               rowb += dl;
             } else {
-              if (acc != 0.0f && xl >= 0 && xl < W && on) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
+              if (acc != 0.0f && xl >= 0 && xl < W) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
               acc = 0.0f;
               wb = ((n_iu & 15) == 15) ? n_iu : (n_iu & ~15);
               rowb = n_row - n_iu;
@@ -104,7 +103,7 @@ LP_DEV void splat_walk_vox_weights(float* wgt, const LpGrid& g, int row0, int iu
       }
     }
     const int xl = wb + sub;
-    if (acc != 0.0f && xl >= 0 && xl < W && on) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
+    if (acc != 0.0f && xl >= 0 && xl < W) atomic_add_f32(wgt + (int64_t)(rowb + koff + xl), acc);
   }
 }
 
@@ -123,7 +122,7 @@ LP_DEV void splat_walk_vox_weights(float* wgt, const LpGrid& g, int row0, int iu
 // (k_lo in {0,2,4,6}, {0,1,4,5}, {0,1,2,3}) on distinct 16-byte bank slots; callers whose table has the room pass it.
 template <int C, int RPW, class Src, bool SPLAT = true, int WLD = RPW>
 LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live,
-                           int lane, const Src& src, float* wT, int dbg) {
+                           int lane, const Src& src, float* wT) {
   constexpr int CPL = C / 16;
   constexpr int NQ = 64 / RPW;
   constexpr int SPQ = 8 / NQ;
@@ -147,7 +146,7 @@ LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, floa
   const int prow_ = lane_prev(row0), pok_ = lane_prev(ok);  // all lanes enabled: see run_head()
   const bool head = run_head(r, row0, prow_, ok, pok_);
   const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(head));
-  if (!(dbg & 64)) {
+  {
     // merge axis A (wave-uniform): the axis of the first cell change of this walk
     int A = 0;
     if (mask & ~1u) {
@@ -178,7 +177,6 @@ LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, floa
     int s_row = __builtin_amdgcn_readlane(row0, 0);
     int s_cell = __builtin_amdgcn_readlane(cell, 0);
     unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
-    const bool on = !(dbg & 1);
 #pragma unroll
     for (int c8 = 0; c8 < RPW / 8; ++c8) {
       const float4 a0 = wlo[2 * c8], a1 = wlo[2 * c8 + 1], b0 = whi[2 * c8], b1 = whi[2 * c8 + 1];
@@ -206,13 +204,13 @@ LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, floa
           asm volatile("" : "+s"(up), "+s"(down));
           float* const rowp = feat + (int64_t)s_row * C;  // (wave-uniform: scalar base + per-lane 32-bit offset)
           if (down != 0) {  // the near column is left behind
-            if ((s_ok & bit_lo) && on) {
+            if (s_ok & bit_lo) {
 #pragma unroll
               for (int j = 0; j < CPL; ++j) atomic_add_f32(rowp + lane_off + 16 * j, lo[j]);
             }
           }
           if (up != 0) {  // the far column is left behind
-            if ((s_ok & bit_hi) && on) {
+            if (s_ok & bit_hi) {
 #pragma unroll
               for (int j = 0; j < CPL; ++j) atomic_add_f32(rowp + hi_off + lane_off + 16 * j, hi[j]);
             }
@@ -237,17 +235,17 @@ LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, floa
       __builtin_amdgcn_sched_barrier(0);
     }
     float* const rowp = feat + (int64_t)s_row * C;
-    if ((s_ok & bit_lo) && on) {
+    if (s_ok & bit_lo) {
 #pragma unroll
       for (int j = 0; j < CPL; ++j) atomic_add_f32(rowp + lane_off + 16 * j, lo[j]);
     }
-    if ((s_ok & bit_hi) && on) {
+    if (s_ok & bit_hi) {
 #pragma unroll
       for (int j = 0; j < CPL; ++j) atomic_add_f32(rowp + hi_off + lane_off + 16 * j, hi[j]);
     }
   }
-  if (!SPLAT || (dbg & 32)) return;  // the Renderer's gradient scatter has no weight grid  (dbg & 32 / 64: timing experiments)
-  splat_walk_vox_weights<RPW, WLD>(wgt, g, row0, iu, tp.sv, tp.st, mask, lane, wT, dbg);
+  if (!SPLAT) return;  // the Renderer's gradient scatter has no weight grid
+  splat_walk_vox_weights<RPW, WLD>(wgt, g, row0, iu, tp.sv, tp.st, mask, lane, wT);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -264,7 +262,7 @@ LP_DEV void splat_walk_vox(float* feat, float* wgt, const LpGrid& g, int b, floa
 // the second pass through the step code costs every run head a loop).
 template <int C, int RPW, int WLD, class Enc, bool DIAG = false>
 LP_DEV void splat_walk_vox_feat2(float* feat, const LpGrid& g, int row0, int cell, int ok, int su, int sv, int st, unsigned mask,
-                                 int lane, const Enc& enc, const float* wT, int dbg) {
+                                 int lane, const Enc& enc, const float* wT) {
   static_assert(C % 32 == 0, "32 channels per lane group");
   constexpr int CPL = C / 32;
   const int ch = lane & 31, gc = lane >> 5;
@@ -326,7 +324,6 @@ LP_DEV void splat_walk_vox_feat2(float* feat, const LpGrid& g, int row0, int cel
 #pragma unroll
     for (int b = 0; b < 2; ++b) wrow[a][b] = reinterpret_cast<const float4*>(wT + (k00 + a * bA + b * bB) * WLD);
   const unsigned lane_off = (unsigned)(gc * sX * C + ch);
-  const bool on = !(dbg & 1);
   float acc[2][2][CPL];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -337,7 +334,7 @@ LP_DEV void splat_walk_vox_feat2(float* feat, const LpGrid& g, int row0, int cel
   int s_row = __builtin_amdgcn_readlane(row0, 0);
   unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
   auto flush = [&](int a, int b) {  // column (a, b) of the cell at s_row leaves the registers
-    if ((s_ok & bit[a][b]) && on) {
+    if (s_ok & bit[a][b]) {
       float* const rowp = feat + ((int64_t)s_row + a * sA + b * sB) * C;  // (wave-uniform base + per-lane 32-bit offset)
 #pragma unroll
       for (int j = 0; j < CPL; ++j) atomic_add_f32(rowp + lane_off + 32 * j, acc[a][b][j]);
@@ -416,7 +413,7 @@ LP_DEV void splat_walk_vox_feat2(float* feat, const LpGrid& g, int row0, int cel
 // (Enc: enc[j][i] = channel (lane & 31) + 32 j of item i -- a register array [C / 32][RPW], or SplatEncConst for the transposed march)
 template <int C, int RPW, int WLD, class Enc, bool DIAG = false>
 LP_DEV void splat_walk_vox2(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live, int lane,
-                            const Enc& enc, float* wT, int dbg) {
+                            const Enc& enc, float* wT) {
   constexpr int NQ = 64 / RPW;
   constexpr int SPQ = 8 / NQ;
   const int q = lane / RPW, r = lane % RPW;
@@ -438,9 +435,8 @@ LP_DEV void splat_walk_vox2(float* feat, float* wgt, const LpGrid& g, int b, flo
   const int prow_ = lane_prev(row0), pok_ = lane_prev(ok);  // all lanes enabled: see run_head()
   const bool head = run_head(r, row0, prow_, ok, pok_);
   const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(head));
-  if (!(dbg & 64)) splat_walk_vox_feat2<C, RPW, WLD, Enc, DIAG>(feat, g, row0, tp.cell, ok, tp.su, tp.sv, tp.st, mask, lane, enc, wT, dbg);
-  if (dbg & 32) return;
-  splat_walk_vox_weights<RPW, WLD>(wgt, g, row0, tp.iu, tp.sv, tp.st, mask, lane, wT, dbg);
+  splat_walk_vox_feat2<C, RPW, WLD, Enc, DIAG>(feat, g, row0, tp.cell, ok, tp.su, tp.sv, tp.st, mask, lane, enc, wT);
+  splat_walk_vox_weights<RPW, WLD>(wgt, g, row0, tp.iu, tp.sv, tp.st, mask, lane, wT);
 }
 
 }  // namespace lp

@@ -68,8 +68,7 @@ __global__ void __launch_bounds__(256) splat_fwd_kernel(const LpSplatterArgs a) 
 // bit mask (ballot in the lane = ray layout): the walk is scalar-branched, tap rows come from
 // v_readlane.  Same scheme as the Renderer's gradient scatter (lp_mfma_common.h).
 // ---------------------------------------------------------------------------------------
-// RPW rays per wave (16: twice as many waves in flight for the same ray count -- the walk is a
-// latency-bound scalar loop, and 256x256 rays are only 2048 waves of 32).
+// RPW rays per wave: 32 (C = 16 / 32), 16 (C = 64), 32 samples of one ray in the transposed march.
 // (Enc: enc[j][item] -- a register array [C / 16][RPW] of the wave's rays, or SplatEncConst for the transposed march)
 template <int CPL>
 struct SplatEncConst {
@@ -79,7 +78,7 @@ struct SplatEncConst {
 };
 template <int C, int RPW, class Enc>
 LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live,
-                       int lane, const Enc& enc, float* wT, int dbg) {
+                       int lane, const Enc& enc, float* wT) {
   constexpr int CPL = C / 16;        // channels per lane: 16 lanes per tap slot, four slots per pass
   constexpr int NQ = 64 / RPW;       // lanes per ray in the lane = ray layout
   constexpr int SPQ = 8 / NQ;        // tap-weight slots each of them writes
@@ -123,7 +122,7 @@ LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x,
       for (int i = 0; i < 8; ++i) {
         const int rr = 8 * c8 + i;
         if (rr > 0 && ((mask >> rr) & 1u)) {
-          if ((s_ok & kbit) && !(dbg & 1)) {
+          if (s_ok & kbit) {
 #pragma unroll
             for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
           }
@@ -137,7 +136,7 @@ LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x,
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if ((s_ok & kbit) && !(dbg & 1)) {
+    if (s_ok & kbit) {
 #pragma unroll
       for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
     }
@@ -160,7 +159,7 @@ LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x,
       for (int i = 0; i < 8; ++i) {
         const int rr = 8 * c8 + i;
         if (rr > 0 && ((mask >> rr) & 1u)) {
-          if ((s_ok & kbit) && !(dbg & 2)) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
+          if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
           runw = 0.0f;
           s_row = __builtin_amdgcn_readlane(row0, rr);
           s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
@@ -168,14 +167,14 @@ LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x,
         runw += w[i];
       }
     }
-    if ((s_ok & kbit) && !(dbg & 2)) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
+    if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
   }
 }
 
 // W2 (all output grids voxel grids, C a multiple of 32): the voxel walk with two carry axes (splat_walk_vox2, lp_splat_walk.h) --
 // lane = channel of 32, lane group = corner along the third axis
 template <int C, int RPW, bool W2 = false>
-__global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArgs a, int dbg, int n_seg, int grp) {
+__global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArgs a, int n_seg, int grp) {
   constexpr int LD = RPW + 4;  // row stride of the transposed encoding tile [channel][ray]
   constexpr int NQ = 64 / RPW;
   constexpr int CPL = C / 16;
@@ -223,14 +222,8 @@ __global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArg
   const int s_tot = a.march.num_samples + a.march.num_samples_inf;
   const bool contract = a.march.contract_coords != 0;
   const bool mask = a.march.mask_out_of_bounds != 0;
-  // segment `seg` takes the samples seg, seg + n_seg, ...: interleaved, not a contiguous range (splat_forward_segments() on the host);
-  // (dbg & 8: contiguous ranges, the A/B)
-  const bool interleaved = !(dbg & 8);
-  const int per_seg = (s_tot + n_seg - 1) / n_seg;
-  const int s_lo = interleaved ? seg : seg * per_seg;
-  const int s_hi = interleaved ? s_tot : ((s_lo + per_seg < s_tot) ? s_lo + per_seg : s_tot);
-  const int s_step = interleaved ? n_seg : 1;
-  for (int s = s_lo; s < s_hi; s += s_step) {
+  // segment `seg` takes the samples seg, seg + n_seg, ...: interleaved, not a contiguous range (splat_forward_segments() on the host)
+  for (int s = seg; s < s_tot; s += n_seg) {
     const float depth = sample_depth(s, a.march, ray.near_t, ray.far_t);
     float x, y, z;
     sample_point(ray, depth, contract, x, y, z);
@@ -238,12 +231,12 @@ __global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArg
     for (int g = 0; g < a.out.n_grids; ++g) {
       const LpGrid& og = a.out.grids[g];
       if constexpr (W2) {
-        splat_walk_vox2<C, RPW, WLD, float[NJ][RPW]>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT, dbg);
+        splat_walk_vox2<C, RPW, WLD, float[NJ][RPW]>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
       } else {
-        if (og.D > 1 && og.H > 1 && og.W > 1 && !(dbg & 4))
-          splat_walk_vox<C, RPW, SplatSrcRegs<CPL, RPW>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, SplatSrcRegs<CPL, RPW>{enc}, wT, dbg);
+        if (og.D > 1 && og.H > 1 && og.W > 1)
+          splat_walk_vox<C, RPW, SplatSrcRegs<CPL, RPW>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, SplatSrcRegs<CPL, RPW>{enc}, wT);
         else
-          splat_walk<C, RPW>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT, dbg);
+          splat_walk<C, RPW>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
       }
     }
   }
@@ -258,7 +251,7 @@ __global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArg
 // W2 (all output grids voxel grids, 32 / 64 channels): the voxel walk with two carry axes -- a ray steps along all three grid axes in
 // the proportions of its direction, one carry axis catches the dominant one only
 template <int C, bool W2 = false>
-__global__ void __launch_bounds__(256) splat_fwd_ray_kernel(const LpSplatterArgs a, int dbg, int rpw) {
+__global__ void __launch_bounds__(256) splat_fwd_ray_kernel(const LpSplatterArgs a, int rpw) {
   constexpr int LPG = W2 ? 32 : 16;
   constexpr int CPL = C / LPG;
   constexpr int WLD = 32 + 8;
@@ -289,12 +282,12 @@ __global__ void __launch_bounds__(256) splat_fwd_ray_kernel(const LpSplatterArgs
       for (int g = 0; g < a.out.n_grids; ++g) {
         const LpGrid& og = a.out.grids[g];
         if constexpr (W2) {
-          splat_walk_vox2<C, 32, WLD, SplatEncConst<CPL>, true>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT, dbg);
+          splat_walk_vox2<C, 32, WLD, SplatEncConst<CPL>, true>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
         } else {
-          if (og.D > 1 && og.H > 1 && og.W > 1 && !(dbg & 4))
-            splat_walk_vox<C, 32, SplatSrcConst<CPL>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, src, wT, dbg);
+          if (og.D > 1 && og.H > 1 && og.W > 1)
+            splat_walk_vox<C, 32, SplatSrcConst<CPL>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, src, wT);
           else
-            splat_walk<C, 32>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT, dbg);
+            splat_walk<C, 32>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
         }
       }
     }
@@ -351,9 +344,9 @@ __global__ void __launch_bounds__(256) splat_bwd_kernel(const LpSplatterArgs a) 
 // eight rays are issued before the first one is used.  The four corner pairs of a ray are summed across the
 // lane groups at the end.  (The per-ray kernel below re-derives the geometry in every lane and reads eight rows
 // per ray and sample.)
-// RPW = rays per wave: 16 (default), or 8 -- half the per-lane accumulators and batch buffers, so twice the waves fit a SIMD
+// RPW = rays per wave: 8 (round 4; 16 before) -- half the per-lane accumulators and batch buffers, so twice the waves fit a SIMD
 // and twice the gathers are in flight, for the price of the per-sample geometry being amortised over 8 rays instead of 16
-// (LP_SPLAT_BWD_RPW, measured in DESIGN.md 4.4).
+// (measured in DESIGN.md 4.4).
 // The 64 / RPW lanes of a ray each take ONE SAMPLE of a block of 64 / RPW consecutive samples (round 6): the per-sample geometry
 // (depth, point, tap set: ~60 % of the instructions of a VALU-bound kernel when every lane of a ray repeated it for the same sample)
 // is computed once per (ray, sample); the walk then goes through the block's samples, reading the tap rows of sample j from the lanes
@@ -366,10 +359,12 @@ __global__ void __launch_bounds__(256) splat_bwd_kernel(const LpSplatterArgs a) 
 #ifndef LP_SBW_OCC16
 #define LP_SBW_OCC16 4
 #endif
-template <int C, int B, int RPW = 16>
-__global__ void __launch_bounds__(256, RPW == 8 ? (C < 32 ? LP_SBW_OCC16 : (C < 64 ? LP_SBW_OCC32 : 2)) : ((B == 4 && C < 64) ? 3 : 2))
+// (B = batch of rays read together, RPW = rays per wave: both 8.  They stay template parameters because the body is written in
+// terms of them, and the kernel keeps the name splat_bwd_walk_kernel<C, 8, 8> that the profiles and traces of earlier rounds use.)
+template <int C, int B, int RPW>
+__global__ void __launch_bounds__(256, C < 32 ? LP_SBW_OCC16 : (C < 64 ? LP_SBW_OCC32 : 2))
 splat_bwd_walk_kernel(const LpSplatterArgs a, int n_seg) {
-  static_assert(RPW == 16 || (RPW == 8 && B == 8), "rays per wave: 16, or 8 with one batch of 8");
+  static_assert(RPW == 8 && B == 8, "rays per wave: 8, in one batch of 8");
   constexpr int CPL = C / 16, NQ = 64 / RPW;
   __shared__ __attribute__((aligned(16))) float lds[4][NQ * 8 * RPW];  // per wave: [sample of the block][tap][ray]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -548,14 +543,13 @@ __global__ void __launch_bounds__(256) hash_randn_kernel(const int32_t* x1, cons
 
 // Small batches (BACKWARD): a wave marches its rays one sample after the other, so fewer than ~16 k rays leave most of the chip idle.
 // The samples of a ray are independent in the Splatter, so the march is cut into segments of at least 16 samples, as many
-// as bring the launch to ~3 workgroups per CU (LP_SPLAT_SEGMENTS=1 switches it off).  Walk kernels on MI355X, 256 samples
+// as bring the launch to ~3 workgroups per CU.  Walk kernels on MI355X, 256 samples
 // into a 128^3 x 32 grid (scripts/bench_small_batch.py --splatter, profiles/r02_small_batch.txt): 4 096 rays backward
 // 1.19 -> 0.23 ms; 16 384 rays 1.16 -> 0.81 ms; at 32 768 rays (512 ray blocks) two segments no longer pay (1.17 -> 1.29 ms),
 // hence the 768.
 static int splat_segments(const LpSplatterArgs& a, unsigned ray_blocks) {
-  static const int forced = getenv("LP_SPLAT_SEGMENTS") ? atoi(getenv("LP_SPLAT_SEGMENTS")) : 0;
   const int s_tot = a.march.num_samples + a.march.num_samples_inf;
-  int n = forced > 0 ? forced : (int)(768u / (ray_blocks ? ray_blocks : 1u));
+  int n = (int)(768u / (ray_blocks ? ray_blocks : 1u));
   if (n > s_tot / 16) n = s_tot / 16;
   return n < 1 ? 1 : n;
 }
@@ -570,69 +564,54 @@ static int splat_segments(const LpSplatterArgs& a, unsigned ray_blocks) {
 //     phases and a phase of the whole batch is short;
 //   * ray-block-major (the segments of a ray block side by side): right for grids far beyond the caches (cfg 5, 256^3 x 32 = 2.15 GB:
 //     forward 149.8 -> 139.4 ms; segment-major 157) and for very large batches (1024^2 rays: every phase re-reads all encodings).
-// Measured on nine image / grid shapes; the rule below picks the faster order on each.  LP_SPLAT_FWD_SEGMENTS / LP_SPLAT_FWD_GROUP: A/B.
+// Measured on nine image / grid shapes; the rule below picks the faster order on each.
 static int splat_forward_segments(const LpSplatterArgs& a) {
-  static const int forced = getenv("LP_SPLAT_FWD_SEGMENTS") ? atoi(getenv("LP_SPLAT_FWD_SEGMENTS")) : 0;
   const int s_tot = a.march.num_samples + a.march.num_samples_inf;
-  int n = forced > 0 ? forced : s_tot / 8;
-  if (forced <= 0 && n > 32) n = 32;
+  int n = s_tot / 8;
+  if (n > 32) n = 32;
   if (n > s_tot) n = s_tot;
   return n < 1 ? 1 : n;
 }
 // ray blocks per launch group: inside a group the workgroups are issued segment after segment (group = every ray block: segment-major;
 // group = 1: ray-block-major)
 static int splat_forward_group(const LpSplatterArgs& a, unsigned ray_blocks) {
-  static const int forced = getenv("LP_SPLAT_FWD_GROUP") ? atoi(getenv("LP_SPLAT_FWD_GROUP")) : 0;
-  if (forced > 0) return forced;
   const double grid_bytes = (double)a.out.n_rows * (double)a.out.channels * 4.0;
   return (grid_bytes <= 1.0e9 && ray_blocks <= 4096u) ? (int)ray_blocks : 1;
 }
 
 int splatter_forward_launch(const LpSplatterArgs& a, hipStream_t stream) {
   const int Cw = a.out.channels;
-  static const bool no_walk = getenv("LP_SPLAT_NO_WALK") != nullptr;  // A/B timing knob
-  if ((Cw == 16 || Cw == 32 || Cw == 64) && a.out.n_rows < ((int64_t)1 << 31) && !no_walk) {
-    // 32 rays per wave since round 4 (C = 16 / 32): the per-sample geometry is amortised over twice the rays and a run is cut at every
-    // 32nd ray instead of every 16th -- cfg 3 forward 2.26 -> 2.15 ms, cfg 5's splat forward 155.6 -> 149.4 ms
-    // (profiles/r04_splat_fwd_rpw32_ab.txt); LP_SPLAT_RPW=16 selects the 16-ray waves (A/B, tests)
-    static const int rpw = getenv("LP_SPLAT_RPW") ? atoi(getenv("LP_SPLAT_RPW")) : 32;
-    static const int dbg = getenv("LP_SPLAT_DEBUG") ? atoi(getenv("LP_SPLAT_DEBUG")) : 0;  // timing experiments
-    static const bool tm_off = getenv("LP_TM_OFF") != nullptr;
-    if (a.march_order == LP_MARCH_SAMPLES_PER_WAVE && !tm_off) {  // batches of unrelated rays: one ray x 32 samples per wavefront
+  if ((Cw == 16 || Cw == 32 || Cw == 64) && a.out.n_rows < ((int64_t)1 << 31)) {
+    // voxel grids only, 32 / 64 channels: the walk with two carry axes
+    bool all_voxel = true;
+    for (int g = 0; g < a.out.n_grids; ++g) all_voxel = all_voxel && a.out.grids[g].D > 1 && a.out.grids[g].H > 1 && a.out.grids[g].W > 1;
+    if (a.march_order == LP_MARCH_SAMPLES_PER_WAVE) {  // batches of unrelated rays: one ray x 32 samples per wavefront
       if (a.rays.n_rays == 0) return LP_OK;
-      static const int forced = getenv("LP_TM_RPW") ? atoi(getenv("LP_TM_RPW")) : 0;
       int rays_pw = 32;  // (rays per wave: fewer while the batch leaves workgroup slots idle -- 4 workgroups per CU)
       while (rays_pw > 1 && (a.rays.n_rays + 4 * rays_pw - 1) / (4 * rays_pw) < 1024) rays_pw >>= 1;
-      if (forced >= 1 && forced <= 32) rays_pw = forced;
       const unsigned blocks = (unsigned)((a.rays.n_rays + 4 * rays_pw - 1) / (4 * rays_pw));
-      static const bool walk2r = getenv("LP_SPLAT_WALK2") == nullptr || atoi(getenv("LP_SPLAT_WALK2")) != 0;
-      bool all_vox = walk2r && !(dbg & 4);
-      for (int g = 0; g < a.out.n_grids; ++g) all_vox = all_vox && a.out.grids[g].D > 1 && a.out.grids[g].H > 1 && a.out.grids[g].W > 1;
-      if (all_vox && Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64, true>), dim3(blocks), dim3(256), 0, stream, a, dbg, rays_pw);
-      else if (all_vox && Cw == 32) hipLaunchKernelGGL((splat_fwd_ray_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, a, dbg, rays_pw);
-      else if (Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64>), dim3(blocks), dim3(256), 0, stream, a, dbg, rays_pw);
-      else if (Cw == 32) hipLaunchKernelGGL((splat_fwd_ray_kernel<32>), dim3(blocks), dim3(256), 0, stream, a, dbg, rays_pw);
-      else hipLaunchKernelGGL((splat_fwd_ray_kernel<16>), dim3(blocks), dim3(256), 0, stream, a, dbg, rays_pw);
+      if (all_voxel && Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64, true>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
+      else if (all_voxel && Cw == 32) hipLaunchKernelGGL((splat_fwd_ray_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
+      else if (Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
+      else if (Cw == 32) hipLaunchKernelGGL((splat_fwd_ray_kernel<32>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
+      else hipLaunchKernelGGL((splat_fwd_ray_kernel<16>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
       return check_launch("splat_fwd_ray_kernel");
     }
-    const int rpw_eff = Cw == 64 ? 16 : rpw;
-    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * rpw_eff - 1) / (4 * rpw_eff));
+    // 32 rays per wave since round 4 (C = 16 / 32): the per-sample geometry is amortised over twice the rays and a run is cut at every
+    // 32nd ray instead of every 16th -- cfg 3 forward 2.26 -> 2.15 ms, cfg 5's splat forward 155.6 -> 149.4 ms
+    // (profiles/r04_splat_fwd_rpw32_ab.txt).  (64 channels -- the reference's own speed benchmark splats into [1,160,160,160,64] --:
+    // 16 rays per wave, four channels per lane.)
+    const int rpw = Cw == 64 ? 16 : 32;
+    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * rpw - 1) / (4 * rpw));
     if (ray_blocks == 0) return LP_OK;
     const int n_seg = splat_forward_segments(a);
     const unsigned blocks = ray_blocks * (unsigned)n_seg;
     const int grp = splat_forward_group(a, ray_blocks);
-    // (64 channels -- the reference's own speed benchmark splats into [1,160,160,160,64] -- : four channels per lane)
-    // voxel grids only, 32 / 64 channels: the walk with two carry axes  (LP_SPLAT_WALK2=0: the one-axis walk, A/B)
-    static const bool walk2 = getenv("LP_SPLAT_WALK2") == nullptr || atoi(getenv("LP_SPLAT_WALK2")) != 0;
-    bool all_voxel = walk2 && !(dbg & 4);
-    for (int g = 0; g < a.out.n_grids; ++g) all_voxel = all_voxel && a.out.grids[g].D > 1 && a.out.grids[g].H > 1 && a.out.grids[g].W > 1;
-    if (all_voxel && Cw == 64) hipLaunchKernelGGL((splat_fwd_walk_kernel<64, 16, true>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else if (all_voxel && Cw == 32 && rpw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 32, true>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else if (Cw == 64) hipLaunchKernelGGL((splat_fwd_walk_kernel<64, 16>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else if (Cw == 16 && rpw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<16, 32>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else if (Cw == 16) hipLaunchKernelGGL((splat_fwd_walk_kernel<16, 16>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else if (rpw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 32>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
-    else hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 16>), dim3(blocks), dim3(256), 0, stream, a, dbg, n_seg, grp);
+    if (all_voxel && Cw == 64) hipLaunchKernelGGL((splat_fwd_walk_kernel<64, 16, true>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
+    else if (all_voxel && Cw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 32, true>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
+    else if (Cw == 64) hipLaunchKernelGGL((splat_fwd_walk_kernel<64, 16>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
+    else if (Cw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 32>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
+    else hipLaunchKernelGGL((splat_fwd_walk_kernel<16, 32>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
     return check_launch("splat_fwd_walk_kernel");
   }
   LP_SPLAT_DISPATCH(splat_fwd_kernel);
@@ -641,24 +620,20 @@ int splatter_forward_launch(const LpSplatterArgs& a, hipStream_t stream) {
 
 int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream) {
   const int Cw = a.out.channels;
-  static const bool no_walk = getenv("LP_SPLAT_NO_WALK") != nullptr;  // A/B timing knob
   // (plane grids take the same walk: their tap sets have four slots, so the two lane groups of the second z layer see
   // validity bits and weights of zero and contribute nothing -- half the lanes idle, but a run of rays still reads its
   // rows once instead of once per ray)
-  if ((Cw == 16 || Cw == 32 || Cw == 64) && a.out.n_grids > 0 && a.out.n_rows < ((int64_t)1 << 31) && !no_walk) {
+  if ((Cw == 16 || Cw == 32 || Cw == 64) && a.out.n_grids > 0 && a.out.n_rows < ((int64_t)1 << 31)) {
     // 8 rays per wave (round 4): cfg 3 backward 2.32 -> 2.01 ms -- 146 instead of 210 registers (C = 32), three waves per SIMD
-    // instead of two, i.e. 1.5x the gathers in flight of a latency-bound walk; LP_SPLAT_BWD_RPW=16 selects the 16-ray waves
-    static const int rpw = getenv("LP_SPLAT_BWD_RPW") ? atoi(getenv("LP_SPLAT_BWD_RPW")) : 8;
-    const int rpw_eff = rpw == 8 ? 8 : 16;
-    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * rpw_eff - 1) / (4 * rpw_eff));
+    // instead of two, i.e. 1.5x the gathers in flight of a latency-bound walk
+    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * 8 - 1) / (4 * 8));
     if (ray_blocks == 0) return LP_OK;
-    int n_seg = splat_segments(a, rpw_eff == 8 ? (ray_blocks + 1) / 2 : ray_blocks);
+    int n_seg = splat_segments(a, (ray_blocks + 1) / 2);
     // Mid-sized batches: fill whole rounds of resident waves.  cfg 3 = 8 192 waves of 8 rays on 3 072 wave slots (C = 32: three waves
     // per SIMD) = 2.67 rounds, the last one a third empty; three segments make it exactly 8 rounds: backward 2.04 -> 1.94 ms (2 or 4
     // segments, 5.33 / 10.67 rounds: 2.18 / 2.21 ms -- profiles/r04_knob_sweep.txt).  Among 1, 2, 3, 4, 6 segments the fewest that bring
     // the last round to >= 90 % full, for launches of up to 16 rounds (beyond that the tail does not matter).
-    static const int forced_seg = getenv("LP_SPLAT_SEGMENTS") ? atoi(getenv("LP_SPLAT_SEGMENTS")) : 0;
-    if (n_seg == 1 && forced_seg <= 0) {
+    if (n_seg == 1) {
       static int n_simd = 0;
       if (n_simd == 0) {
         int dev = 0, cus = 0;
@@ -669,12 +644,11 @@ int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream) {
       // resident workgroups per CU (= waves per SIMD: four-wave workgroups) of the instantiation that will run, asked from
       // the runtime once per instantiation (C = 16 / 32 / 64 at 8 rays per wave: 4 / 3 / 2 with this compiler) -- not a table
       // that has to track the register allocator
-      const int ki = (Cw == 16 ? 0 : Cw == 32 ? 1 : 2) + (rpw_eff == 8 ? 0 : 3);
-      static int occ_cache[6] = {0, 0, 0, 0, 0, 0};
+      const int ki = Cw == 16 ? 0 : Cw == 32 ? 1 : 2;
+      static int occ_cache[3] = {0, 0, 0};
       if (occ_cache[ki] == 0) {
         const void* kfn = ki == 0 ? (const void*)splat_bwd_walk_kernel<16, 8, 8> : ki == 1 ? (const void*)splat_bwd_walk_kernel<32, 8, 8>
-                        : ki == 2 ? (const void*)splat_bwd_walk_kernel<64, 8, 8> : ki == 3 ? (const void*)splat_bwd_walk_kernel<16, 8>
-                        : ki == 4 ? (const void*)splat_bwd_walk_kernel<32, 8> : (const void*)splat_bwd_walk_kernel<64, 4>;
+                                  : (const void*)splat_bwd_walk_kernel<64, 8, 8>;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 256, 0) != hipSuccess || nb < 1) nb = 2;
         occ_cache[ki] = nb > 8 ? 8 : nb;
@@ -695,20 +669,16 @@ int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream) {
       }
     }
     // (With n_seg > 1 the segments of a ray ADD their partial grad_encoding with fp32 atomics: the sum's order, hence its last
-    // bits, vary from run to run -- like every grid / parameter gradient of this library.  LP_SPLAT_SEGMENTS=1 restores the
-    // single-writer, bit-reproducible form.)
+    // bits, vary from run to run -- like every grid / parameter gradient of this library.)
     if (n_seg > 1) {  // the segments accumulate into grad_encoding
       const hipError_t e = hipMemsetAsync(a.grad_encoding, 0, (size_t)a.rays.n_rays * Cw * sizeof(float), stream);
       if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync(grad_encoding): %s", hipGetErrorString(e));
     }
     const unsigned blocks = ray_blocks * (unsigned)n_seg;
     // batches of 8 rays; batches of 4 at three waves/SIMD measured the same (cfg 3)
-    if (Cw == 16 && rpw_eff == 8) hipLaunchKernelGGL((splat_bwd_walk_kernel<16, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
-    else if (Cw == 32 && rpw_eff == 8) hipLaunchKernelGGL((splat_bwd_walk_kernel<32, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
-    else if (Cw == 64 && rpw_eff == 8) hipLaunchKernelGGL((splat_bwd_walk_kernel<64, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
-    else if (Cw == 16) hipLaunchKernelGGL((splat_bwd_walk_kernel<16, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
-    else if (Cw == 32) hipLaunchKernelGGL((splat_bwd_walk_kernel<32, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
-    else hipLaunchKernelGGL((splat_bwd_walk_kernel<64, 4>), dim3(blocks), dim3(256), 0, stream, a, n_seg);  // (batches of 8: 300 B of scratch)
+    if (Cw == 16) hipLaunchKernelGGL((splat_bwd_walk_kernel<16, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
+    else if (Cw == 32) hipLaunchKernelGGL((splat_bwd_walk_kernel<32, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
+    else hipLaunchKernelGGL((splat_bwd_walk_kernel<64, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
     return check_launch("splat_bwd_walk_kernel");
   }
   LP_SPLAT_DISPATCH(splat_bwd_kernel);

@@ -24,9 +24,8 @@ struct SplatLoopParams {
   int inf;                     // float offset of the beyond-far table in the small block
   int img_end;                 // bytes before the per-wave tiles
   int n_seg;                   // segments the march is cut into (blockIdx = (ray block, segment))
-  int fwd_group;               // forward: > 0 = INTERLEAVED samples per segment (g, g + n_seg, ...), issued in groups of this many ray
-                               // blocks segment after segment (lp_splatter.hip, splat_forward_segments / _group); 0 = contiguous ranges
-  int dbg;
+  int fwd_group;               // forward: INTERLEAVED samples per segment (g, g + n_seg, ...), issued in groups of this many ray
+                               // blocks segment after segment (lp_splatter.hip, splat_forward_segments / _group)
 };
 
 // per-wave LDS area (floats): two [32][36] tiles, contiguous (together: the [64][36] dx tile of a 64-channel input grid),
@@ -192,7 +191,7 @@ __global__ void __launch_bounds__(64 * NW, 2) splat_mlp_fwd_loop(const LpSplatte
   float* const vt = wv + T::XT;
   float* const wT = wv + T::WT;
   // (ray block, segment): the plain Splatter's forward launch shape (splat_fwd_walk_kernel) -- interleaved samples, grouped issue order
-  const int grp = sp.fwd_group > 0 ? sp.fwd_group : 1;
+  const int grp = sp.fwd_group;
   const int n_blk = (int)gridDim.x / sp.n_seg;
   const int per_group = grp * sp.n_seg;
   const int gi = (int)blockIdx.x / per_group, gl = (int)blockIdx.x - gi * per_group;
@@ -207,12 +206,7 @@ __global__ void __launch_bounds__(64 * NW, 2) splat_mlp_fwd_loop(const LpSplatte
   sloop_load_encoding<E>(a, rid, h, enc);
   const int s_tot = a.march.num_samples + a.march.num_samples_inf;
   const bool mask = a.march.mask_out_of_bounds != 0;
-  const bool interleaved = sp.fwd_group > 0;
-  const int per_seg = (s_tot + sp.n_seg - 1) / sp.n_seg;
-  const int s_lo = interleaved ? seg : seg * per_seg;
-  const int s_hi = interleaved ? s_tot : ((s_lo + per_seg < s_tot) ? s_lo + per_seg : s_tot);
-  const int s_step = interleaved ? sp.n_seg : 1;
-  for (int s = s_lo; s < s_hi; s += s_step) {
+  for (int s = seg; s < s_tot; s += sp.n_seg) {
     Sample<E> sm;
     fetch_sample<E, GM_GENERIC, true>(rv, geo, ray, s, h, sm);
     const bool live = valid && !(mask && !point_in_bounds(sm.x, sm.y, sm.z));
@@ -242,7 +236,7 @@ __global__ void __launch_bounds__(64 * NW, 2) splat_mlp_fwd_loop(const LpSplatte
     for (int g = 0; g < a.out.n_grids; ++g) {
       const LpGrid& og = a.out.grids[g];
       if (og.D > 1 && og.H > 1 && og.W > 1)
-        splat_walk_vox<CO, 32>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, SplatSrcLds{vt, LT_LD, lane & 15}, wT, 0);
+        splat_walk_vox<CO, 32>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, SplatSrcLds{vt, LT_LD, lane & 15}, wT);
       else
         sloop_walk_lds<CO>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, vt, wT);
     }
@@ -388,7 +382,7 @@ __global__ void __launch_bounds__(256, NB == 1 ? 2 : 1) splat_mlp_bwd_loop(const
       for (int q = 0; q < E / 2; ++q) xt[(32 * (q >> 4) + featq(q & 15, h)) * DX_LD + r] = g[q >> 4][q & 15];
 #pragma unroll 1
       for (int gi = 0; gi < a.input_grid.n_grids; ++gi)
-        scatter_grid<E, GM_GENERIC, false>(a.grad_input_grid_list[gi], a.input_grid.grids[gi], ray.b, x, y, z, live, lane, xt, wT, sp.dbg);
+        scatter_grid<E, GM_GENERIC, false>(a.grad_input_grid_list[gi], a.input_grid.grids[gi], ray.b, x, y, z, live, lane, xt, wT);
     }
   }
 
@@ -443,8 +437,6 @@ static SplatLoopParams sloop_params(const LpSplatterArgs& a, int NB) {
   const int small_bytes = f * 4;
   for (int l = 0; l < p.n; ++l) p.l[l].img += small_bytes;
   p.img_end = small_bytes + img;
-  static const int dbg = getenv("LP_MFMA_DEBUG") ? atoi(getenv("LP_MFMA_DEBUG")) : 0;
-  p.dbg = dbg;
   p.n_seg = 1;
   p.fwd_group = 0;
   return p;
@@ -465,13 +457,12 @@ static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, b
 template <int E, int CO, int NB>
 static int sloop_launch_fwd(const LpSplatterArgs& a, hipStream_t stream) {
   if constexpr (NB == 2) {
-    static const bool no_nw8 = getenv("LP_LOOP_FWD_NW4") != nullptr;  // A/B
     static const bool force8 = getenv("LP_LOOP_FWD_NW8") != nullptr;  // tests: also for batches below one round of workgroups
     const SplatLoopParams p0 = sloop_params(a, NB);
     const size_t lds4 = (size_t)p0.img_end + (size_t)WAVES * SplatLoopTileFwd::PER_WAVE * 4;
     const size_t lds8 = (size_t)p0.img_end + (size_t)8 * SplatLoopTileFwd::PER_WAVE * 4;
     const unsigned nb8 = (unsigned)((a.rays.n_rays + 8 * RAYS_PER_WAVE - 1) / (8 * RAYS_PER_WAVE));
-    if (2 * lds4 > 160 * 1024 && lds8 <= 160 * 1024 && (nb8 >= 256u || force8) && !no_nw8)
+    if (2 * lds4 > 160 * 1024 && lds8 <= 160 * 1024 && (nb8 >= 256u || force8))
       return sloop_launch(splat_mlp_fwd_loop<E, CO, NB, 8>, a, stream, false, 8, SplatLoopTileFwd::PER_WAVE);
   }
   return sloop_launch(splat_mlp_fwd_loop<E, CO, NB, WAVES>, a, stream, false, WAVES, SplatLoopTileFwd::PER_WAVE);
@@ -489,25 +480,19 @@ static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, b
   rv.rays = a.rays;
   const unsigned nb = (unsigned)((a.rays.n_rays + nw * RAYS_PER_WAVE - 1) / (nw * RAYS_PER_WAVE));
   // small batches (see splat_segments in lp_splatter.hip): segments of >= 16 samples, within one round of workgroups
-  static const int forced = getenv("LP_SPLAT_SEGMENTS") ? atoi(getenv("LP_SPLAT_SEGMENTS")) : 0;
   const int s_tot = a.march.num_samples + a.march.num_samples_inf;
-  int n_seg = forced > 0 ? forced : (int)(256u / (nb ? nb : 1u));
+  int n_seg = (int)(256u / (nb ? nb : 1u));
   if (n_seg > s_tot / 16) n_seg = s_tot / 16;
   if (n_seg < 1) n_seg = 1;
   p.fwd_group = 0;
   if (!backward) {
     // forward: as the plain Splatter's (lp_splatter.hip: interleaved segments of >= 16 samples here -- every workgroup stages the MLP's
-    // limb images --, segment-major while the output grid is cache-sized; LP_SPLAT_FWD_SEGMENTS / LP_SPLAT_FWD_GROUP: A/B, 0 group = rounds 2-5)
-    static const int forced_f = getenv("LP_SPLAT_FWD_SEGMENTS") ? atoi(getenv("LP_SPLAT_FWD_SEGMENTS")) : 0;
-    static const int forced_g = getenv("LP_SPLAT_FWD_GROUP") ? atoi(getenv("LP_SPLAT_FWD_GROUP")) : -1;
-    if (forced_g != 0) {
-      n_seg = forced_f > 0 ? forced_f : s_tot / 16;
-      if (forced_f <= 0 && n_seg > 16) n_seg = 16;
-      if (n_seg > s_tot) n_seg = s_tot;
-      if (n_seg < 1) n_seg = 1;
-      const double grid_bytes = (double)a.out.n_rows * (double)a.out.channels * 4.0;
-      p.fwd_group = forced_g > 0 ? forced_g : ((grid_bytes <= 1.0e9 && nb <= 4096u) ? (int)nb : 1);
-    }
+    // limb images --, segment-major while the output grid is cache-sized)
+    n_seg = s_tot / 16;
+    if (n_seg > 16) n_seg = 16;
+    if (n_seg < 1) n_seg = 1;
+    const double grid_bytes = (double)a.out.n_rows * (double)a.out.channels * 4.0;
+    p.fwd_group = (grid_bytes <= 1.0e9 && nb <= 4096u) ? (int)nb : 1;
   }
   p.n_seg = n_seg;
   if (backward && n_seg > 1 && a.grad_encoding) {

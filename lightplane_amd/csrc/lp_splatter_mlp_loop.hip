@@ -58,7 +58,7 @@ int splatter_mlp_forward_loop(const LpSplatterArgs& a, hipStream_t stream) {
 int splatter_mlp_backward_loop(const LpSplatterArgs& a, hipStream_t stream) {
   if (a.rays.n_rays == 0) return LP_OK;
   int rc;
-  static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;  // A/B: the deep instantiation for every shape
+  static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;  // tests: the deep instantiation for every shape
   if (a.mlp.n_layers <= 2 && sloop_nb(a) == 1 && !no_shallow) {
     if ((rc = splatter_mlp_backward_loop_shallow(a, stream))) return rc;
     return check_launch("splat_mlp_bwd_loop (two layers)");

@@ -43,10 +43,9 @@ def splat_kernel_ms(wl, reps):
 
 def splatter_main(reps):
     """cfg 3's Splatter (32 ch -> 128^3 x 32 voxel grid, 256 samples) on small images.  The march segmentation is decided
-    inside the library (lp_splatter.hip, splat_segments); LP_SPLAT_SEGMENTS=1 in the environment switches it off."""
+    inside the library (lp_splatter.hip, splat_segments)."""
     dev = torch.device("cuda:0")
     lp.config.check_inputs = False
-    print(f"LP_SPLAT_SEGMENTS={os.environ.get('LP_SPLAT_SEGMENTS', '(auto)')}")
     print(f"{'rays':>8s} | {'fwd walk ms':>12s} {'bwd walk ms':>12s}")
     for H, W in ((64, 64), (128, 128), (128, 256), (256, 256)):
         wl = bench.SplatterWorkload(0, dev, None, image=(H, W))

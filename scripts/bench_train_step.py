@@ -53,7 +53,7 @@ def main():
     dev = torch.device("cuda:0")
     lp.config.check_inputs = False
     C, G, S = 32, 128, 128
-    print(f"march_order={args.march} LP_MFMA_DEBUG={os.environ.get('LP_MFMA_DEBUG', '')}")
+    print(f"march_order={args.march}")
     print(f"{'hidden':>6s} {'rays':>6s} {'family':>6s} | {'step wall ms':>12s} {'lp kernels ms':>13s} | {'Mrays/s (wall)':>14s}  kernels")
     for hidden in [int(v) for v in args.hidden.split(",")]:
         gen = torch.Generator().manual_seed(0)

@@ -763,20 +763,6 @@ def test_fit_synthetic_scene_converges():
         lp.config.stop_transmittance = old
 
 
-def test_splatter_walk_16_rays_per_wave():
-    """The Splatter's forward walk with 16 instead of 32 rays per wave (LP_SPLAT_RPW, read once per process; 32 is the default
-    since round 4 -- longer walks meet more masked / padding rays next to live ones, the case that once dropped a carried
-    column -- so the default run covers it now and this test the other width).  Runs the golden Splatter cases in a child process."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, LP_SPLAT_RPW="16")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests"), "-m", "gpu", "-q", "-x",
-                        "-k", "test_splatter_matches", "-p", "no:cacheprovider"],
-                       cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
-
-
 def test_hip_graph_capture_of_forward_backward():
     """A Renderer forward+backward captures into a HIP graph (torch.cuda.CUDAGraph: no host syncs, launches on the
     capturing stream) and the replay reproduces the eager gradients (atomics: summation order only)."""
