@@ -73,7 +73,10 @@ extern "C" {
                            0.2.7: no struct change; LP_SEG_LEN 16 -> 8: LpRendererArgs.seg_prefix holds a record per 8 samples
                                   (lp_renderer_backward_segments() returns ceil(S / 8) for a small batch): batches of up to ~2 000 rays
                                   are dealt to the CUs in 8-sample segments, larger ones in 16-sample segments as before; the MFMA
-                                  families take grid-lists of any byte size below 2^31 rows (were: below 4 GB) */
+                                  families take grid-lists of any byte size below 2^31 rows (were: below 4 GB); later, without a
+                                  version change (additive: no struct or behaviour change, every existing entry point as before):
+                                  the MLP-Splatter test hooks lp_mlp_splatter_backward_relu_dump() and
+                                  lp_mlp_splatter_relu_dump_words(), the launch-shape query lp_mlp_splatter_launch_shape() */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -367,6 +370,22 @@ int lp_renderer_backward_relu_dump(const LpRendererArgs* args, uint32_t* dump, i
  *     visited flag (1 / 2 / 0 as above);
  *   family 0 (shape-generic, also LP_KERNEL_GENERIC): the same layout with NB = ceil(widest site / 32). */
 int lp_renderer_relu_dump_words(const LpRendererArgs* args);
+
+/* Debug / parity hook: lp_splatter_backward() of an MLP-Splatter through the DUMP twin of the kernel it would launch (layer-looped
+ * family 3 -- every instantiation, two-layer kernel included -- or the shape-generic kernel), which also writes the ReLU decisions of
+ * the backward's MLP recompute: per (ray, sample) lp_mlp_splatter_relu_dump_words(args) words -- for each hidden layer l (the ReLU
+ * sites in the oracle's call order) ceil(dims[l + 1] / 32) words, bit f of word b set when unit 32 b + f is active, then one flag
+ * word: 1 (live sample), 2 (visited, masked out of bounds), 0 (never visited).  dump_words must be n_rays * S_tot * that count; the
+ * caller zero-fills.  LP_EUNSUPPORTED in a library built without -DLP_TEST_HOOKS. */
+int lp_mlp_splatter_backward_relu_dump(const LpSplatterArgs* args, uint32_t* dump, int64_t dump_words, void* stream);
+/* Words per (ray, sample) of that dump for these arguments (shapes only, no launch). */
+int lp_mlp_splatter_relu_dump_words(const LpSplatterArgs* args);
+/* How an MLP-Splatter of these arguments is launched (shapes and batch size only, no launch): shape[0] kernel family (3 / 0, as
+ * lp_splatter_kernel_family, 0 also for LP_KERNEL_GENERIC), shape[1] forward waves per workgroup (4 or 8; 1 for the generic
+ * kernels), shape[2] backward segments per ray (1 = one sweep), shape[3] layers the backward instantiation is unrolled for (2: the
+ * two-layer kernel at two waves per SIMD, 4: the deep one, 0: generic), shape[4] 32-unit blocks per layer (0: generic), shape[5]
+ * forward segments per ray.  shape must hold 6 int32. */
+int lp_mlp_splatter_launch_shape(const LpSplatterArgs* args, int32_t* shape);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,7 @@ EXPORTS = (
     "lp_renderer_corner_rows", "lp_renderer_kernel_family", "lp_splatter_kernel_family",
     "lp_renderer_backward_segments", "lp_renderer_backward_relu_dump", "lp_renderer_relu_dump_words", "lp_build_info",
     "lp_ray_embedding_forward", "lp_ray_embedding_backward",
+    "lp_mlp_splatter_backward_relu_dump", "lp_mlp_splatter_relu_dump_words", "lp_mlp_splatter_launch_shape",
 )
 
 
@@ -150,6 +151,12 @@ def lib() -> C.CDLL:
     L.lp_renderer_backward_relu_dump.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p, C.c_int64, C.c_void_p]
     L.lp_renderer_relu_dump_words.restype = C.c_int
     L.lp_renderer_relu_dump_words.argtypes = [C.POINTER(LpRendererArgs)]
+    L.lp_mlp_splatter_backward_relu_dump.restype = C.c_int
+    L.lp_mlp_splatter_backward_relu_dump.argtypes = [C.POINTER(LpSplatterArgs), C.c_void_p, C.c_int64, C.c_void_p]
+    L.lp_mlp_splatter_relu_dump_words.restype = C.c_int
+    L.lp_mlp_splatter_relu_dump_words.argtypes = [C.POINTER(LpSplatterArgs)]
+    L.lp_mlp_splatter_launch_shape.restype = C.c_int
+    L.lp_mlp_splatter_launch_shape.argtypes = [C.POINTER(LpSplatterArgs), C.c_void_p]
     L.lp_build_info.restype = C.c_char_p
     L.lp_renderer_kernel_family.restype = C.c_int
     L.lp_renderer_kernel_family.argtypes = [C.POINTER(LpRendererArgs)]

@@ -18,17 +18,18 @@ PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "liblightplane_hip.so")
 # (longest compiles first: the translation units are compiled in parallel)
 SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_dump.hip", "lp_renderer_mfma_bwd.hip", "lp_renderer_mfma_bwd_dump.hip", "lp_renderer_mfma_bwd_c32.hip", "lp_renderer_mfma_bwd_aux.hip", "lp_renderer_mfma_bwd_tm.hip",
-           "lp_splatter_mlp_loop.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
-           "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_loop_shallow.hip", "lp_ray_embedding.hip", "lp_api.hip"]
+           "lp_splatter_mlp_loop.hip", "lp_splatter_mlp_loop_dump.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
+           "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_dump.hip", "lp_splatter_mlp_loop_shallow.hip",
+           "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_api.hip"]
 HEADERS = ["lp_device.h", "lp_host.h", "lp_mfma_common.h", "lp_generic_mlp.h", "lp_splat_walk.h", "lp_bf3.h", "lp_loop.h", "lp_renderer_loop.h",
-           "lp_renderer_mfma_bwd.h", "lp_splatter_mlp_loop.h", os.path.join("..", "..", "include", "lightplane_hip.h")]
+           "lp_renderer_mfma_bwd.h", "lp_splatter_mlp.h", "lp_splatter_mlp_loop.h", os.path.join("..", "..", "include", "lightplane_hip.h")]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
     "-fno-gpu-rdc", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function",
 ]
 
 
-# -DLP_TEST_HOOKS: the DUMP twins behind lp_renderer_backward_relu_dump() (their own translation units; the production kernels are the
+# -DLP_TEST_HOOKS: the DUMP twins behind lp_renderer_backward_relu_dump() / lp_mlp_splatter_backward_relu_dump() (their own translation units; the production kernels are the
 # same with or without them).  LP_NO_TEST_HOOKS=1 builds a library without them (the hook then returns LP_EUNSUPPORTED).
 if not os.environ.get("LP_NO_TEST_HOOKS"):
     FLAGS.append("-DLP_TEST_HOOKS")
@@ -58,6 +59,7 @@ FILE_FLAGS = {
     "lp_renderer_loop_shallow.hip": _LOOP_FLAGS,
     "lp_renderer_loop_shallow_dump.hip": _LOOP_FLAGS,
     "lp_splatter_mlp_loop_shallow.hip": _LOOP_FLAGS,
+    "lp_splatter_mlp_loop_shallow_dump.hip": _LOOP_FLAGS,
 }
 
 

@@ -445,6 +445,46 @@ int lp_splatter_backward(const LpSplatterArgs* args_, void* stream) {
   return splatter_backward_launch(*args, (hipStream_t)stream);
 }
 
+int lp_mlp_splatter_relu_dump_words(const LpSplatterArgs* args) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  if ((rc = check_mlp("splatter", args->mlp, false))) return rc;
+  if (args->mlp.n_layers < 2) return set_error(LP_EINVAL, "relu dump: a one-layer MLP has no ReLU");
+  if (args->kernel != LP_KERNEL_GENERIC && splatter_mlp_family(*args) == 3) return splatter_mlp_loop_dump_words(*args);
+  return splatter_mlp_dump_words(*args);
+}
+
+int lp_mlp_splatter_backward_relu_dump(const LpSplatterArgs* args, uint32_t* dump, int64_t dump_words, void* stream) {
+  if (!args || !dump) return set_error(LP_ENULL, "args / dump is NULL");
+  const int w = lp_mlp_splatter_relu_dump_words(args);
+  if (w < 0) return w;
+  const int64_t want = args->rays.n_rays * (int64_t)(args->march.num_samples + args->march.num_samples_inf) * w;
+  if (dump_words != want) return set_error(LP_EINVAL, "relu dump: %lld words given, [n_rays][S_tot][%d] = %lld needed", (long long)dump_words, w, (long long)want);
+  g_relu_dump = dump;
+  const int rc = lp_splatter_backward(args, stream);
+  g_relu_dump = nullptr;
+  return rc;
+}
+
+int lp_mlp_splatter_launch_shape(const LpSplatterArgs* args, int32_t* shape) {
+  if (!args || !shape) return set_error(LP_ENULL, "args / shape is NULL");
+  int rc;
+  if ((rc = check_mlp("splatter", args->mlp, false))) return rc;
+  const int fam = args->kernel == LP_KERNEL_GENERIC ? 0 : splatter_mlp_family(*args);
+  if (args->kernel == LP_KERNEL_MFMA && fam == 0) return set_error(LP_EUNSUPPORTED, "MFMA MLP-splatter kernel unavailable for this shape");
+  shape[0] = fam;
+  if (fam == 3) {
+    splatter_mlp_loop_shape(*args, shape);
+  } else {  // one-wave workgroups, one sweep per ray both ways
+    shape[1] = 1;
+    shape[2] = 1;
+    shape[3] = 0;
+    shape[4] = 0;
+    shape[5] = 1;
+  }
+  return LP_OK;
+}
+
 /* developer / test hook (not part of include/lightplane_hip.h): which Renderer backward the process launched last --
  * "tuned family, rays per wavefront", "tuned family, samples per wavefront (transposed march)", "layer-looped family",
  * "shape-generic kernels" (static strings) */

@@ -87,10 +87,14 @@ int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream);
 // MLP-Splatter: lp_splatter_mlp.hip
 int splatter_mlp_forward_launch(const LpSplatterArgs& a, hipStream_t stream);
 int splatter_mlp_backward_launch(const LpSplatterArgs& a, hipStream_t stream);
+int splatter_mlp_backward_dump_launch(const LpSplatterArgs& a, hipStream_t stream);  // DUMP twin: lp_splatter_mlp_dump.hip
+int splatter_mlp_dump_words(const LpSplatterArgs& a);  // words per (ray, sample) of its ReLU dump
 // MLP-Splatter, layer-looped bf16x3 family (2-4 layers, widths 16 / 32 / 64): lp_splatter_mlp_loop.hip
 bool splatter_mlp_loop_supported(const LpSplatterArgs& a);
 int splatter_mlp_forward_loop(const LpSplatterArgs& a, hipStream_t stream);
 int splatter_mlp_backward_loop(const LpSplatterArgs& a, hipStream_t stream);
+int splatter_mlp_loop_dump_words(const LpSplatterArgs& a);
+void splatter_mlp_loop_shape(const LpSplatterArgs& a, int32_t* shape);  // lp_mlp_splatter_launch_shape, family 3
 int splatter_normalize_launch(float* feature, const float* weight, int64_t n_rows, int channels,
                               hipStream_t stream);
 // ray-direction embedding of the module front-end: lp_ray_embedding.hip

@@ -26,6 +26,10 @@ struct SplatLoopParams {
   int n_seg;                   // segments the march is cut into (blockIdx = (ray block, segment))
   int fwd_group;               // forward: INTERLEAVED samples per segment (g, g + n_seg, ...), issued in groups of this many ray
                                // blocks segment after segment (lp_splatter.hip, splat_forward_segments / _group)
+  // test hook (lp_mlp_splatter_backward_relu_dump): ReLU decisions of the backward's recompute, [ray][sample][dump_words] words --
+  // ceil(H / 32) words per hidden layer, then the visited flag (include/lightplane_hip.h).  Only the DUMP twins read it.
+  uint32_t* relu_dump;
+  int dump_words;
 };
 
 // per-wave LDS area (floats): two [32][36] tiles, contiguous (together: the [64][36] dx tile of a 64-channel input grid),
@@ -251,7 +255,10 @@ __global__ void __launch_bounds__(64 * NW, 2) splat_mlp_fwd_loop(const LpSplatte
 // (its images + tiles are <= 63 KB: two workgroups per CU): the four-layer ones were at 244 + 32 ... 256 + 82 registers, i.e. one
 // wave per SIMD for a handful of registers; under the bound <32,16> fits 254 without a spill and <32,32> spills 70 and is STILL 17 %
 // faster ([32,32,32,32]: 10.03 -> 8.30 ms fwd+bwd, profiles/r04_loop_shallow_ab.txt)
-template <int E, int CO, int NB, int ML = SLOOP_MAX>
+// DUMP (test hook, its own instantiations in lp_splatter_mlp_loop_dump.hip / lp_splatter_mlp_loop_shallow_dump.hip, built with the
+// flags of their production twins): the ReLU decisions of the recompute are also written to sp.relu_dump -- same instruction
+// sequence, stores added.
+template <int E, int CO, int NB, int ML = SLOOP_MAX, bool DUMP = false>
 __global__ void __launch_bounds__(256, NB == 1 ? 2 : 1) splat_mlp_bwd_loop(const LpSplatterArgs a, const LpRendererArgs rv, const SplatLoopParams sp) {
   using T = SplatLoopTile;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -312,6 +319,26 @@ __global__ void __launch_bounds__(256, NB == 1 ? 2 : 1) splat_mlp_bwd_loop(const
         if (l == 0) loop_layer_fwd<NB>(lbase, smf, sp.l[0], lane, xin, act[0]);
         else loop_layer_fwd<NB>(lbase, smf, sp.l[l], lane, act[l > 0 ? l - 1 : 0], act[l]);
       }
+    }
+    if constexpr (DUMP) {
+      // one site per hidden layer (the oracle's ReLU call order), sp.l[0].ob = ceil(H / 32) words each.  A post-ReLU activation is
+      // > 0 exactly where the unit is active -- the test every mask of this backward applies.
+      uint32_t* const dsite = sp.relu_dump + (rid * (int64_t)s_tot + s) * sp.dump_words;
+      const int wps = sp.l[0].ob;
+#pragma unroll
+      for (int l = 0; l < ML - 1; ++l) {
+        if (l < sp.n - 1) {
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            unsigned m = 0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) m |= (act[l][b][q] > 0.0f) ? (1u << featq(q, h)) : 0u;
+            m |= __shfl_xor(m, 32);
+            if (valid && h == 0 && b < wps) dsite[l * wps + b] = m;
+          }
+        }
+      }
+      if (valid && h == 0) dsite[sp.dump_words - 1] = live ? 1u : 2u;
     }
     LP_SCHED_FENCE();
     // ---- d v: gather of grad_out / clamp(weight) at the output taps (Splatter interpolation) ----
@@ -448,22 +475,51 @@ static int sloop_nb(const LpSplatterArgs& a) {
   return w <= 32 ? 1 : 2;
 }
 
-template <typename K>
-static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, bool backward, int nw = WAVES,
-                        int per_wave = SplatLoopTile::PER_WAVE);
+// words per (ray, sample) of the ReLU dump (include/lightplane_hip.h, lp_mlp_splatter_relu_dump_words): ceil(H / 32) per hidden
+// layer + the flag word
+static int sloop_dump_words(const LpSplatterArgs& a) { return (a.mlp.n_layers - 1) * ((a.mlp.dims[1] + 31) / 32) + 1; }
 
 // forward: four-wave workgroups, two per CU, where images + tiles fit twice in the 160 KB; otherwise ONE eight-wave workgroup
 // per CU over one copy of the images (two-block MLPs of three / four layers) -- two waves per SIMD either way
-template <int E, int CO, int NB>
-static int sloop_launch_fwd(const LpSplatterArgs& a, hipStream_t stream) {
-  if constexpr (NB == 2) {
+static int sloop_fwd_waves(const LpSplatterArgs& a) {
+  const int NB = sloop_nb(a);
+  if (NB == 2) {
     static const bool force8 = getenv("LP_LOOP_FWD_NW8") != nullptr;  // tests: also for batches below one round of workgroups
     const SplatLoopParams p0 = sloop_params(a, NB);
     const size_t lds4 = (size_t)p0.img_end + (size_t)WAVES * SplatLoopTileFwd::PER_WAVE * 4;
     const size_t lds8 = (size_t)p0.img_end + (size_t)8 * SplatLoopTileFwd::PER_WAVE * 4;
     const unsigned nb8 = (unsigned)((a.rays.n_rays + 8 * RAYS_PER_WAVE - 1) / (8 * RAYS_PER_WAVE));
-    if (2 * lds4 > 160 * 1024 && lds8 <= 160 * 1024 && (nb8 >= 256u || force8))
-      return sloop_launch(splat_mlp_fwd_loop<E, CO, NB, 8>, a, stream, false, 8, SplatLoopTileFwd::PER_WAVE);
+    if (2 * lds4 > 160 * 1024 && lds8 <= 160 * 1024 && (nb8 >= 256u || force8)) return 8;
+  }
+  return WAVES;
+}
+
+// segments the march of a launch with `nw` waves per workgroup is cut into
+static int sloop_segments(const LpSplatterArgs& a, bool backward, int nw) {
+  const unsigned nb = (unsigned)((a.rays.n_rays + nw * RAYS_PER_WAVE - 1) / (nw * RAYS_PER_WAVE));
+  // small batches (see splat_segments in lp_splatter.hip): segments of >= 16 samples, within one round of workgroups
+  const int s_tot = a.march.num_samples + a.march.num_samples_inf;
+  int n_seg = (int)(256u / (nb ? nb : 1u));
+  if (n_seg > s_tot / 16) n_seg = s_tot / 16;
+  if (n_seg < 1) n_seg = 1;
+  if (!backward) {
+    // forward: as the plain Splatter's (lp_splatter.hip: interleaved segments of >= 16 samples here -- every workgroup stages the MLP's
+    // limb images --, segment-major while the output grid is cache-sized)
+    n_seg = s_tot / 16;
+    if (n_seg > 16) n_seg = 16;
+    if (n_seg < 1) n_seg = 1;
+  }
+  return n_seg;
+}
+
+template <typename K>
+static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, bool backward, int nw = WAVES,
+                        int per_wave = SplatLoopTile::PER_WAVE);
+
+template <int E, int CO, int NB>
+static int sloop_launch_fwd(const LpSplatterArgs& a, hipStream_t stream) {
+  if constexpr (NB == 2) {
+    if (sloop_fwd_waves(a) == 8) return sloop_launch(splat_mlp_fwd_loop<E, CO, NB, 8>, a, stream, false, 8, SplatLoopTileFwd::PER_WAVE);
   }
   return sloop_launch(splat_mlp_fwd_loop<E, CO, NB, WAVES>, a, stream, false, WAVES, SplatLoopTileFwd::PER_WAVE);
 }
@@ -479,20 +535,14 @@ static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, b
   rv.march = a.march;
   rv.rays = a.rays;
   const unsigned nb = (unsigned)((a.rays.n_rays + nw * RAYS_PER_WAVE - 1) / (nw * RAYS_PER_WAVE));
-  // small batches (see splat_segments in lp_splatter.hip): segments of >= 16 samples, within one round of workgroups
-  const int s_tot = a.march.num_samples + a.march.num_samples_inf;
-  int n_seg = (int)(256u / (nb ? nb : 1u));
-  if (n_seg > s_tot / 16) n_seg = s_tot / 16;
-  if (n_seg < 1) n_seg = 1;
+  const int n_seg = sloop_segments(a, backward, nw);
   p.fwd_group = 0;
   if (!backward) {
-    // forward: as the plain Splatter's (lp_splatter.hip: interleaved segments of >= 16 samples here -- every workgroup stages the MLP's
-    // limb images --, segment-major while the output grid is cache-sized)
-    n_seg = s_tot / 16;
-    if (n_seg > 16) n_seg = 16;
-    if (n_seg < 1) n_seg = 1;
     const double grid_bytes = (double)a.out.n_rows * (double)a.out.channels * 4.0;
     p.fwd_group = (grid_bytes <= 1.0e9 && nb <= 4096u) ? (int)nb : 1;
+  } else {
+    p.relu_dump = g_relu_dump;  // test hook (NULL in every product call; only the DUMP twins read it)
+    p.dump_words = sloop_dump_words(a);
   }
   p.n_seg = n_seg;
   if (backward && n_seg > 1 && a.grad_encoding) {
@@ -503,7 +553,45 @@ static int sloop_launch(K kernel, const LpSplatterArgs& a, hipStream_t stream, b
   return LP_OK;
 }
 
+// The instantiation tables of the backward, shared by the production translation units and their DUMP twins: one wave per SIMD
+// for the two-block (width-64) MLPs, two for the others; the TWO-layer MLPs [E, H, Cout], E, H in {16, 32}, keep one hidden
+// activation (ML = 2: lp_splatter_mlp_loop_shallow.hip).
+template <bool DUMP>
+static int sloop_bwd_table_deep(const LpSplatterArgs& a, hipStream_t stream) {
+  const int E = a.mlp.dims[0], CO = a.mlp.dims[a.mlp.n_layers], NB = sloop_nb(a);
+#define LP_SL_BWD(EV, COV, NBV) return sloop_launch(splat_mlp_bwd_loop<EV, COV, NBV, SLOOP_MAX, DUMP>, a, stream, true)
+  if (E == 16) {
+    if (CO == 16) { if (NB == 1) LP_SL_BWD(16, 16, 1); LP_SL_BWD(16, 16, 2); }
+    if (NB == 1) LP_SL_BWD(16, 32, 1);
+    LP_SL_BWD(16, 32, 2);
+  }
+  if (E == 32) {
+    if (CO == 16) { if (NB == 1) LP_SL_BWD(32, 16, 1); LP_SL_BWD(32, 16, 2); }
+    if (NB == 1) LP_SL_BWD(32, 32, 1);
+    LP_SL_BWD(32, 32, 2);
+  }
+  if (CO == 16) LP_SL_BWD(64, 16, 2);
+  LP_SL_BWD(64, 32, 2);
+#undef LP_SL_BWD
+}
+
+template <bool DUMP>
+static int sloop_bwd_table_shallow(const LpSplatterArgs& a, hipStream_t stream) {
+  const int E = a.mlp.dims[0], CO = a.mlp.dims[a.mlp.n_layers];
+  if (E == 16) return CO == 16 ? sloop_launch(splat_mlp_bwd_loop<16, 16, 1, 2, DUMP>, a, stream, true) : sloop_launch(splat_mlp_bwd_loop<16, 32, 1, 2, DUMP>, a, stream, true);
+  return CO == 16 ? sloop_launch(splat_mlp_bwd_loop<32, 16, 1, 2, DUMP>, a, stream, true) : sloop_launch(splat_mlp_bwd_loop<32, 32, 1, 2, DUMP>, a, stream, true);
+}
+
+// the two-layer two-waves-per-SIMD backward runs (else the deep table)
+static bool sloop_bwd_shallow(const LpSplatterArgs& a) {
+  static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;  // tests: the deep instantiation for every shape
+  return a.mlp.n_layers <= 2 && sloop_nb(a) == 1 && !no_shallow;
+}
+
 // backward of a TWO-layer MLP [E, H, Cout], E, H in {16, 32}, at two waves per SIMD: lp_splatter_mlp_loop_shallow.hip
 int splatter_mlp_backward_loop_shallow(const LpSplatterArgs& a, hipStream_t stream);
+// DUMP twins (with -DLP_TEST_HOOKS; LP_EUNSUPPORTED without): lp_splatter_mlp_loop_dump.hip, lp_splatter_mlp_loop_shallow_dump.hip
+int splatter_mlp_backward_loop_deep_dump(const LpSplatterArgs& a, hipStream_t stream);
+int splatter_mlp_backward_loop_shallow_dump(const LpSplatterArgs& a, hipStream_t stream);
 
 }  // namespace lp

@@ -23,21 +23,6 @@ bool splatter_mlp_loop_supported(const LpSplatterArgs& a) {
   return (size_t)p.img_end + (size_t)WAVES * SplatLoopTile::PER_WAVE * 4 <= 160 * 1024;
 }
 
-#define LP_DISPATCH_SL(KERNEL, BWD)                                                                        \
-  do {                                                                                                     \
-    const int E = a.mlp.dims[0], CO = a.mlp.dims[a.mlp.n_layers], NB = sloop_nb(a);                        \
-    if (E == 16) {                                                                                         \
-      if (CO == 16) rc = NB == 1 ? sloop_launch(KERNEL<16, 16, 1>, a, stream, BWD) : sloop_launch(KERNEL<16, 16, 2>, a, stream, BWD); \
-      else rc = NB == 1 ? sloop_launch(KERNEL<16, 32, 1>, a, stream, BWD) : sloop_launch(KERNEL<16, 32, 2>, a, stream, BWD);          \
-    } else if (E == 32) {                                                                                  \
-      if (CO == 16) rc = NB == 1 ? sloop_launch(KERNEL<32, 16, 1>, a, stream, BWD) : sloop_launch(KERNEL<32, 16, 2>, a, stream, BWD); \
-      else rc = NB == 1 ? sloop_launch(KERNEL<32, 32, 1>, a, stream, BWD) : sloop_launch(KERNEL<32, 32, 2>, a, stream, BWD);          \
-    } else {                                                                                               \
-      if (CO == 16) rc = sloop_launch(KERNEL<64, 16, 2>, a, stream, BWD);                                  \
-      else rc = sloop_launch(KERNEL<64, 32, 2>, a, stream, BWD);                                           \
-    }                                                                                                      \
-  } while (0)
-
 int splatter_mlp_forward_loop(const LpSplatterArgs& a, hipStream_t stream) {
   if (a.rays.n_rays == 0) return LP_OK;
   int rc;
@@ -58,15 +43,25 @@ int splatter_mlp_forward_loop(const LpSplatterArgs& a, hipStream_t stream) {
 int splatter_mlp_backward_loop(const LpSplatterArgs& a, hipStream_t stream) {
   if (a.rays.n_rays == 0) return LP_OK;
   int rc;
-  static const bool no_shallow = getenv("LP_LOOP_NO_SHALLOW") != nullptr;  // tests: the deep instantiation for every shape
-  if (a.mlp.n_layers <= 2 && sloop_nb(a) == 1 && !no_shallow) {
-    if ((rc = splatter_mlp_backward_loop_shallow(a, stream))) return rc;
+  if (sloop_bwd_shallow(a)) {
+    if ((rc = g_relu_dump ? splatter_mlp_backward_loop_shallow_dump(a, stream) : splatter_mlp_backward_loop_shallow(a, stream))) return rc;
     return check_launch("splat_mlp_bwd_loop (two layers)");
   }
-  LP_DISPATCH_SL(splat_mlp_bwd_loop, true);
-  if (rc) return rc;
+  if ((rc = g_relu_dump ? splatter_mlp_backward_loop_deep_dump(a, stream) : sloop_bwd_table_deep<false>(a, stream))) return rc;
   return check_launch("splat_mlp_bwd_loop");
 }
+
+// launch shape (include/lightplane_hip.h, lp_mlp_splatter_launch_shape)
+void splatter_mlp_loop_shape(const LpSplatterArgs& a, int32_t* shape) {
+  const int fw = sloop_fwd_waves(a);
+  shape[1] = fw;
+  shape[2] = sloop_segments(a, true, WAVES);
+  shape[3] = sloop_bwd_shallow(a) ? 2 : SLOOP_MAX;
+  shape[4] = sloop_nb(a);
+  shape[5] = sloop_segments(a, false, fw);
+}
+
+int splatter_mlp_loop_dump_words(const LpSplatterArgs& a) { return sloop_dump_words(a); }
 
 // what the MLP-Splatter's looped backward computes in (lp_build_info): the dX chains keep three limbs; dW per translation unit
 const char* build_info_splatter_mlp() {

@@ -6,10 +6,6 @@
 
 namespace lp {
 
-int splatter_mlp_backward_loop_shallow(const LpSplatterArgs& a, hipStream_t stream) {
-  const int E = a.mlp.dims[0], CO = a.mlp.dims[a.mlp.n_layers];
-  if (E == 16) return CO == 16 ? sloop_launch(splat_mlp_bwd_loop<16, 16, 1, 2>, a, stream, true) : sloop_launch(splat_mlp_bwd_loop<16, 32, 1, 2>, a, stream, true);
-  return CO == 16 ? sloop_launch(splat_mlp_bwd_loop<32, 16, 1, 2>, a, stream, true) : sloop_launch(splat_mlp_bwd_loop<32, 32, 1, 2>, a, stream, true);
-}
+int splatter_mlp_backward_loop_shallow(const LpSplatterArgs& a, hipStream_t stream) { return sloop_bwd_table_shallow<false>(a, stream); }
 
 }  // namespace lp

@@ -168,7 +168,16 @@ class LightplaneMLPSplatterFunction(torch.autograd.Function):
             else:
                 a.grad_input_grid = _lib.ptr(grad_in[0])
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().lp_splatter_backward(ctypes.byref(a), stream), "lp_splatter_backward")
+            if _RELU_DUMP is not None:  # test hook (mlp_splatter_relu_dump_recorder): the DUMP twin of the same kernel
+                L = _lib.lib()
+                words = L.lp_mlp_splatter_relu_dump_words(ctypes.byref(a))
+                if words < 0:
+                    _lib.check(words, "lp_mlp_splatter_relu_dump_words")
+                d = _RELU_DUMP.reset(directions.shape[0], cfg.num_samples + cfg.num_samples_inf, words, dev)
+                _lib.check(L.lp_mlp_splatter_backward_relu_dump(ctypes.byref(a), d.data_ptr(), d.numel(), stream),
+                           "lp_mlp_splatter_backward_relu_dump")
+            else:
+                _lib.check(_lib.lib().lp_splatter_backward(ctypes.byref(a), stream), "lp_splatter_backward")
         if cfg.process_group is not None:
             # ray-sharded MLP-Splatter: the MLP / input-grid gradients are partial sums over this rank's rays
             # (SURVEY.md 8(e)); grad_feature belongs to the local rays and stays local
@@ -254,6 +263,70 @@ def mlp_splatter_kernel_family(output_grid_size, mlp_params: SplatterParams, inp
     a.input_grid = _lib.make_grid_list(None, in_descs, in_channels, in_n_rows)
     a.mlp = _lib.make_mlp(int_list_of(mlp_params.n_hidden), 0)
     return int(_lib.lib().lp_splatter_kernel_family(ctypes.byref(a)))
+
+
+def _mlp_shape_args(output_grid_size, mlp_params: SplatterParams, input_grid_sizes, n_rays: int = 0, num_samples: int = 1,
+                    num_samples_inf: int = 0, kernel: int = _lib.LP_KERNEL_AUTO) -> _lib.LpSplatterArgs:
+    descs, channels, n_rows = make_grid_descs(sizes_to_list(output_grid_size))
+    in_descs, in_channels, in_n_rows = make_grid_descs(sizes_to_list(input_grid_sizes))
+    a = _lib.LpSplatterArgs()
+    a.rays.n_rays = int(n_rays)
+    a.march = _lib.make_march(int(num_samples), int(num_samples_inf), False, False, 1e-5)
+    a.out = _lib.make_grid_list(None, descs, channels, n_rows)
+    a.input_grid = _lib.make_grid_list(None, in_descs, in_channels, in_n_rows)
+    a.mlp = _lib.make_mlp(int_list_of(mlp_params.n_hidden), 0)
+    a.kernel = int(kernel)
+    return a
+
+
+def mlp_splatter_relu_dump_words(output_grid_size, mlp_params: SplatterParams, input_grid_sizes, num_samples_inf: int = 0,
+                                 kernel: int = _lib.LP_KERNEL_AUTO) -> int:
+    """Words per (ray, sample) of the MLP-Splatter's ReLU dump for these shapes (``lp_mlp_splatter_relu_dump_words``; test hook, needs
+    no GPU): ceil(width / 32) per hidden layer + the flag word."""
+    a = _mlp_shape_args(output_grid_size, mlp_params, input_grid_sizes, num_samples_inf=num_samples_inf, kernel=kernel)
+    w = int(_lib.lib().lp_mlp_splatter_relu_dump_words(ctypes.byref(a)))
+    if w < 0:
+        _lib.check(w, "lp_mlp_splatter_relu_dump_words")
+    return w
+
+
+def mlp_splatter_launch_shape(n_rays: int, output_grid_size, mlp_params: SplatterParams, input_grid_sizes, num_samples: int,
+                              num_samples_inf: int = 0, kernel: int = _lib.LP_KERNEL_AUTO, **_unused) -> dict:
+    """How an MLP-Splatter call of these shapes is launched (``lp_mlp_splatter_launch_shape``; needs no GPU): ``family`` (3 layer-looped,
+    0 shape-generic), ``fwd_waves`` per workgroup (4 or 8; 1 generic), ``bwd_segments`` per ray (1 = one sweep), ``bwd_layers`` the
+    backward instantiation is unrolled for (2 = the two-layer kernel at two waves per SIMD, 4 = the deep one, 0 generic), ``blocks`` of
+    32 units per layer (0 generic), ``fwd_segments``."""
+    a = _mlp_shape_args(output_grid_size, mlp_params, input_grid_sizes, n_rays, num_samples, num_samples_inf, kernel)
+    shape = (ctypes.c_int32 * 6)()
+    _lib.check(_lib.lib().lp_mlp_splatter_launch_shape(ctypes.byref(a), shape), "lp_mlp_splatter_launch_shape")
+    return dict(zip(("family", "fwd_waves", "bwd_segments", "bwd_layers", "blocks", "fwd_segments"), (int(v) for v in shape)))
+
+
+_RELU_DUMP = None
+
+
+class mlp_splatter_relu_dump_recorder:
+    """Test hook (``lp_mlp_splatter_backward_relu_dump``, include/lightplane_hip.h): inside the context every MLP-Splatter backward
+    runs the DUMP twin of its kernel and leaves the ReLU decisions it took in ``.dump`` -- int32 ``[n_rays, S_tot, W]``,
+    ``W = lp_mlp_splatter_relu_dump_words``: per hidden layer of the MLP (the oracle's ReLU call order) ceil(width / 32) words (bit f
+    of word b = unit 32 b + f active), then one flag word: 1 = live sample, 2 = visited but masked out of bounds, 0 = never visited.
+    Raises for a library built without -DLP_TEST_HOOKS."""
+
+    def __init__(self):
+        self.dump = None
+
+    def reset(self, n_rays, s_tot, words, dev):
+        self.dump = torch.zeros(n_rays, s_tot, words, dtype=torch.int32, device=dev)
+        return self.dump
+
+    def __enter__(self):
+        global _RELU_DUMP
+        self._prev, _RELU_DUMP = _RELU_DUMP, self
+        return self
+
+    def __exit__(self, *exc):
+        global _RELU_DUMP
+        _RELU_DUMP = self._prev
 
 
 def lightplane_mlp_splatter(

@@ -558,16 +558,28 @@ def _splat_one_grid(out_flat, shape, points, grid_idx, feature, ray_mask):
     return out_flat
 
 
-def _splatter_impl(rays, output_grid_size, num_samples, num_samples_inf, mask_out_of_bounds_samples,
-                   contract_coords, disparity_at_inf, return_list, mlp_params=None, input_grid=None,
-                   input_grid_sizes=None):
-    sizes = [[int(v) for v in gs] for gs in (output_grid_size.tolist() if torch.is_tensor(output_grid_size) else output_grid_size)]
-    dtype, device = rays.directions.dtype, rays.directions.device
-    depths = ray_depths(rays.near, rays.far, num_samples, num_samples_inf, disparity_at_inf)
-    points = depths[..., None] * rays.directions[:, None] + rays.origins[:, None]
+def _splatter_points(rays, num_samples, num_samples_inf, contract_coords, disparity_at_inf):
+    """Sample points ``[R, S, 3]`` of the Splatter's march, in the geometry dtype (``geometry_dtype``) where one is set."""
+    near, far, directions, origins = rays.near, rays.far, rays.directions, rays.origins
+    gd = _GEOMETRY_DTYPE
+    if gd is not None and directions.dtype != gd:  # test diagnostics (geometry_dtype): the march's geometry in its own dtype
+        near, far, directions, origins = near.to(gd), far.to(gd), directions.to(gd), origins.to(gd)
+    depths = ray_depths(near, far, num_samples, num_samples_inf, disparity_at_inf)
+    points = depths[..., None] * directions[:, None] + origins[:, None]
     if contract_coords:
         points = contract_pi(points)
-    tot = depths.shape[1]
+    return points
+
+
+def _splatter_impl(rays, output_grid_size, num_samples, num_samples_inf, mask_out_of_bounds_samples,
+                   contract_coords, disparity_at_inf, return_list, mlp_params=None, input_grid=None,
+                   input_grid_sizes=None, weight_grids=None):
+    sizes = [[int(v) for v in gs] for gs in (output_grid_size.tolist() if torch.is_tensor(output_grid_size) else output_grid_size)]
+    dtype, device = rays.directions.dtype, rays.directions.device
+    # (the geometry -- depths, points, contraction, cells and interpolation weights of both the input-grid sampling and the output
+    # splat -- stays in the geometry dtype; features, MLP and grids in the rays' dtype)
+    points = _splatter_points(rays, num_samples, num_samples_inf, contract_coords, disparity_at_inf)
+    tot = points.shape[1]
     feat = rays.encoding[:, None, :].expand(-1, tot, -1)
     if mlp_params is not None:
         in_grids = _as_grid_list(input_grid, input_grid_sizes)
@@ -580,12 +592,15 @@ def _splatter_impl(rays, output_grid_size, num_samples, num_samples_inf, mask_ou
         ray_mask = torch.ones(points.shape[:-1], dtype=dtype, device=device)
     ones = torch.ones(points.shape[:-1] + (1,), dtype=dtype, device=device)
     out = []
-    for gs in sizes:
+    for i, gs in enumerate(sizes):
         B, D, H, W, C = gs
         fgrid = torch.zeros(B * D * H * W, C, dtype=dtype, device=device)
-        wgrid = torch.zeros(B * D * H * W, 1, dtype=dtype, device=device)
         fgrid = _splat_one_grid(fgrid, gs, points, rays.grid_idx, feat, ray_mask)
-        wgrid = _splat_one_grid(wgrid, gs, points, rays.grid_idx, ones, ray_mask)
+        if weight_grids is None:
+            wgrid = torch.zeros(B * D * H * W, 1, dtype=dtype, device=device)
+            wgrid = _splat_one_grid(wgrid, gs, points, rays.grid_idx, ones, ray_mask)
+        else:
+            wgrid = weight_grids[i]
         out.append((fgrid / wgrid.clamp(min=1e-5)).reshape(B, D, H, W, C))
     if return_list:
         return out
@@ -598,6 +613,65 @@ def lightplane_splatter_naive(rays, output_grid_size, num_samples, num_samples_i
     """Oracle Splatter (reference naive_splatter.py:41-103)."""
     return _splatter_impl(rays, output_grid_size, num_samples, num_samples_inf,
                           mask_out_of_bounds_samples, contract_coords, disparity_at_inf, return_list)
+
+
+def _ray_chunk(rays, lo, hi):
+    import copy
+    r = copy.copy(rays)
+    for f in ("directions", "origins", "near", "far", "grid_idx", "encoding"):
+        setattr(r, f, getattr(rays, f)[lo:hi])
+    return r
+
+
+def splatter_weight_grids(rays, output_grid_size, num_samples, num_samples_inf=0, mask_out_of_bounds_samples=False,
+                          contract_coords=False, disparity_at_inf=1e-5, chunk=8192, **_ignored):
+    """The Splatter's unit-weight grids (``[B*D*H*W, 1]`` per output grid, un-clamped) from the geometry alone, in ray chunks."""
+    sizes = [[int(v) for v in gs] for gs in (output_grid_size.tolist() if torch.is_tensor(output_grid_size) else output_grid_size)]
+    dtype, device = rays.directions.dtype, rays.directions.device
+    wgrids = [torch.zeros(gs[0] * gs[1] * gs[2] * gs[3], 1, dtype=dtype, device=device) for gs in sizes]
+    with torch.no_grad():
+        for lo in range(0, rays.directions.shape[0], chunk):
+            r = _ray_chunk(rays, lo, lo + chunk)
+            points = _splatter_points(r, num_samples, num_samples_inf, contract_coords, disparity_at_inf)
+            ray_mask = in_bounds(points).to(dtype) if mask_out_of_bounds_samples else torch.ones(points.shape[:-1], dtype=dtype, device=device)
+            ones = torch.ones(points.shape[:-1] + (1,), dtype=dtype, device=device)
+            for i, gs in enumerate(sizes):
+                wgrids[i] = _splat_one_grid(wgrids[i], gs, points, r.grid_idx, ones, ray_mask)
+    return wgrids
+
+
+def lightplane_mlp_splatter_chunked(rays, output_grid_size, mlp_params, input_grid, upstream, num_samples, num_samples_inf=0,
+                                    mask_out_of_bounds_samples=False, contract_coords=False, disparity_at_inf=1e-5,
+                                    input_grid_sizes=None, chunk=4096, chunk_context=None, **_ignored):
+    """``lightplane_mlp_splatter_naive`` forward AND backward of ``sum_k <out_k, upstream[k]>`` in ray chunks (batches whose whole
+    autograd graph does not fit in memory).  The normalisation couples all rays only through the weight grids, which depend on the
+    geometry alone and carry no gradient: they are computed once (``splatter_weight_grids``), then every chunk contributes
+    ``fgrid_chunk / clamp(wgrid, 1e-5)`` to the outputs and its own backward to the gradients.  ``chunk_context(lo, hi)``: an optional
+    context manager entered around each chunk's forward (e.g. ``relu_mask_forcer`` with the chunk's masks).
+    Returns (outputs [B, D, H, W, C] per grid, grad_encoding, grad_mlp_params, grad_input_grids), in the dtype of the inputs."""
+    import contextlib
+    import copy
+    sizes = [[int(v) for v in gs] for gs in (output_grid_size.tolist() if torch.is_tensor(output_grid_size) else output_grid_size)]
+    march = dict(num_samples=num_samples, num_samples_inf=num_samples_inf, mask_out_of_bounds_samples=mask_out_of_bounds_samples,
+                 contract_coords=contract_coords, disparity_at_inf=disparity_at_inf)
+    wgrids = splatter_weight_grids(rays, sizes, chunk=max(chunk, 8192), **march)
+    mlp = copy.copy(mlp_params)
+    mlp.mlp_params = mlp_params.mlp_params.detach().clone().requires_grad_(True)
+    in_grids = [g.detach().clone().requires_grad_(True) for g in _as_grid_list(input_grid, input_grid_sizes)]
+    outs = [torch.zeros(gs[0] * gs[1] * gs[2] * gs[3], gs[4], dtype=rays.directions.dtype) for gs in sizes]
+    g_enc = []
+    for lo in range(0, rays.directions.shape[0], chunk):
+        r = _ray_chunk(rays, lo, lo + chunk)
+        r.encoding = r.encoding.detach().clone().requires_grad_(True)
+        with (chunk_context(lo, lo + chunk) if chunk_context is not None else contextlib.nullcontext()):
+            o = _splatter_impl(r, sizes, num_samples, num_samples_inf, mask_out_of_bounds_samples, contract_coords, disparity_at_inf,
+                               True, mlp_params=mlp, input_grid=in_grids, weight_grids=wgrids)
+        sum((ok * u.to(ok.dtype)).sum() for ok, u in zip(o, upstream)).backward()
+        for k, ok in enumerate(o):
+            outs[k] += ok.detach().reshape(outs[k].shape)
+        g_enc.append(r.encoding.grad)
+    outs = [o.reshape(gs[:4] + [gs[4]]) for o, gs in zip(outs, sizes)]
+    return outs, torch.cat(g_enc), mlp.mlp_params.grad, [g.grad for g in in_grids]
 
 
 def lightplane_mlp_splatter_naive(rays, output_grid_size, mlp_params, input_grid, num_samples,

@@ -604,3 +604,58 @@ def test_row_length_hint_gives_the_same_rays_their_same_results(H, W, C, tri, S)
     o1, g1 = splat(W)
     _assert_close("splat out", o1, o0.detach().cpu().numpy(), tol=2e-5)
     _assert_close("splat grad_encoding", g1, g0.cpu().numpy(), tol=2e-5)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MLP-Splatter at full-chip batches: the forced-oracle proof on the launches only batches of this size select
+# ---------------------------------------------------------------------------------------------------------------------
+def _mlp_splatter_scale_inputs(H, W, n_layers, hidden, E, CO, out_base, triplane, in_base, S, S_inf=0, mask=False, contract=False, seed=0):
+    """A pinhole image of H x W rays (one batch entry) through an MLP [E, hidden x (n_layers - 1), CO] splatted into an output grid
+    of ``out_base`` (voxel or triplane), reading a voxel input grid of ``in_base``; in the layout of tests.synth.SplatterCase.build()."""
+    from tests.synth import random_splatter_mlp
+    gen = torch.Generator().manual_seed(seed)
+    rays = pinhole_rays(H, W, cam_dist=2.4, enc_dim=E, gen=gen, azimuth_deg=30.0, elevation_deg=20.0)
+    rays.encoding = torch.rand(rays.n_rays, E, generator=gen)
+    out_sizes = grid_sizes_for(list(out_base[:4]) + [CO], triplane)
+    in_sizes = grid_sizes_for(list(in_base[:4]) + [E], False)
+    in_grids = random_grids(gen, in_sizes)
+    mlp = random_splatter_mlp(gen, n_layers, E, hidden, CO, std=0.2)
+    cfg = dict(num_samples=S, num_samples_inf=S_inf, mask_out_of_bounds_samples=mask, contract_coords=contract)
+    up = [torch.randn(*s, generator=gen) for s in out_sizes]
+    return dict(rays=rays, out_sizes=out_sizes, mlp=mlp, in_grids=in_grids, in_sizes=in_sizes, cfg=cfg, upstream=up)
+
+
+# name: (image H, W, layers, hidden, E, CO, output grid, triplane, input grid, samples, beyond-far samples, mask, contract, kernel,
+#        the launch it has to reach: (family, forward waves per workgroup, backward segments, backward instantiation, blocks))
+MLP_SPLAT_SCALE_CASES = {
+    # the reference sweep's shape at 65 536 rays: eight-wave forward, one-sweep two-block backward (two-limb bf16 dW)
+    "voxel_3x64_e64_co32_65k": (256, 256, 3, 64, 64, 32, (1, 40, 40, 40), False, (1, 24, 24, 24), 16, 11, False, True,
+                                _lib.LP_KERNEL_AUTO, (3, 8, 1, 4, 2)),
+    "triplane_4x64_e32_co16_65k": (256, 256, 4, 64, 32, 16, (1, 64, 64, 64), True, (1, 24, 24, 24), 16, 11, True, False,
+                                   _lib.LP_KERNEL_AUTO, (3, 8, 1, 4, 2)),
+    # LightplaneMLPSplatter's default depth: the two-layer backward at two waves per SIMD
+    "voxel_2x32_e32_co32_s64_65k": (256, 256, 2, 32, 32, 32, (1, 40, 40, 40), False, (1, 24, 24, 24), 64, 0, False, False,
+                                    _lib.LP_KERNEL_AUTO, (3, 4, 1, 2, 1)),
+    # a small batch of long rays: the segmented backward
+    "voxel_3x64_e64_co32_s96_1k": (32, 32, 3, 64, 64, 32, (1, 40, 40, 40), False, (1, 24, 24, 24), 96, 0, True, False,
+                                   _lib.LP_KERNEL_AUTO, (3, 4, 6, 4, 2)),
+    # the shape-generic kernels at 16 384 rays
+    "generic_voxel_3x64_e64_co32_16k": (128, 128, 3, 64, 64, 32, (1, 40, 40, 40), False, (1, 24, 24, 24), 16, 11, False, True,
+                                        _lib.LP_KERNEL_GENERIC, (0, 1, 1, 0, 0)),
+}
+
+
+@pytest.mark.filterwarnings("ignore:The splatter has been configured")
+@pytest.mark.parametrize("name", list(MLP_SPLAT_SCALE_CASES), ids=list(MLP_SPLAT_SCALE_CASES))
+def test_mlp_splatter_forced_proof_at_scale(name):
+    """The MLP-Splatter at the batch sizes that select its full-chip launches (asserted through lp_mlp_splatter_launch_shape): the
+    production backward's ReLU decisions forced onto the chunked fp64 oracle, every forced unit a near tie, every output and every
+    gradient entry -- grad_mlp_params summed over every sample of every ray included -- within 1e-4 outright."""
+    from lightplane_amd.splatter import mlp_splatter_launch_shape
+    from tests.test_gpu_parity import forced_oracle_check_mlp_splatter
+    H, W, L, hid, E, CO, ob, tri, ib, S, S_inf, mask, contract, kernel, want = MLP_SPLAT_SCALE_CASES[name]
+    d = _mlp_splatter_scale_inputs(H, W, L, hid, E, CO, ob, tri, ib, S, S_inf, mask, contract)
+    shape = mlp_splatter_launch_shape(d["rays"].n_rays, d["out_sizes"], d["mlp"], d["in_sizes"], S, S_inf, kernel=kernel)
+    got = (shape["family"], shape["fwd_waves"], shape["bwd_segments"], shape["bwd_layers"], shape["blocks"])
+    assert got == want, f"{name}: launch {shape}, this test is meant for {want}"
+    forced_oracle_check_mlp_splatter(name, d, _dev(), kernel=kernel)

@@ -368,6 +368,98 @@ def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_li
     return n_forced
 
 
+def run_hip_mlp_splatter_with_dump(d, dev, kernel=_lib.LP_KERNEL_AUTO):
+    """The production MLP-Splatter AND the same call through the DUMP twin of its backward kernel (ReLU decisions recorded).
+    Returns (production results, dump)."""
+    from lightplane_amd.splatter import mlp_splatter_relu_dump_recorder
+    prod = run_hip_mlp_splatter(d, dev, kernel)
+    with mlp_splatter_relu_dump_recorder() as rec:
+        twin = run_hip_mlp_splatter(d, dev, kernel)
+    assert rec.dump is not None, "the backward did not go through the dump hook"
+    # the twin is the same template with stores added: same arithmetic, so its gradients equal the production launch's up to the
+    # order of the fp32 atomics
+    pairs = [("grad_encoding", prod[1], twin[1]), ("grad_mlp_params", prod[2], twin[2])] + \
+        [(f"grad_input_grid{i}", a, b) for i, (a, b) in enumerate(zip(prod[3], twin[3]))]
+    for nm, a, b in pairs:
+        sc = float(a.abs().max()) + 1e-30
+        e = float((a - b).abs().max()) / sc
+        assert e <= 2e-5, f"dump twin vs production launch: {nm} differs by {e:.3e}"
+    return prod, rec.dump
+
+
+def unpack_mlp_splatter_dump(dump, widths):
+    """int32 [R, S, W] (lp_mlp_splatter_backward_relu_dump: ceil(width / 32) words per hidden layer, then the flag word) -> (list of
+    bool [R, S, width] masks in the oracle's ReLU call order, int [R, S] flags: 1 live, 2 masked out of bounds, 0 not visited)."""
+    d = dump.cpu().to(torch.int64) & 0xFFFFFFFF
+    wps = [-(-w // 32) for w in widths]
+    assert d.shape[-1] == sum(wps) + 1, (tuple(d.shape), widths)
+    bits = torch.arange(32, dtype=torch.int64)
+    masks, k = [], 0
+    for w, n in zip(widths, wps):
+        words = [((d[..., k + b, None] >> bits) & 1).bool() for b in range(n)]
+        masks.append(torch.cat(words, dim=-1)[..., :w])
+        k += n
+    return masks, d[..., -1]
+
+
+def forced_oracle_check_mlp_splatter(name, d, dev, kernel=_lib.LP_KERNEL_AUTO, tol=1e-4, chunk=4096):
+    """forced_oracle_check for the MLP-Splatter: the production backward's own ReLU decisions (DUMP twin) are forced onto the fp64
+    oracle (chunked over rays: oracle.lightplane_mlp_splatter_chunked, on the reference's fp32 geometry); every forced unit has to be
+    a near tie in that oracle, there cannot be more forced units than near-tie units, and then every output and every gradient entry
+    has to meet ``tol`` outright."""
+    import copy
+    (out, ge, gp, gin), dump = run_hip_mlp_splatter_with_dump(d, dev, kernel)
+    widths = [int(w) for w in d["mlp"].n_hidden[1:-1]]
+    masks, flags = unpack_mlp_splatter_dump(dump, widths)
+    live = flags == 1  # (the MLP of a masked-out sample feeds nothing: its decisions are not forced)
+    F = torch.float64
+    rays = copy.copy(d["rays"])
+    for f in ("directions", "origins", "near", "far", "encoding"):
+        setattr(rays, f, getattr(rays, f).detach().to(F))
+    mlp = copy.copy(d["mlp"])
+    mlp.mlp_params = d["mlp"].mlp_params.detach().to(F)
+    forcers = []
+
+    def forced(lo, hi):
+        fc = O.relu_mask_forcer([m[lo:hi] for m in masks], [live[lo:hi, :, None].expand(-1, -1, w) for w in widths],
+                                near_eps=FORCED_TIE_K * TIE_EPS)
+        forcers.append(fc)
+        return fc
+
+    old_threads = torch.get_num_threads()
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    try:
+        with O.geometry_dtype(torch.float32):
+            f_out, f_ge, f_gp, f_gin = O.lightplane_mlp_splatter_chunked(rays, d["out_sizes"], mlp, [g.to(F) for g in d["in_grids"]],
+                                                                         [u.to(F) for u in d["upstream"]], chunk=chunk, chunk_context=forced,
+                                                                         **d["cfg"])
+    finally:
+        torch.set_num_threads(old_threads)
+    assert all(fc.k == len(widths) for fc in forcers), f"the oracle evaluated {[fc.k for fc in forcers]} ReLU sites, the dump holds {len(widths)}"
+    n_forced = sum(fc.n_forced for fc in forcers)
+    n_near = sum(fc.n_near_units for fc in forcers)
+    n_units = sum(fc.n_units for fc in forcers)
+    max_margin = max([fc.max_forced_margin for fc in forcers] + [0.0])
+    worst = {}
+    for nm, a, b in [(f"out{k}", o, fo) for k, (o, fo) in enumerate(zip(out, f_out))] + \
+            [("grad_encoding", ge, f_ge), ("grad_mlp_params", gp, f_gp)] + \
+            [(f"grad_input_grid{k}", a, b) for k, (a, b) in enumerate(zip(gin, f_gin))]:
+        worst[nm] = _rel_err(a, b.numpy())
+    visited = int((flags != 0).sum())
+    FORCED_EVENTS.append(dict(name=name, forced_units=n_forced, visited_samples=visited, max_forced_margin=float(f"{max_margin:.3e}"),
+                              near_tie_units=n_near, units=n_units, worst={k: float(f"{v:.3e}") for k, v in worst.items()}))
+    print(f"forced-oracle {name}: {n_forced} ReLU units forced against the fp64 oracle's own sign over {visited} visited samples "
+          f"(largest forced |pre-activation| / site max {max_margin:.2e}; the oracle has {n_near} of {n_units} units "
+          f"within {FORCED_TIE_K * TIE_EPS:g}); max err / scale: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert max_margin <= FORCED_TIE_K * TIE_EPS, (
+        f"{name}: the kernel decided a ReLU unit against the fp64 oracle whose pre-activation is {max_margin:.3e} of its "
+        f"site's largest -- not a near tie (bar {FORCED_TIE_K * TIE_EPS:g}): the kernel's pre-activations are off")
+    assert n_forced <= n_near, f"{name}: {n_forced} forced units but only {n_near} near-tie units in the fp64 oracle"
+    bad = {k: v for k, v in worst.items() if not v <= tol}
+    assert not bad, f"{name}: with the kernel's own ReLU decisions forced onto the fp64 oracle these still miss {tol:g}: {bad}"
+    return n_forced, (out, ge, gp, gin)
+
+
 def _rays_to(rays, dev, requires_grad=False):
     r = rays.to(dev)
     if requires_grad and r.encoding is not None:

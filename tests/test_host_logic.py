@@ -432,6 +432,42 @@ def test_arithmetic_selection_and_dump_words_without_gpu():
     assert _lib.lib().lp_renderer_forward(ctypes.byref(a), None) == -1 and b"arithmetic" in _lib.lib().lp_last_error()
 
 
+def test_mlp_splatter_dump_words_and_launch_shape_without_gpu():
+    """lp_mlp_splatter_relu_dump_words (ceil(width / 32) words per hidden layer + the flag word, both kernel families) and
+    lp_mlp_splatter_launch_shape: the launches the scale tests of tests/test_gpu_config_scale.py assert they reach."""
+    from lightplane_amd.params import mlp_numel
+    from lightplane_amd.splatter import mlp_splatter_launch_shape, mlp_splatter_relu_dump_words
+
+    def mlp(dims):
+        return lp.SplatterParams(torch.zeros(mlp_numel(dims)), dims)
+
+    vox, tri = [[1, 64, 64, 64, 32]], [[1, 1, 64, 64, 16], [1, 64, 1, 64, 16], [1, 64, 64, 1, 16]]
+    in64, in32 = [[1, 32, 32, 32, 64]], [[1, 32, 32, 32, 32]]
+    deep = mlp([64, 64, 64, 32])
+    for kernel in (_lib.LP_KERNEL_AUTO, _lib.LP_KERNEL_GENERIC):
+        assert mlp_splatter_relu_dump_words(vox, deep, in64, kernel=kernel) == 2 * 2 + 1
+        assert mlp_splatter_relu_dump_words(tri, mlp([32, 64, 64, 64, 16]), in32, kernel=kernel) == 3 * 2 + 1
+        assert mlp_splatter_relu_dump_words(vox, mlp([32, 32, 32]), in32, kernel=kernel) == 1 + 1
+        assert mlp_splatter_relu_dump_words(vox, mlp([64, 16, 16, 32]), in64, kernel=kernel) == 2 + 1  # two blocks of input, one of units
+    assert mlp_splatter_relu_dump_words(vox, mlp([64, 96, 40, 32]), in64, kernel=_lib.LP_KERNEL_GENERIC) == 3 + 2 + 1
+
+    def shape(n_rays, out, m, ins, S, S_inf=0, kernel=_lib.LP_KERNEL_AUTO):
+        return mlp_splatter_launch_shape(n_rays, out, m, ins, S, S_inf, kernel=kernel)
+
+    a = shape(65536, vox, deep, in64, 16, 11)  # eight-wave forward, one-sweep two-block backward
+    assert (a["family"], a["fwd_waves"], a["bwd_segments"], a["bwd_layers"], a["blocks"]) == (3, 8, 1, 4, 2), a
+    b = shape(65536, tri, mlp([32, 64, 64, 64, 16]), in32, 16, 11)
+    assert (b["family"], b["fwd_waves"], b["bwd_segments"], b["bwd_layers"], b["blocks"]) == (3, 8, 1, 4, 2), b
+    c = shape(65536, vox, mlp([32, 32, 32]), in32, 64)  # the two-layer backward at two waves per SIMD
+    assert (c["family"], c["fwd_waves"], c["bwd_segments"], c["bwd_layers"], c["blocks"]) == (3, 4, 1, 2, 1), c
+    d = shape(1024, vox, deep, in64, 96)  # small batch: the segmented backward, four-wave forward
+    assert (d["family"], d["fwd_waves"], d["bwd_segments"], d["bwd_layers"]) == (3, 4, 6, 4), d
+    assert shape(16384, vox, deep, in64, 32)["bwd_segments"] == 2 and shape(16385, vox, deep, in64, 32)["bwd_segments"] == 1
+    assert shape(65280, vox, deep, in64, 27)["fwd_waves"] == 4  # below one round of eight-wave workgroups
+    e = shape(16384, vox, deep, in64, 27, kernel=_lib.LP_KERNEL_GENERIC)
+    assert (e["family"], e["fwd_waves"], e["bwd_segments"], e["bwd_layers"]) == (0, 1, 1, 0), e
+
+
 def test_march_order_heuristic_without_gpu():
     """march_order "auto": neighbouring rays (an image in scanline order) march rays per wavefront; unrelated rays -- random rays, and
     random PIXELS of one camera -- samples per wavefront; explicit orders are taken as given; no look when check_inputs is off."""

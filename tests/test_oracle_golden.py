@@ -203,3 +203,55 @@ def test_chunked_splatter_oracle_equals_oracle():
         _close("chunked oracle: out", got, want.detach().numpy(), tol=2e-6)
         _close("chunked oracle: grad_encoding", g_enc, rays.encoding.grad.numpy(), tol=2e-6)
         assert torch.equal(wgrid > 0, (want.detach() != 0).any(dim=-1))
+
+
+def test_chunked_mlp_splatter_oracle_equals_oracle():
+    """oracle.lightplane_mlp_splatter_chunked (the fp64 MLP-Splatter oracle of the GPU suite's forced proofs at full-chip batches: the
+    weight grid once from the geometry, then forward + backward per ray chunk) equals lightplane_mlp_splatter_naive + autograd in fp64
+    -- outputs and every gradient -- for several chunk sizes, with and without the out-of-bounds mask; and geometry_dtype(fp32) keeps
+    the fp32 oracle's cells and weights under fp64 features."""
+    import copy
+    from tests.synth import SplatterCase
+
+    F64 = torch.float64
+    for mask in (True, False):
+        case = SplatterCase("chunked", seed=31, n_rays=70, out_base=(2, 7, 5, 6, 16), is_triplane=not mask, num_samples=13,
+                            num_samples_inf=2, mask_oob=mask, contract=not mask, use_mlp=True, n_layers=3, hidden=32, feat_dim=16,
+                            in_base=(2, 5, 4, 6, 16), in_triplane=mask)
+        d = case.build()
+        rays = copy.copy(d["rays"])
+        for f in ("directions", "origins", "near", "far", "encoding"):
+            setattr(rays, f, getattr(rays, f).to(F64))
+        mlp = copy.copy(d["mlp"])
+        mlp.mlp_params = d["mlp"].mlp_params.to(F64)
+        in_grids = [g.to(F64) for g in d["in_grids"]]
+        up = [u.to(F64) for u in d["upstream"]]
+
+        r = copy.copy(rays)
+        r.encoding = r.encoding.clone().requires_grad_(True)
+        m = copy.copy(mlp)
+        m.mlp_params = mlp.mlp_params.clone().requires_grad_(True)
+        g = [x.clone().requires_grad_(True) for x in in_grids]
+        want = O.lightplane_mlp_splatter_naive(r, d["out_sizes"], m, g, **d["cfg"])
+        sum((o * u).sum() for o, u in zip(want, up)).backward()
+        for chunk in (1, 16, 33, 70, 1000):
+            outs, g_enc, g_par, g_in = O.lightplane_mlp_splatter_chunked(rays, d["out_sizes"], mlp, in_grids, up, chunk=chunk, **d["cfg"])
+            assert g_enc.dtype == F64 and g_par.dtype == F64
+            for k, (a, b) in enumerate(zip(outs, want)):
+                _close(f"chunk {chunk}: out{k}", a, b.detach().numpy(), tol=1e-12)
+            _close(f"chunk {chunk}: grad_encoding", g_enc, r.encoding.grad.numpy(), tol=1e-12)
+            _close(f"chunk {chunk}: grad_mlp_params", g_par, m.mlp_params.grad.numpy(), tol=1e-12)
+            for k, (a, b) in enumerate(zip(g_in, g)):
+                _close(f"chunk {chunk}: grad_input_grid{k}", a, b.grad.numpy(), tol=1e-12)
+
+        # geometry_dtype: fp64 features on the fp32 geometry are within fp32 round-off of both oracles, and the dtype reverts
+        r32 = copy.copy(d["rays"])
+        m32 = copy.copy(d["mlp"])
+        o32 = O.lightplane_mlp_splatter_naive(r32, d["out_sizes"], m32, d["in_grids"], **d["cfg"])
+        with O.geometry_dtype(torch.float32):
+            mixed = O.lightplane_mlp_splatter_naive(rays, d["out_sizes"], mlp, in_grids, **d["cfg"])
+        assert O._GEOMETRY_DTYPE is None
+        for a32, a64, am in zip(o32, want, mixed):
+            assert am.dtype == F64
+            scale = float(a64.detach().abs().max())
+            assert float((am - a64.detach()).abs().max()) / scale < 2e-5 and float((am - a32.double()).abs().max()) / scale < 2e-5
