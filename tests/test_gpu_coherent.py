@@ -537,7 +537,9 @@ def _chain_hip(rays_s, rays_r, dec, out_sizes, S, dev):
 def test_cfg5_chain_splatter_into_renderer():
     """BASELINE cfg 5 in miniature: several views are splatted into a voxel grid, the normalised grid is rendered from a
     new view, and the loss back-propagates through the render, the normalisation and the splat into the splatted
-    features.  Oracle: naive_splatter -> naive_renderer chained the same way."""
+    features.  Oracle: naive_splatter -> naive_renderer chained the same way.  The small companion of
+    tests/test_gpu_config_scale.py::test_cfg5_full_chain_against_oracle (the same chain at the size bench.py times): small enough for
+    the full oracle and autograd end to end, it checks what that test checks per box and per ray."""
     dev = _dev()
     gen = torch.Generator().manual_seed(2)
     S = 48

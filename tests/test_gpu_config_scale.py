@@ -9,6 +9,10 @@
   is non-zero on a 24 x 40 pixel block only -- every other ray then contributes exactly nothing, so the whole launch's grid /
   parameter gradients must equal the oracle's gradients of the block alone, and its outputs / encoding gradients on the block
   the oracle's (per-ray quantities; the rest of grad_encoding must be exactly zero).
+* configs[2] (cfg 3): the whole 128^3 x 32 splat of 65 536 rays and their grad_encoding against the chunked oracle.
+* configs[4] (cfg 5): one chained step of bench.py's JointWorkload at full size -- 13 views x 512^2 rays splatted into the 2.15 GB
+  256^3 x 32 grid, 135 x 1920 rays rendered from it, the backward through the normalisation into every splat ray's encoding -- against
+  the in-place fp64 weight pass over all 16.7 M cells, oracle.splatter_box_oracle on boxes of cells, and the forced fp64 Renderer proof.
 * index parity from the HOT kernels: the set of grid rows the MFMA backward scatters into equals the oracle's, exactly
   (test_corner_indices_bit_exact proves the formulas on a debug kernel; this proves the production tap code -- axis_taps /
   triplane_taps with the border re-expression, the voxel column walk -- addresses the same cells).
@@ -394,6 +398,195 @@ def test_cfg3_full_batch_against_oracle():
     # integer indexing of the walk at full scale: a cell received weight on the GPU iff it did in the oracle
     assert torch.equal((out != 0).any(dim=-1).cpu(), wgrid > 0), "cfg3 full: touched cells differ from the oracle's"
     assert int((wgrid > 0).sum()) > 100000
+
+
+def _footprint_box(rays, shape, S):
+    """Bounding box ((z0, z1), (y0, y1), (x0, x1)) of the cells the Renderer's samples of ``rays`` touch with non-zero weight
+    (oracle.renderer_corner_indices' corners, the reference's fp32 geometry), and the flat indices of those cells."""
+    _, D, H, W, _ = shape
+    depths = O.ray_depths(rays.near, rays.far, S, 0, 1e-5)
+    pts = depths[..., None] * rays.directions[:, None] + rays.origins[:, None]
+    cells = torch.cat([idx[valid & (w != 0)] for idx, w, valid in O._corner_setup(pts, shape, O._unnormalize_renderer)]).unique()
+    z, y, x = cells // (H * W), (cells // W) % H, cells % W
+    box = tuple((int(a.min()), int(a.max()) + 1) for a in (z, y, x))
+    return box, cells
+
+
+def _oracle_render_forward(rays, grid64, decoder, cfg, chunk=512):
+    """fp64 oracle forward (fp32 geometry) of ``rays`` on the fp64 grid ``grid64``, in chunks; no gradients."""
+    dec = copy.copy(decoder)
+    dec.mlp_params = decoder.mlp_params.to(F64)
+    outs = [[], [], []]
+    with torch.no_grad(), O.geometry_dtype(torch.float32):
+        for lo in range(0, rays.n_rays, chunk):
+            r = rays[lo:lo + chunk]
+            r.encoding = r.encoding.to(F64)
+            for k, o in enumerate(O.lightplane_renderer_naive(r, [grid64], dec, **cfg)):
+                outs[k].append(o)
+    return [torch.cat(o) for o in outs]
+
+
+def test_cfg5_full_chain_against_oracle(monkeypatch):
+    """BASELINE configs[4] at the size bench.py's `cfg5` times, one chained step through JointWorkload.forward itself: 13 views x 512^2
+    rays splatted into the 256^3 x 32 voxel grid (2.15 GB: the ray-block-major forward walk, 26 624 ray blocks; the backward with one
+    segment, grad_encoding a plain store; 4-row patches of 512-ray rows over 13 views), normalised over 2^29 entries, then 135 x 1920 rays
+    of a 1080p camera rendered from it at S = 256 (the 3-waves-per-SIMD forward), the end-to-end backward.  The upstream gradient is
+    non-zero on a 24 x 40 render block (not aligned to the 32-ray waves) only.  Held to fp64 oracles:
+
+    A. the kernel's weight grid (the first tensor LightplaneSplatterFunction saves) against the in-place fp64 weight pass over all
+       16.7 M cells at 1e-4, the cells with weight > 0 exactly the oracle's; the splat finite and in [0, 1) everywhere;
+    B. the splat's values against oracle.splatter_box_oracle on four boxes (the render block's footprint, the grid's low and high index
+       corners, an interior box) at 1e-4;
+    C. the Renderer on the grid it was given: forced_oracle_check on the block (every output and gradient entry, the whole 2.15 GB grid
+       gradient included, at 1e-4); the chain's render outputs bit-identical to that launch's, its retained grid gradient within the
+       2e-5 of fp32 atomic order; every 63rd ray's outputs (all 135 rows, every lane) against the fp64 oracle forward at 1e-4;
+    D. the chain into the splat encodings: every candidate ray of the box oracle's prefilter (upstream = the forced oracle's grid
+       gradient, the weights of A) at 1e-4, every other of the 3 407 872 rays exactly 0;
+    E. end to end: the block's render outputs against box-oracle splat -> fp64 oracle render (the grid zero outside the footprint box).
+
+    The block and the boxes were chosen with the oracle alone; the test asserts that they are not vacuous.  Run time on one MI355X with
+    the oracle on 16 host threads (the printed `cfg5 full chain: time` line): 52-54 s -- the chained step 2.6 s, the forced proof of the
+    render block 8.3 s (its two GPU launches and the fp64 oracle), the other host oracles 42 s (the weight pass over 872 M samples, the
+    box oracles, the oracle renders).  In the same run test_cfg3_full_batch_against_oracle took under 5 s, the whole GPU suite 4.4 min."""
+    import time
+
+    import bench
+    from tests.test_gpu_parity import forced_oracle_check
+
+    for k in ("CFG5_VIEWS", "CFG5_IMG", "CFG5_GRID", "CFG5_ROWS", "CFG5_S", "LP_BENCH_NO_ROW_HINT"):
+        monkeypatch.delenv(k, raising=False)
+    dev = _dev()
+    t_gpu, t_cpu = 0.0, 0.0
+    t = time.time()
+    wl = bench.JointWorkload(0, 1, dev, None, _lib.LP_KERNEL_AUTO)
+    assert (wl.V, wl.img, wl.G, wl.rows, wl.S, wl.C) == (13, 512, 256, 135, 256, 32)
+    shape = wl.sizes[0]
+    assert shape == [1, 256, 256, 256, 32] and wl.splat_rays.n_rays == 13 * 512 * 512 and wl.cam.n_rays == 135 * 1920
+    n_cells = 256 ** 3
+    assert n_cells * 32 * 4 > 1e9, "the grid has to select the ray-block-major forward walk (splat_forward_group: > 1 GB)"
+    S = wl.S
+
+    # the render block (rows 100..123 of the 135, columns 941..980: 941 = 29 * 32 + 13) and its upstream gradient
+    Wimg, y0, x0, bh, bw = 1920, 100, 941, 24, 40
+    idx = (torch.arange(y0, y0 + bh)[:, None] * Wimg + torch.arange(x0, x0 + bw)[None, :]).reshape(-1)
+    n = wl.cam.n_rays
+    gen = torch.Generator().manual_seed(55)
+    up = [torch.zeros(n), torch.zeros(n), torch.zeros(n, 3)]
+    up[0][idx] = torch.randn(idx.numel(), generator=gen)
+    up[1][idx] = torch.randn(idx.numel(), generator=gen)
+    up[2][idx] = torch.randn(idx.numel(), 3, generator=gen)
+
+    # one chained step, recording the splat the Renderer consumed and the weight grid its launch produced
+    captured = {}
+    splatter = bench.lp.lightplane_splatter
+
+    def recording_splatter(*args, **kw):
+        saved = []
+
+        def pack(x):
+            saved.append(x)
+            return x
+
+        with torch.autograd.graph.saved_tensors_hooks(pack, lambda x: x):
+            grid = splatter(*args, **kw)
+        grid.retain_grad()
+        captured.update(grid=grid, weight=saved[0], kw=kw)
+        return grid
+
+    monkeypatch.setattr(bench.lp, "lightplane_splatter", recording_splatter)
+    wl.zero_grads()
+    out = wl.forward(replicated=False)
+    torch.autograd.backward(list(out[:3]), [u.to(dev) for u in up])
+    torch.cuda.synchronize(dev)
+    monkeypatch.setattr(bench.lp, "lightplane_splatter", splatter)
+    grid, wk = captured["grid"].detach(), captured["weight"]
+    assert captured["kw"].get("rays_per_row") == 512, "the chain has to run with bench.py's row-length hint"
+    assert wk.shape == (n_cells,) and wk.dtype == torch.float32 and grid.shape == (n_cells, 32)
+    g_chain = captured["grid"].grad
+    ge_chain = wl.splat_rays.encoding.grad
+    out = [o.detach() for o in out[:3]]
+    t_gpu += time.time() - t
+
+    old_threads = torch.get_num_threads()
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    try:
+        # A. the weight grid, whole grid
+        t = time.time()
+        rays_c = wl.splat_rays.to("cpu")
+        rays_c.encoding = rays_c.encoding.detach()
+        cfg_s = dict(num_samples=S, num_samples_inf=0, mask_out_of_bounds_samples=False, contract_coords=False)
+        (w_or,) = O.splatter_weight_grids(rays_c, [shape], S, sum_dtype=F64)
+        w_or = w_or[:, 0]
+        t_cpu += time.time() - t
+        wk_c = wk.cpu()
+        _assert_close("cfg5 full: weight grid", wk_c, w_or.numpy())
+        assert torch.equal(wk_c > 0, w_or > 0), f"cfg5 full: cells with weight differ in {int(((wk_c > 0) != (w_or > 0)).sum())} cells"
+        assert bool(torch.isfinite(grid).all()) and float(grid.min()) >= 0.0 and float(grid.max()) < 1.0
+        del wk_c
+
+        # B. the splat's values on four boxes
+        t = time.time()
+        cam_c = wl.cam.to("cpu")
+        fbox, fcells = _footprint_box(cam_c[idx], shape, S)
+        boxes = {"footprint": fbox, "low_corner": ((0, 24), (0, 24), (0, 24)), "high_corner": ((232, 256), (232, 256), (232, 256)),
+                 "interior": ((116, 140), (116, 140), (116, 140))}
+        box_res = {}
+        for nm, box in boxes.items():
+            res = O.splatter_box_oracle(rays_c, shape, box, cfg_s)
+            box_res[nm] = res
+            assert int((res.weight_sums > 0).sum()) >= 1000, f"value box {nm} {box}: too few cells with weight"
+            (z0, z1), (yb0, yb1), (xb0, xb1) = box
+            got = grid.reshape(256, 256, 256, 32)[z0:z1, yb0:yb1, xb0:xb1]
+            _assert_close(f"cfg5 full: splat values, {nm} box {box}", got, (res.feature_sums / res.weight_sums.clamp(min=1e-5)[..., None]).numpy())
+        t_cpu += time.time() - t
+
+        # C. the Renderer on the grid it was given: the forced fp64 proof of the whole launch on the block
+        t = time.time()
+        cam_c.encoding = cam_c.encoding.detach()
+        grid_c = grid.cpu().reshape(shape)
+        cfg_r = dict(num_samples=S, gain=1.0, num_samples_inf=0, mask_out_of_bounds_samples=False, contract_coords=False,
+                     inject_noise_sigma=0.0, inject_noise_seed=0)
+        d = dict(rays=cam_c, grids=[grid_c], color_grids=None, decoder=wl.dec_c, scaffold=None, cfg=cfg_r, sizes=[shape], upstream=tuple(up))
+        _, prod, forced = forced_oracle_check("cfg5 full chain: render block", d, dev, idx, return_results=True)
+        t_proof = time.time() - t
+        for k in range(3):
+            assert torch.equal(out[k], prod[0][k]), f"cfg5 full: chained render output {k} differs from the proof launch's"
+        err = float((g_chain.reshape(-1) - prod[3][0].reshape(-1)).abs().max() / prod[3][0].abs().max())
+        assert err <= 2e-5, f"cfg5 full: retained grid gradient vs the proof launch's {err:.3e}"
+        f_gg = forced[3][0].reshape(n_cells, 32)
+        del prod
+        t = time.time()
+        sidx = torch.arange(0, n, 63)
+        assert sidx.numel() >= 4096 and (sidx // Wimg).unique().numel() == 135 and (sidx % 32).unique().numel() == 32
+        grid64 = grid_c.to(F64)
+        o_sub = _oracle_render_forward(cam_c[sidx], grid64, wl.dec_c, cfg_r)
+        for k, nm in enumerate(("ray_length", "neg_log_t", "feature")):
+            _assert_close(f"cfg5 full: every 63rd ray, {nm}", out[k][sidx.to(dev)], o_sub[k].numpy())
+
+        # D. the chain into the splat encodings
+        nz = (f_gg != 0).any(dim=-1)
+        assert int(nz[fcells].sum()) >= 1000 and int(nz.sum()) == int(nz[fcells].sum())
+        res = O.splatter_box_oracle(rays_c, shape, fbox, cfg_s, upstream=f_gg, weights=w_or)
+        cand = res.candidates
+        assert int((res.grad_encoding != 0).any(dim=-1).sum()) >= 1000
+        dc = cand.to(dev)
+        _assert_close("cfg5 full: grad_encoding of the prefilter's candidate rays", ge_chain[dc], res.grad_encoding[cand].numpy())
+        assert float(ge_chain[~dc].abs().max()) == 0.0, "cfg5 full: a ray that cannot reach the footprint box got an encoding gradient"
+
+        # E. end to end: box-oracle splat -> fp64 oracle render, on a grid zero outside the footprint box
+        r = box_res["footprint"]
+        (z0, z1), (yb0, yb1), (xb0, xb1) = fbox
+        grid64.zero_()
+        grid64[0, z0:z1, yb0:yb1, xb0:xb1] = r.feature_sums / r.weight_sums.clamp(min=1e-5)[..., None]
+        o_blk = _oracle_render_forward(cam_c[idx], grid64, wl.dec_c, cfg_r)
+        for k, nm in enumerate(("ray_length", "neg_log_t", "feature")):
+            _assert_close(f"cfg5 full: end to end, block {nm}", out[k][idx.to(dev)], o_blk[k].numpy())
+        t_cpu += time.time() - t
+    finally:
+        torch.set_num_threads(old_threads)
+    print(f"cfg5 full chain: time: chained step {t_gpu:.1f} s, forced proof of the render block (GPU launches + fp64 oracle) {t_proof:.1f} s, "
+          f"other host oracles {t_cpu:.1f} s; footprint box {fbox} ({fcells.numel()} cells), {int(cand.sum())} candidate splat rays, "
+          f"{res.n_samples} samples evaluated")
 
 
 SPLAT_INDEX_CASES = {

@@ -332,7 +332,7 @@ def oracle_forced(d, dump, idx=None, chunk=2048, dtype=torch.float64, words_per_
 FORCED_EVENTS = []  # one record per forced-oracle check; printed by conftest.pytest_terminal_summary
 
 
-def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_lib.LP_KERNEL_AUTO, **extra):
+def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_lib.LP_KERNEL_AUTO, return_results=False, **extra):
     """THE PROOF behind the ReLU-flip allowance (round-4 review, next 2): the production backward's own ReLU decisions, read
     back from the DUMP twin of its kernel, are forced onto the fp64 oracle; then EVERY entry of every gradient family and every
     output has to meet the north_star bar outright -- no allowance, no second oracle, no mask.  Whatever separated the kernel
@@ -341,7 +341,10 @@ def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_li
     The forcing itself is bounded (round-5 review, weak 1): a kernel with WRONG pre-activations would decide many units against the
     oracle and forcing them all would hide it.  So every forced unit has to be a near tie in the fp64 oracle -- its |pre-activation|
     at most FORCED_TIE_K * TIE_EPS of its site's largest one -- and there cannot be more forced units than the oracle has units
-    that close to zero."""
+    that close to zero.
+
+    ``return_results``: return (n_forced, the production launch's results as run_hip_renderer returns them, the forced fp64 oracle's
+    (outs, grad_params, grad_encoding, grad_grids, grad_color_grids)) instead of n_forced alone, once everything above has passed."""
     prod, dump, wps = run_hip_renderer_with_dump(d, dev, kernel, **extra)
     out, gp, ge, gg, gc = prod
     f_out, f_gp, f_ge, f_gg, f_gc, st = oracle_forced(d, dump, idx, chunk=chunk, words_per_site=wps)
@@ -365,6 +368,8 @@ def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_li
     assert n_forced <= st["n_near_units"], f"{name}: {n_forced} forced units but only {st['n_near_units']} near-tie units in the fp64 oracle"
     bad = {k: v for k, v in worst.items() if not v <= tol}
     assert not bad, f"{name}: with the kernel's own ReLU decisions forced onto the fp64 oracle these still miss {tol:g}: {bad}"
+    if return_results:
+        return n_forced, prod, (f_out, f_gp, f_ge, f_gg, f_gc)
     return n_forced
 
 

@@ -255,3 +255,172 @@ def test_chunked_mlp_splatter_oracle_equals_oracle():
             assert am.dtype == F64
             scale = float(a64.detach().abs().max())
             assert float((am - a64.detach()).abs().max()) / scale < 2e-5 and float((am - a32.double()).abs().max()) / scale < 2e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the box-restricted Splatter oracle (oracle.splatter_box_oracle) and the in-place weight pass (oracle.splatter_weight_grids): the
+# references of tests/test_gpu_config_scale.py::test_cfg5_full_chain_against_oracle, equal to the full oracle where both run
+# ---------------------------------------------------------------------------------------------------------------------
+BOX_SHAPE = [1, 12, 14, 10, 8]   # [B, D, H, W, C]: D, H, W all different, so a transposed axis cannot pass
+BOX_S = 24
+
+
+def _box_rays():
+    """Rays of every kind the prefilter has to get right: a pinhole image from outside (rays that cross the grid obliquely, rays that
+    miss it), rays parallel to each axis (both directions) on a lattice of un-normalised coordinates at, just inside and just outside
+    every integer -- a face of the footprint region of some box lies on each --, rays that start inside the grid, rays far away."""
+    import math as _m
+    from lightplane_amd.rays import Rays
+    from tests.synth import cat_rays, pinhole_rays
+    gen = torch.Generator().manual_seed(17)
+    _, D, H, W, C = BOX_SHAPE
+    size = {0: W, 1: H, 2: D}
+    parts = [pinhole_rays(16, 20, cam_dist=2.3, azimuth_deg=20.0, elevation_deg=35.0)]
+    for ax in (0, 1, 2):
+        a, b = [q for q in (0, 1, 2) if q != ax]
+        ua = torch.tensor([-1.0, -0.9999, 0.0, 2.0, 3.0001, 4.5, size[a] - 1.0, size[a] - 0.5, float(size[a])])
+        ub = torch.tensor([-1.0, 1.0, 2.9999, 5.0, size[b] - 1.0, float(size[b])])
+        uu_a, uu_b = torch.meshgrid(ua, ub, indexing="ij")
+        n = uu_a.numel()
+        o = torch.zeros(n, 3)
+        o[:, a] = (uu_a.reshape(-1) + 0.5) * 2.0 / size[a] - 1.0
+        o[:, b] = (uu_b.reshape(-1) + 0.5) * 2.0 / size[b] - 1.0
+        for sign in (1.0, -1.0):
+            oo = o.clone()
+            oo[:, ax] = -2.0 * sign
+            dd = torch.zeros(n, 3)
+            dd[:, ax] = sign
+            parts.append(Rays(directions=dd, origins=oo, grid_idx=torch.zeros(n, dtype=torch.long), near=torch.full((n,), 0.7),
+                              far=torch.full((n,), 3.3), encoding=None))
+    n = 200   # starting inside the grid (and inside most boxes), random directions, short marches
+    dd = torch.randn(n, 3, generator=gen)
+    parts.append(Rays(directions=dd / dd.norm(dim=-1, keepdim=True), origins=torch.rand(n, 3, generator=gen) * 1.4 - 0.7,
+                      grid_idx=torch.zeros(n, dtype=torch.long), near=torch.zeros(n), far=torch.full((n,), 1.3), encoding=None))
+    n = 20    # far away and pointing away
+    parts.append(Rays(directions=torch.ones(n, 3) / _m.sqrt(3.0), origins=torch.full((n, 3), 3.0) + torch.rand(n, 3, generator=gen),
+                      grid_idx=torch.zeros(n, dtype=torch.long), near=torch.zeros(n), far=torch.full((n,), 2.0), encoding=None))
+    rays = cat_rays(parts)
+    rays.encoding = torch.rand(rays.n_rays, C, generator=gen)
+    return rays
+
+
+def _box_cases():
+    """(name, ((z0, z1), (y0, y1), (x0, x1))): a box at each corner of the grid (every face and every corner, clamped and partly
+    valid corners), a box on each face alone, one interior box, a single cell, the whole grid."""
+    _, D, H, W, _ = BOX_SHAPE
+    boxes = []
+    for bits in range(8):
+        z = (0, 5) if bits & 4 else (7, D)
+        y = (0, 6) if bits & 2 else (9, H)
+        x = (0, 4) if bits & 1 else (6, W)
+        boxes.append((f"corner{bits}", (z, y, x)))
+    mid = ((4, 8), (5, 10), (3, 7))
+    for ax, ext in enumerate((D, H, W)):
+        for lo, hi in ((0, 3), (ext - 3, ext)):
+            b = list(mid)
+            b[ax] = (lo, hi)
+            boxes.append((f"face{ax}_{lo}", tuple(b)))
+    boxes += [("interior", ((3, 9), (4, 10), (2, 8))), ("single_cell", ((6, 7), (7, 8), (4, 5))), ("whole", ((0, D), (0, H), (0, W)))]
+    return boxes
+
+
+def _rays64(rays):
+    import copy
+    r = copy.copy(rays)
+    for f in ("directions", "origins", "near", "far", "encoding"):
+        setattr(r, f, getattr(rays, f).to(torch.float64))
+    return r
+
+
+def _naive_box_reference(rays, cfg, box, gen):
+    """The full fp64 oracle on the reference's fp32 geometry: normalised output, un-normalised feature / weight sums (the oracle's own
+    scatter, oracle._splat_one_grid) and, for an upstream zero outside ``box``, grad_encoding by autograd."""
+    B, D, H, W, C = BOX_SHAPE
+    r = _rays64(rays)
+    r.encoding = r.encoding.clone().requires_grad_(True)
+    up = torch.zeros(D, H, W, C, dtype=torch.float64)
+    (z0, z1), (y0, y1), (x0, x1) = box
+    up[z0:z1, y0:y1, x0:x1] = torch.randn(z1 - z0, y1 - y0, x1 - x0, C, generator=gen, dtype=torch.float64)
+    with O.geometry_dtype(torch.float32):
+        (out,) = O.lightplane_splatter_naive(r, [BOX_SHAPE], num_samples=BOX_S, **cfg)
+        (out[0] * up).sum().backward()
+        pts = O._splatter_points(r, BOX_S, 0, False, 1e-5)
+    mask = O.in_bounds(pts).double() if cfg["mask_out_of_bounds_samples"] else torch.ones(pts.shape[:-1], dtype=torch.float64)
+    with torch.no_grad():
+        f = O._splat_one_grid(torch.zeros(D * H * W, C, dtype=torch.float64), BOX_SHAPE, pts, r.grid_idx,
+                              r.encoding[:, None, :].expand(-1, BOX_S, -1), mask)
+        w = O._splat_one_grid(torch.zeros(D * H * W, 1, dtype=torch.float64), BOX_SHAPE, pts, r.grid_idx,
+                              torch.ones(pts.shape[:-1] + (1,), dtype=torch.float64), mask)
+    return out[0].detach(), f.reshape(D, H, W, C), w.reshape(D, H, W), up, r.encoding.grad
+
+
+def _box_values(res):
+    return res.feature_sums / res.weight_sums.clamp(min=1e-5)[..., None]
+
+
+@pytest.mark.parametrize("mask", [False, True], ids=["nomask", "mask_oob"])
+def test_box_splatter_oracle_equals_oracle(mask):
+    """oracle.splatter_box_oracle (only the samples the analytic prefilter keeps, corners outside the box dropped) and the in-place
+    fp64 weight pass equal lightplane_splatter_naive in fp64 on the fp32 geometry, restricted to the box, at the 2e-6 of
+    test_chunked_splatter_oracle_equals_oracle: feature sums, weight sums, normalised values, and grad_encoding of every ray against
+    autograd of the full oracle with an upstream zero outside the box.  Every box of _box_cases, all ray kinds of _box_rays.
+    The bar bites: a splat with one sample per ray dropped and one with the rays moved by a quarter cell miss 1e-4 in the box."""
+    B, D, H, W, C = BOX_SHAPE
+    rays = _box_rays()
+    cfg = dict(num_samples_inf=0, mask_out_of_bounds_samples=mask, contract_coords=False)
+    gen = torch.Generator().manual_seed(3 + mask)
+    (wpass,) = O.splatter_weight_grids(rays, [BOX_SHAPE], BOX_S, sum_dtype=torch.float64, chunk=97, **cfg)
+    assert wpass.dtype == torch.float64
+    wpass = wpass.reshape(D, H, W)
+    seen_cand, seen_miss, seen_partial = 0, 0, 0
+    for name, box in _box_cases():
+        out, f, w, up, g_want = _naive_box_reference(rays, cfg, box, gen)
+        (z0, z1), (y0, y1), (x0, x1) = box
+        sel = (slice(z0, z1), slice(y0, y1), slice(x0, x1))
+        res = O.splatter_box_oracle(rays, BOX_SHAPE, box, dict(cfg, num_samples=BOX_S), upstream=up)
+        _close(f"{name}: feature sums", res.feature_sums, f[sel].numpy(), tol=2e-6)
+        _close(f"{name}: weight sums", res.weight_sums, w[sel].numpy(), tol=2e-6)
+        _close(f"{name}: weight pass", wpass[sel], w[sel].numpy(), tol=2e-6)
+        _close(f"{name}: values", _box_values(res), out[sel].numpy(), tol=2e-6)
+        _close(f"{name}: grad_encoding", res.grad_encoding, g_want.numpy(), tol=2e-6)
+        assert bool((res.grad_encoding[~res.candidates] == 0).all())
+        assert int((w[sel] > 0).sum()) > 0 and bool((g_want[~res.candidates] == 0).all())
+        seen_cand += int(res.candidates.sum())
+        seen_miss += int((~res.candidates).sum())
+        seen_partial += int((res.n_samples < res.candidates.sum() * BOX_S))
+    assert seen_cand > 0 and seen_miss > 0 and seen_partial > 0
+    _close("weight pass, whole grid", wpass, w.numpy(), tol=2e-6)
+
+    # the bar bites: subtly wrong splats of the same rays, through the same box oracle, miss 1e-4 inside the box
+    box = dict(_box_cases())["interior"]
+    ref =_box_values(O.splatter_box_oracle(rays, BOX_SHAPE, box, dict(cfg, num_samples=BOX_S)))
+    import copy
+    drop = copy.copy(rays)     # the first sample of every ray dropped: S - 1 samples from the second sample's depth on
+    drop.near = rays.near + (rays.far - rays.near) / (BOX_S - 1)
+    moved = copy.copy(rays)    # every ray moved by a quarter cell along x
+    moved.origins = rays.origins + torch.tensor([0.25 * 2.0 / W, 0.0, 0.0])
+    for nm, r, s in (("one sample dropped", drop, BOX_S - 1), ("moved a quarter cell", moved, BOX_S)):
+        got = _box_values(O.splatter_box_oracle(r, BOX_SHAPE, box, dict(cfg, num_samples=s)))
+        err = float((got - ref).abs().max() / ref.abs().max())
+        assert err > 1e-4, f"{nm}: differs from the right splat by only {err:.2e}: the 1e-4 bar would not see it"
+
+
+def test_box_splatter_oracle_refuses_what_it_does_not_cover():
+    """Triplanes, contraction, beyond-far samples, several batch entries and empty boxes raise; they are never approximated."""
+    rays = _box_rays()
+    cfg = dict(num_samples=BOX_S, num_samples_inf=0, mask_out_of_bounds_samples=False, contract_coords=False)
+    box = ((0, 2), (0, 2), (0, 2))
+    with pytest.raises(NotImplementedError):
+        O.splatter_box_oracle(rays, [1, 1, 14, 10, 8], box, cfg)
+    with pytest.raises(NotImplementedError):
+        O.splatter_box_oracle(rays, [2, 12, 14, 10, 8], box, cfg)
+    with pytest.raises(NotImplementedError):
+        O.splatter_box_oracle(rays, BOX_SHAPE, box, dict(cfg, contract_coords=True))
+    with pytest.raises(NotImplementedError):
+        O.splatter_box_oracle(rays, BOX_SHAPE, box, dict(cfg, num_samples_inf=4))
+    with pytest.raises(ValueError):
+        O.splatter_box_oracle(rays, BOX_SHAPE, ((3, 3), (0, 2), (0, 2)), cfg)
+    up = torch.zeros(BOX_SHAPE)
+    up[0, 5, 5, 5, 0] = 1.0
+    with pytest.raises(AssertionError, match="outside the box"):
+        O.splatter_box_oracle(rays, BOX_SHAPE, box, cfg, upstream=up)
