@@ -317,7 +317,8 @@ int lp_abi_sizeof(int which);
 int lp_renderer_backward_segments(const LpRendererArgs* args);
 
 /* Which kernel family LP_KERNEL_AUTO selects for these arguments (no launch; shapes only):
- *   lp_renderer_kernel_family: 0 shape-generic VALU kernels, 1 tuned bf16x3 MFMA kernels of the default decoder (2/2/2 x 32),
+ *   lp_renderer_kernel_family: the BACKWARD's family = the family of lp_renderer_forward (lp_renderer_forward_ws has its own answer,
+ *                              lp_renderer_forward_family below): 0 shape-generic VALU kernels, 1 tuned bf16x3 MFMA kernels of the default decoder (2/2/2 x 32),
  *                              3 layer-looped bf16x3 MFMA family (1-4 layers per MLP, one hidden width of 16 / 32 and <= 32
  *                              colour channels -- or width 64 / 64 grid channels with at most 2 layers per MLP and <= 4 colour
  *                              channels); 2 (the fp32-MFMA hidden-64 family of 0.1 - 0.2.3) is no longer returned
@@ -330,6 +331,27 @@ int lp_splatter_kernel_family(const LpSplatterArgs* args);
 
 int lp_renderer_forward(const LpRendererArgs* args, void* stream);
 int lp_renderer_backward(const LpRendererArgs* args, void* stream);
+
+/* Forward with a caller-provided workspace: the layer-looped MFMA forward also for the decoders lp_renderer_kernel_family() turns down
+ * ONLY for their depth -- hidden width 64 (or 64 grid channels) with 3 or 4 layers in any of the three MLPs; default arithmetic,
+ * <= 4 colour channels, everything else as family 3.  Their backward stays on the shape-generic kernels (lp_renderer_backward,
+ * unchanged): this forward leaves neg_log_t and neg_log_t_ckpt exactly as that backward reads them, and stops early-terminated
+ * rays per 64 consecutive rays, the wavefront of the generic kernels.  For every other shape -- and for LP_KERNEL_GENERIC and
+ * LP_ARITH_FP32 -- it IS lp_renderer_forward (workspace ignored).
+ *   lp_renderer_forward_family: what lp_renderer_forward_ws runs (no launch; shapes only): 0 / 1 / 3 as lp_renderer_kernel_family,
+ *     3 also for a deep decoder whose weight images fit the 160 KB LDS without the backward's tiles (e.g. 3/2/2 x 64), 4 = the
+ *     layer-looped forward with STREAMED weight images (a resident prefix of layers + a two-slot LDS ring for the rest).
+ *     A decoder with a separate colour grid is laid out WITH the ring's two slots reserved (the resident kernel has no eight-wave form
+ *     for it): 0/3/3 x 64 still fits whole and reports 3 (four-wave resident kernel), 0/4/4 x 64 reports 4 (its last layers pass
+ *     through the ring) although its 20 block images alone would fit the LDS.
+ *   lp_renderer_forward_workspace_bytes: 0 unless the family is 4; then the bytes of the streamed layers' pre-split block images,
+ *     back to back, no header (per layer ceil(rows_in / 32) * ceil(cols / 32) * 6528).  Depends on shapes only.
+ *   lp_renderer_forward_ws: packs the images into `workspace` (device memory, 16-byte aligned, at least that many bytes; owned by the
+ *     caller, free to reuse once the call's work on `stream` is done) and runs the forward on `stream`.  LP_EINVAL, before any launch, when
+ *     the family is 4 and the workspace is NULL, short or misaligned. */
+int lp_renderer_forward_family(const LpRendererArgs* args);
+int64_t lp_renderer_forward_workspace_bytes(const LpRendererArgs* args);
+int lp_renderer_forward_ws(const LpRendererArgs* args, void* workspace, int64_t workspace_bytes, void* stream);
 
 int lp_splatter_forward(const LpSplatterArgs* args, void* stream);
 /* feature[r, :] /= max(weight[r], 1e-5) for r in [0, n_rows) (in place). */

@@ -109,6 +109,7 @@ LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(
 EXPORTS = (
     "lp_version", "lp_last_error", "lp_abi_sizeof", "lp_renderer_forward", "lp_renderer_backward",
     "lp_splatter_forward", "lp_splatter_normalize", "lp_splatter_backward", "lp_hash_randn",
+    "lp_renderer_forward_family", "lp_renderer_forward_ws",  # (+ lp_renderer_forward_workspace_bytes, which returns int64_t)
     "lp_renderer_corner_rows", "lp_renderer_kernel_family", "lp_splatter_kernel_family",
     "lp_renderer_backward_segments", "lp_renderer_backward_relu_dump", "lp_renderer_relu_dump_words", "lp_build_info",
     "lp_ray_embedding_forward", "lp_ray_embedding_backward",
@@ -160,6 +161,12 @@ def lib() -> C.CDLL:
     L.lp_build_info.restype = C.c_char_p
     L.lp_renderer_kernel_family.restype = C.c_int
     L.lp_renderer_kernel_family.argtypes = [C.POINTER(LpRendererArgs)]
+    L.lp_renderer_forward_family.restype = C.c_int
+    L.lp_renderer_forward_family.argtypes = [C.POINTER(LpRendererArgs)]
+    L.lp_renderer_forward_workspace_bytes.restype = C.c_int64
+    L.lp_renderer_forward_workspace_bytes.argtypes = [C.POINTER(LpRendererArgs)]
+    L.lp_renderer_forward_ws.restype = C.c_int
+    L.lp_renderer_forward_ws.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p, C.c_int64, C.c_void_p]
     L.lp_renderer_backward_segments.restype = C.c_int
     L.lp_renderer_backward_segments.argtypes = [C.POINTER(LpRendererArgs)]
     L.lp_splatter_kernel_family.restype = C.c_int

@@ -27,6 +27,13 @@
                        unrelated rays, e.g. random training batches -- 3x on the reference's speed benchmark), "auto" (default) =
                        "samples" unless most consecutive rays of the batch are neighbours (directions within 5 %, origins within
                        0.05), decided together with the ``check_inputs`` device sync (no extra sync; "rays" when ``check_inputs`` is off).
+``deep_forward_mfma``  the Renderer FORWARD of decoders with hidden width 64 (or 64 grid channels) and 3-4 layers in an MLP runs the
+                       layer-looped MFMA forward (``lp_renderer_forward_ws``: weight images resident in LDS where they fit, streamed
+                       per layer through a workspace the call allocates with ``torch.empty`` where they do not) instead of the
+                       shape-generic kernel; their backward runs the shape-generic kernels either way.  Off: the old entry point,
+                       nothing differs from releases before the switch.  Default OFF: the new forward is held to the fp64 oracle,
+                       but its times against the shape-generic forward (the gate of DESIGN.md 4.3: faster by more than the 2 %
+                       run-to-run spread on every measured shape and batch) have not been taken; it becomes the default with them.
 """
 import os
 
@@ -38,4 +45,5 @@ segment_forward: bool = os.environ.get("LIGHTPLANE_AMD_SEGMENT_FORWARD", "1") !=
 warn_generic_kernel: bool = os.environ.get("LIGHTPLANE_AMD_WARN_GENERIC", "1") != "0"
 stop_transmittance: float = float(os.environ.get("LIGHTPLANE_AMD_STOP_TRANSMITTANCE", "0"))
 arithmetic: int = int(os.environ.get("LIGHTPLANE_AMD_ARITHMETIC", "0"))
+deep_forward_mfma: bool = os.environ.get("LIGHTPLANE_AMD_DEEP_FORWARD_MFMA", "0") == "1"
 march_order: str = os.environ.get("LIGHTPLANE_AMD_MARCH_ORDER", "auto")

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "liblightplane_hip.so")
 # (longest compiles first: the translation units are compiled in parallel)
-SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_dump.hip", "lp_renderer_mfma_bwd.hip", "lp_renderer_mfma_bwd_dump.hip", "lp_renderer_mfma_bwd_c32.hip", "lp_renderer_mfma_bwd_aux.hip", "lp_renderer_mfma_bwd_tm.hip",
+SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_stream.hip", "lp_renderer_loop_dump.hip", "lp_renderer_mfma_bwd.hip", "lp_renderer_mfma_bwd_dump.hip", "lp_renderer_mfma_bwd_c32.hip", "lp_renderer_mfma_bwd_aux.hip", "lp_renderer_mfma_bwd_tm.hip",
            "lp_splatter_mlp_loop.hip", "lp_splatter_mlp_loop_dump.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
            "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_dump.hip", "lp_splatter_mlp_loop_shallow.hip",
            "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_api.hip"]

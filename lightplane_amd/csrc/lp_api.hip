@@ -233,10 +233,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -339,6 +339,36 @@ int lp_renderer_forward(const LpRendererArgs* args, void* stream) {
   if (fam == 1 && a.kernel != LP_KERNEL_GENERIC) return renderer_forward_mfma(a, (hipStream_t)stream);
   if (fam == 3 && a.kernel != LP_KERNEL_GENERIC) return renderer_forward_loop(a, (hipStream_t)stream);
   return renderer_forward_generic(a, (hipStream_t)stream);
+}
+
+// The forward's own selection (lp_renderer_forward_ws): the family of lp_renderer_kernel_family, and on the shapes that one turns down
+// only for their depth at hidden width 64 / 64 grid channels the layer-looped forward -- 3 with resident weight images, 4 streamed.
+static bool deep_forward(const LpRendererArgs& a, int fam) {
+  return fam == 0 && a.kernel != LP_KERNEL_GENERIC && renderer_deep_forward_supported(a);
+}
+
+int lp_renderer_forward_family(const LpRendererArgs* args) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  if (args->kernel == LP_KERNEL_GENERIC) return 0;
+  const char* why = "";
+  const int fam = select_renderer(*args, &why);
+  return deep_forward(*args, fam) ? renderer_deep_forward_family(*args) : fam;
+}
+
+int64_t lp_renderer_forward_workspace_bytes(const LpRendererArgs* args) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  const char* why = "";
+  return deep_forward(*args, select_renderer(*args, &why)) ? renderer_deep_forward_workspace(*args) : 0;
+}
+
+int lp_renderer_forward_ws(const LpRendererArgs* args, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  LpRendererArgs a;
+  int rc = normalized_renderer_args(args, false, a);
+  if (rc) return rc;
+  const char* why = "";
+  if (deep_forward(a, select_renderer(a, &why))) return renderer_forward_deep(a, workspace, workspace_bytes, (hipStream_t)stream);
+  return lp_renderer_forward(args, stream);
 }
 
 int lp_renderer_backward(const LpRendererArgs* args, void* stream) {

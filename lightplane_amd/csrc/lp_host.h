@@ -68,12 +68,20 @@ int renderer_forward_combine_launch(const LpRendererArgs& a, int seg_blocks, hip
 
 // layer-looped bf16x3 MFMA family (1-4 layers per MLP, hidden 16 / 32 / 64): lp_renderer_loop.hip
 bool renderer_loop_supported(const LpRendererArgs& a, const char** why);
+bool renderer_loop_supported_forward(const LpRendererArgs& a, const char** why);  // ... without the two-block family's cap of 2 layers per MLP
 bool renderer_loop_fits(const LpRendererArgs& a);  // its weight images + tiles fit the 160 KB LDS
 int renderer_loop_segments(const LpRendererArgs& a);  // segments of the segment-parallel march (1 = none)
 int renderer_forward_loop(const LpRendererArgs& a, hipStream_t stream);
 int renderer_backward_loop(const LpRendererArgs& a, hipStream_t stream);
 int renderer_loop_dump_words(const LpRendererArgs& a);  // words per (ray, sample) of the ReLU dump
 int renderer_generic_dump_words(const LpRendererArgs& a);  // ... of the shape-generic backward (sites x ceil(widest site / 32) + 1)
+// forward of the deep two-block decoders (hidden 64 / 64 grid channels, 3-4 layers in an MLP; their backward is generic):
+// lp_renderer_loop_stream.hip
+bool renderer_deep_forward_supported(const LpRendererArgs& a);   // new ground of lp_renderer_forward_ws
+int renderer_deep_forward_family(const LpRendererArgs& a);       // 3 resident images, 4 streamed (only where supported)
+int64_t renderer_deep_forward_workspace(const LpRendererArgs& a);
+int renderer_forward_deep(const LpRendererArgs& a, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+const char* build_info_loop_stream();
 // per-translation-unit arithmetic reports for lp_build_info() (JSON fragments, static storage)
 const char* build_info_tuned_bwd();
 const char* build_info_tuned_bwd_aux();

@@ -35,25 +35,32 @@ LP_DEV void lds_barrier_l() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" :
 // staging
 // ---------------------------------------------------------------------------------------------------------------
 // (the staging loops stride by the launch's block size: the eight-wave forwards stage every element once, not twice)
-template <int NB>
-LP_DEV void loop_stage_layer(char* lds, float* sm, const float* P, const LoopLayer& L, int tid) {
+// block images of one layer, written at `base`: block (ib, ob) at base + (ib * ob_count + ob) * LOOP_BLK, limb p of W[k][m] at + p *
+// LOOP_ST + rm_off(k, m).  `base` is LDS (loop_stage_layer) or global memory (the pre-split images of the streamed forward,
+// lp_renderer_loop_stream.hip: the same bytes, copied into LDS as they are)
+LP_DEV void loop_write_images(char* base, const float* P, const LoopLayer& L, int tid) {
   const int in_blocks = (L.rows_in + 31) >> 5;
   for (int ib = 0; ib < in_blocks; ++ib) {
     for (int ob = 0; ob < L.ob; ++ob) {
-      char* blk = lds + L.img + (ib * L.ob + ob) * LOOP_BLK;
+      char* blk = base + (ib * L.ob + ob) * LOOP_BLK;
       for (int i = tid; i < 32 * 32; i += (int)blockDim.x) {
         const int k = i >> 5, m = i & 31;
         const int row = 32 * ib + k, col = 32 * ob + m;
         const float w = (row < L.rows_in && col < L.cols) ? P[L.w + (int64_t)row * L.ld + col] : 0.0f;
         unsigned short l1, l2, l3;
         split3_scalar(w, l1, l2, l3);
-        char* base = blk + rm_off(k, m);
-        *reinterpret_cast<unsigned short*>(base) = l1;
-        *reinterpret_cast<unsigned short*>(base + LOOP_ST) = l2;
-        *reinterpret_cast<unsigned short*>(base + 2 * LOOP_ST) = l3;
+        char* dst = blk + rm_off(k, m);
+        *reinterpret_cast<unsigned short*>(dst) = l1;
+        *reinterpret_cast<unsigned short*>(dst + LOOP_ST) = l2;
+        *reinterpret_cast<unsigned short*>(dst + 2 * LOOP_ST) = l3;
       }
     }
   }
+}
+// images = false: the bias only (a layer whose images are streamed through the ring of the streamed forward)
+template <int NB>
+LP_DEV void loop_stage_layer(char* lds, float* sm, const float* P, const LoopLayer& L, int tid, bool images = true) {
+  if (images) loop_write_images(lds + L.img, P, L, tid);
   for (int i = tid; i < 32 * NB; i += (int)blockDim.x) sm[L.bias + i] = (i < L.cols) ? P[L.b + i] : 0.0f;
 }
 

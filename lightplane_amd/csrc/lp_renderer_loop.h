@@ -62,14 +62,16 @@ struct LoopTile {
 };
 
 
+// n_img: the first n_img layers (order: trunk, opacity head, colour head) get their images staged, the others their bias only (the
+// streamed forward, lp_renderer_loop_stream.hip)
 template <int NB>
-LP_DEV void loop_stage(const LpRendererArgs& a, const LoopParams& lp, float* lds) {
+LP_DEV void loop_stage(const LpRendererArgs& a, const LoopParams& lp, float* lds, int n_img = 1 << 30) {
   const float* P = a.mlp_params;
   const int tid = threadIdx.x;
   char* b = reinterpret_cast<char*>(lds);
-  for (int l = 0; l < lp.n_t; ++l) loop_stage_layer<NB>(b, lds, P, lp.t[l], tid);
-  for (int l = 0; l < lp.n_o; ++l) loop_stage_layer<NB>(b, lds, P, lp.o[l], tid);
-  for (int l = 0; l < lp.n_c; ++l) loop_stage_layer<NB>(b, lds, P, lp.c[l], tid);
+  for (int l = 0; l < lp.n_t; ++l) loop_stage_layer<NB>(b, lds, P, lp.t[l], tid, l < n_img);
+  for (int l = 0; l < lp.n_o; ++l) loop_stage_layer<NB>(b, lds, P, lp.o[l], tid, lp.n_t + l < n_img);
+  for (int l = 0; l < lp.n_c; ++l) loop_stage_layer<NB>(b, lds, P, lp.c[l], tid, lp.n_t + lp.n_o + l < n_img);
   if (a.color_chn > 4) loop_stage_layer<NB>(b, lds, P, lp.co, tid);
   for (int i = tid; i < 32 * NB; i += (int)blockDim.x) {
     lds[lp.wo2 + i] = (i < lp.ho_w) ? P[lp.w_o2 + i] : 0.0f;
@@ -1031,6 +1033,9 @@ static int loop_bwd_table_deep(const LpRendererArgs& a, const LoopParams& p, int
   }
 #undef LP_LOOP_BWD
 }
+
+// host side shared with the streamed forward (lp_renderer_loop_stream.hip)
+LoopParams renderer_loop_params(const LpRendererArgs& a);
 
 int renderer_backward_loop_shallow(const LpRendererArgs& a, const LoopParams& p, unsigned nb, size_t lds, bool tri, hipStream_t stream);
 // DUMP twins (with -DLP_TEST_HOOKS; LP_EUNSUPPORTED without)

@@ -14,7 +14,8 @@ static int loop_nb(int H, int C = 16) { return (H <= 32 && C <= 32) ? 1 : 2; }
 // grid-list; heads of 1..4 layers; every hidden width equal to H in {16, 32} -- or, on the two-block instantiation (H = 64, or
 // C = 64 grid channels with any of the three widths): at most 2 trunk layers, heads of at most 2 layers, <= 4 colour channels, a
 // colour grid only with C <= 32; <= 256 beyond-far samples.
-bool renderer_loop_supported(const LpRendererArgs& a, const char** why) {
+// deep64: also the two-block shapes with more than 2 layers per MLP -- the FORWARD's ground (lp_renderer_loop_stream.hip)
+static bool loop_supported(const LpRendererArgs& a, const char** why, bool deep64) {
   *why = "";
   const int C = a.grid.channels;
   const bool tg = a.color_grid.n_grids > 0;
@@ -33,7 +34,7 @@ bool renderer_loop_supported(const LpRendererArgs& a, const char** why) {
   if (H == 0) H = C;  // two-grid decoder with single-layer heads: no hidden layer at all
   if (!same) { *why = "hidden widths differ between layers"; return false; }
   if (H != 16 && H != 32 && H != 64) { *why = "hidden width other than 16 / 32 / 64"; return false; }
-  if ((H == 64 || C == 64) && (a.trunk.n_layers > 2 || a.opacity.n_layers > 2 || a.color.n_layers > 2)) {
+  if (!deep64 && (H == 64 || C == 64) && (a.trunk.n_layers > 2 || a.opacity.n_layers > 2 || a.color.n_layers > 2)) {
     *why = "hidden width 64 / 64 grid channels with more than 2 layers per MLP";
     return false;
   }
@@ -45,6 +46,12 @@ bool renderer_loop_supported(const LpRendererArgs& a, const char** why) {
   if (a.march.num_samples_inf > LOOP_N_INF) { *why = "more than 256 beyond-far samples"; return false; }
   return true;
 }
+
+bool renderer_loop_supported(const LpRendererArgs& a, const char** why) { return loop_supported(a, why, false); }
+bool renderer_loop_supported_forward(const LpRendererArgs& a, const char** why) { return loop_supported(a, why, true); }
+
+static LoopParams loop_params(const LpRendererArgs& a);
+LoopParams renderer_loop_params(const LpRendererArgs& a) { return loop_params(a); }
 
 static LoopParams loop_params(const LpRendererArgs& a) {
   LoopParams p = {};

@@ -118,8 +118,18 @@ def _warn_if_generic(a, cfg: _RendererCfg) -> None:
         return
     if _lib.lib().lp_renderer_kernel_family(ctypes.byref(a)) == 0:
         _warned_shapes.add(key)
+        fwd = int(_lib.lib().lp_renderer_forward_family(ctypes.byref(a))) if config.deep_forward_mfma else 0
+        if fwd != 0:
+            warnings.warn(
+                "lightplane_amd: the BACKWARD of this decoder shape runs on the shape-generic Renderer kernels (10-100x slower); its "
+                f"forward runs kernel family {fwd} (layer-looped MFMA forward, "
+                f"{'streamed' if fwd == 4 else 'resident'} weight images). "
+                f"Got channels={cfg.channels}, trunk={cfg.dims_trunk}, opacity={cfg.dims_opacity}, "
+                f"color={cfg.dims_color}, color_chn={cfg.color_chn}, separate colour grid={cfg.color_descs is not None}.")
+            return
         warnings.warn(
-            "lightplane_amd: this decoder shape runs on the shape-generic Renderer kernels (10-100x slower). The "
+            "lightplane_amd: this decoder shape runs on the shape-generic Renderer kernels (10-100x slower), forward (kernel family 0) "
+            "and backward. The "
             "MFMA families cover grid channels 16/32, grid-lists below 2^31 rows, trunk 1-4 (0 with a separate colour grid) / "
             "opacity 1-4 / colour 1-4 layers with ONE hidden width of 16 or 32 and <= 32 colour channels, or up to 2/2/2 "
             "layers with hidden width 64 and / or 64 grid channels and <= 4 colour channels (a separate colour grid only with 16 / 32 "
@@ -154,7 +164,7 @@ def _shape_args(grid, decoder_params: DecoderParams, grid_sizes=None, color_grid
 _RENDER_KWARGS = frozenset((
     "num_samples", "gain", "mask_out_of_bounds_samples", "contract_coords", "disparity_at_inf", "inject_noise_sigma",
     "inject_noise_seed", "scaffold", "stop_transmittance", "regenerate_code", "triton_block_size", "triton_num_warps",
-    "allow_unsupported", "checkpointing", "use_naive_impl", "march_order"))
+    "allow_unsupported", "checkpointing", "use_naive_impl", "march_order", "rays_per_row"))
 
 
 def _check_render_kwargs(fn: str, kw) -> None:
@@ -179,6 +189,23 @@ def kernel_family(rays: Rays, grid, decoder_params: DecoderParams, grid_sizes=No
     a.march.num_samples_inf = int(num_samples_inf)
     a.arithmetic = int(config.arithmetic if arithmetic is None else arithmetic)
     return int(_lib.lib().lp_renderer_kernel_family(ctypes.byref(a)))
+
+
+def forward_kernel_family(rays: Rays, grid, decoder_params: DecoderParams, grid_sizes=None, color_grid=None,
+                          color_grid_sizes=None, num_samples_inf: int = 0, kernel: int = _lib.LP_KERNEL_AUTO,
+                          arithmetic: Optional[int] = None, **_unused) -> int:
+    """Kernel family of the FORWARD of these shapes with ``config.deep_forward_mfma`` on (``lp_renderer_forward_family``; needs no
+    GPU): what ``kernel_family`` says, except for decoders it turns down only for their depth at hidden width 64 / 64 grid channels
+    (3-4 layers in an MLP): 3 = layer-looped MFMA forward with resident weight images, 4 = with streamed weight images.  Their
+    backward runs the shape-generic kernels (``kernel_family`` stays 0).  Same arguments as ``kernel_family``."""
+    _check_render_kwargs("forward_kernel_family", _unused)
+    if int(kernel) == _lib.LP_KERNEL_GENERIC:
+        return 0
+    a = _shape_args(grid, decoder_params, grid_sizes, color_grid, color_grid_sizes)
+    a.march.num_samples_inf = int(num_samples_inf)
+    a.kernel = int(kernel)
+    a.arithmetic = int(config.arithmetic if arithmetic is None else arithmetic)
+    return int(_lib.lib().lp_renderer_forward_family(ctypes.byref(a)))
 
 
 def relu_dump_words(rays: Rays, grid, decoder_params: DecoderParams, grid_sizes=None, color_grid=None, color_grid_sizes=None,
@@ -293,7 +320,14 @@ class LightplaneFunction(torch.autograd.Function):
             seg_for_backward = seg
         _warn_if_generic(a, cfg)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().lp_renderer_forward(ctypes.byref(a), stream), "lp_renderer_forward")
+            if config.deep_forward_mfma:
+                # deep hidden-64 decoders: the layer-looped forward; streamed weight images pass through a workspace (a torch
+                # allocation: no host sync, graph-capturable; the allocator keeps it alive for the stream's queued work)
+                ws_bytes = int(_lib.lib().lp_renderer_forward_workspace_bytes(ctypes.byref(a)))
+                ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8) if ws_bytes > 0 else None
+                _lib.check(_lib.lib().lp_renderer_forward_ws(ctypes.byref(a), _lib.ptr(ws), ws_bytes, stream), "lp_renderer_forward_ws")
+            else:
+                _lib.check(_lib.lib().lp_renderer_forward(ctypes.byref(a), stream), "lp_renderer_forward")
         # O(N) state only: the final -log T (the reference saves the same, :558-573)
         ctx.save_for_backward(nlt, ckpt, seg_for_backward, mlp_params, encoding, directions, origins, grid_idx, near, far, scaffold,
                               bg_color, *grids, *color_grids)

@@ -2,6 +2,8 @@
 forward / forward+backward time, the family LP_KERNEL_AUTO picks, and time per multiply-accumulate of the decoder --
 the evidence for "a 4-layer MLP costs its FLOPs, not a fall-back" (layer-looped family, lp_renderer_loop.hip).
     python scripts/bench_shapes.py [renderer|splatter] ; LP_LOOP=1 python scripts/bench_shapes.py   (everything through the loop family)
+    SHAPESET=deep64 FWD_ONLY=1 NPIX=384 python scripts/bench_shapes.py   (forward only: the deep hidden-64 decoders on the shape-generic
+    forward; LIGHTPLANE_AMD_DEEP_FORWARD_MFMA=1 gives their layer-looped MFMA forward, config.deep_forward_mfma)
 """
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -87,6 +89,7 @@ elif what == "renderer":
         params = d.mlp_params.to(dev).requires_grad_(True)
         dec = lp.DecoderParams(params, d.n_hidden_trunk, d.n_hidden_opacity, d.n_hidden_color, 3)
         fam = lp.kernel_family(rays, grids, dec, color_grid=cgrids)
+        fwd_fam = lp.forward_kernel_family(rays, grids, dec, color_grid=cgrids) if lp.config.deep_forward_mfma else fam
         dims = [[int(v) for v in x] for x in (d.n_hidden_trunk, d.n_hidden_opacity, d.n_hidden_color)]
         mac = sum(a * b for x in dims for a, b in zip(x[:-1], x[1:]))
 
@@ -101,8 +104,15 @@ elif what == "renderer":
             o = lp.lightplane_renderer(rays, grids, dec, num_samples=S, gain=1.0, color_grid=cgrids)
             (o[0].sum() + o[1].sum() + o[2].sum()).backward()
 
+        if os.environ.get("FWD_ONLY"):  # forward-only column (inference): time and time per multiply-accumulate of the forward
+            tf = t(fwd, 20)
+            print(json.dumps({"layers": f"{nt}/{no}/{nc}", "hidden": H, "C": C, "grid": G, "colour_grid": sep, "rays": n * n, "S": S,
+                              "forward_family": fwd_fam, "fwd_ms": round(tf, 3), "MAC_per_sample": mac,
+                              "ps_per_MAC_fwd": round(tf * 1e9 / (n * n * S * mac), 4)}), flush=True)
+            continue
         tf, tb = t(fwd), t(fb)
         print(json.dumps({"layers": f"{nt}/{no}/{nc}", "hidden": H, "C": C, "grid": G, "colour_grid": sep, "family": fam,
+                          "forward_family": fwd_fam,
                           "fwd_ms": round(tf, 3), "fwd_bwd_ms": round(tb, 3), "Mrays_per_s_fwd_bwd": round(n * n / tb / 1e3, 3),
                           "MAC_per_sample": mac, "ps_per_MAC_fwd_bwd": round(tb * 1e9 / (n * n * S * mac * 4), 4)}), flush=True)
 else:
