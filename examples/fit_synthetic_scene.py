@@ -7,7 +7,10 @@ plane grids as parameters, optimised with Adam on random rays.  The role of the 
 examples/fit_single_scene.py training loop (:282-334) as a convergence check, on synthetic data because the
 GPU boxes have no datasets.
 
-    python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0]
+    python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0]
+
+``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
+planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -55,7 +58,7 @@ def random_rays(n, gen, dev):
                    near=near.to(dev), far=far.to(dev), encoding=None)
 
 
-def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False):
+def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -65,7 +68,7 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     shapes = [(1, 1, res, res, chn), (1, res, 1, res, chn), (1, res, res, 1, chn)]
     grids = torch.nn.ParameterList([torch.nn.Parameter(0.1 * torch.randn(*s, generator=gen).to(dev)) for s in shapes])
     opt = torch.optim.Adam([{"params": grids.parameters(), "lr": 3e-2}, {"params": renderer.parameters(), "lr": 3e-3}])
-    losses = []
+    losses, tvs = [], []
     for it in range(steps):
         rays = random_rays(n_rays, gen, dev)
         with torch.no_grad():
@@ -74,6 +77,8 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
+        if tv_weight > 0.0:
+            tvs.append(lp.add_grid_tv_grad_(list(grids), [g.grad for g in grids], weight=tv_weight))
         opt.step()
         losses.append(float(loss.detach()))
         if verbose and (it % 50 == 0 or it == steps - 1):
@@ -83,8 +88,12 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         _, _, rgb = renderer(rays, list(grids))
         mse = float(((rgb - tgt_rgb) ** 2).mean())
-    return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": -10.0 * math.log10(mse),
-            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
+    out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": -10.0 * math.log10(mse),
+           "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
+    if tv_weight > 0.0:
+        out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
+                   grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
+    return out
 
 
 if __name__ == "__main__":
@@ -92,5 +101,6 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--rays", type=int, default=8192)
     ap.add_argument("--stop-transmittance", type=float, default=0.0)
+    ap.add_argument("--tv-weight", type=float, default=0.0)
     a = ap.parse_args()
-    print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True)))
+    print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight)))

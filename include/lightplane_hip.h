@@ -76,7 +76,9 @@ extern "C" {
                                   families take grid-lists of any byte size below 2^31 rows (were: below 4 GB); later, without a
                                   version change (additive: no struct or behaviour change, every existing entry point as before):
                                   the MLP-Splatter test hooks lp_mlp_splatter_backward_relu_dump() and
-                                  lp_mlp_splatter_relu_dump_words(), the launch-shape query lp_mlp_splatter_launch_shape() */
+                                  lp_mlp_splatter_relu_dump_words(), the launch-shape query lp_mlp_splatter_launch_shape(); the total-variation
+                                  regulariser of a grid-list, lp_grid_tv_workspace_bytes() / _forward() / _backward() / _fused()
+                                  (lp_build_info() then has a "grid_tv" entry) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -362,6 +364,43 @@ int lp_splatter_backward(const LpSplatterArgs* args, void* stream);
 /* <- LightplaneRenderer._get_ray_embedding (lightplane/renderer_module.py:578-601) and its autograd backward */
 int lp_ray_embedding_forward(const LpRayEmbedArgs* args, void* stream);
 int lp_ray_embedding_backward(const LpRayEmbedArgs* args, void* stream);
+
+/* Total-variation regulariser of a grid-list (an extension: the reference has no such operator; lp_grid_tv.hip).
+ * For one grid x [B, D, H, W, C] and p in {1, 2}, phi_1(d) = |d|, phi_2(d) = d * d:
+ *   T_a    = sum of phi_p(x[.., i + 1, ..] - x[.., i, ..]) over all adjacent pairs along the spatial axis a, all B and all C;
+ *            N_a = the number of those pairs
+ *   loss_g = sum over the axes a in {D, H, W} with extent > 1 of T_a / N_a      (a plane [B, 1, H, W, C] gets its 2-D TV; a
+ *            grid with no axis > 1 has loss 0)
+ *   loss   = sum_g grid_weights[g] * loss_g
+ * The derivative of phi_1 at a zero difference is 0.  There are no pairs across batch entries or across list entries.
+ * `grid`: a grid-list as everywhere in this header (flat tensor + row offsets, or per-grid base pointers), with two relaxations:
+ * a grid may have ANY positive extents (a line [B, 1, 1, W] and a single cell are valid), and the grids need not share a batch
+ * size.  1 .. LP_MAX_WIDTH channels (rows are read 16 bytes at a time where C % 4 == 0 and every pointer is 16-byte aligned, float
+ * by float otherwise); every tensor below 2^31 rows, element offsets are 64-bit.
+ * `grid_weights`: HOST array of n_weights == grid->n_grids floats, or NULL with n_weights == 0 (every weight 1).
+ * No atomics: loss and gradient are bit-reproducible.  No host synchronisation and no allocation: graph-capturable.
+ *   lp_grid_tv_workspace_bytes: bytes of device workspace the loss needs for this list (one fp64 partial per workgroup of the sweep;
+ *     shapes only, no device; never decreases when an extent grows), or a negative LP_E* code for a malformed list.
+ *   lp_grid_tv_forward:  *loss (device, fp32) = loss.  `workspace`: device memory, 8-byte aligned, >= that many bytes, free to reuse
+ *     once the call's work on `stream` is done.
+ *   lp_grid_tv_backward: gradient = scale * (*grad_loss) * d loss / d grid, computed per element from its six neighbours and written
+ *     (accumulate == 0) or added to what the buffer holds (accumulate != 0).  grad_loss: DEVICE scalar (the upstream gradient; NULL =
+ *     1).  Where the gradient goes: `grad_list` -- a HOST array of n_grad_list == n_grids device pointers, entry g shaped like the
+ *     tensor that holds grid g (same row_offset) -- and / or `grad`, the buffer that mirrors the flat tensor grid->data, which serves
+ *     every grid without an own LpGrid.data pointer whose list entry is NULL or absent (grad_list == NULL needs n_grad_list == 0).
+ *   lp_grid_tv_fused:    both in ONE sweep over the grid: *loss = loss (not scaled), gradient buffers += scale * (*grad_loss) * d loss /
+ *     d grid -- for a training step on a grid too large for a second sweep to be free.
+ * Before anything touches the device: LP_EINVAL for p outside {1, 2}, a weight count != n_grids, a short or misaligned workspace, a
+ * gradient list that does not match the grid list; LP_ENULL for a NULL list / loss / workspace / missing data or gradient pointers;
+ * LP_EUNSUPPORTED for a channel count outside [1, LP_MAX_WIDTH] or a tensor of 2^31 rows or more. */
+int64_t lp_grid_tv_workspace_bytes(const LpGridList* grid);
+int lp_grid_tv_forward(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, float* loss, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int lp_grid_tv_backward(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, const float* grad_loss,
+                        float scale, float* grad, float* const* grad_list, int32_t n_grad_list, int32_t accumulate, void* stream);
+int lp_grid_tv_fused(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, float* loss, void* workspace,
+                     int64_t workspace_bytes, const float* grad_loss, float scale, float* grad, float* const* grad_list,
+                     int32_t n_grad_list, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

@@ -114,6 +114,7 @@ EXPORTS = (
     "lp_renderer_backward_segments", "lp_renderer_backward_relu_dump", "lp_renderer_relu_dump_words", "lp_build_info",
     "lp_ray_embedding_forward", "lp_ray_embedding_backward",
     "lp_mlp_splatter_backward_relu_dump", "lp_mlp_splatter_relu_dump_words", "lp_mlp_splatter_launch_shape",
+    "lp_grid_tv_forward", "lp_grid_tv_backward", "lp_grid_tv_fused",  # (+ lp_grid_tv_workspace_bytes, which returns int64_t)
 )
 
 
@@ -175,6 +176,17 @@ def lib() -> C.CDLL:
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(LpRayEmbedArgs), C.c_void_p]
+    # total-variation regulariser (grid-list, HOST weight array, count, p, ...)
+    _tv = [C.POINTER(LpGridList), C.c_void_p, C.c_int32, C.c_int32]
+    _tv_grad = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]  # grad_loss, scale, grad, grad_list (HOST array), n_grad_list
+    L.lp_grid_tv_workspace_bytes.restype = C.c_int64
+    L.lp_grid_tv_workspace_bytes.argtypes = [C.POINTER(LpGridList)]
+    L.lp_grid_tv_forward.restype = C.c_int
+    L.lp_grid_tv_forward.argtypes = _tv + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lp_grid_tv_backward.restype = C.c_int
+    L.lp_grid_tv_backward.argtypes = _tv + _tv_grad + [C.c_int32, C.c_void_p]
+    L.lp_grid_tv_fused.restype = C.c_int
+    L.lp_grid_tv_fused.argtypes = _tv + [C.c_void_p, C.c_void_p, C.c_int64] + _tv_grad + [C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in enumerate((LpGrid, LpGridList, LpRays, LpMarch, LpMlp, LpRendererArgs, LpSplatterArgs,

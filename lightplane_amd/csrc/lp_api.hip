@@ -218,6 +218,69 @@ static int check_splatter(const LpSplatterArgs& a, bool backward) {
   return LP_OK;
 }
 
+// Grid-list of the total-variation regulariser (lp_grid_tv_*): any [B, D, H, W] with positive extents -- a line or a single cell is
+// a valid (if dull) grid here, unlike for the samplers -- and grids of one list may differ in batch size.
+static int check_tv_grid_list(const LpGridList* glp) {
+  if (!glp) return set_error(LP_ENULL, "grid_tv: the grid-list is NULL");
+  const LpGridList& gl = *glp;
+  if (gl.n_grids < 1 || gl.n_grids > LP_MAX_GRIDS)
+    return set_error(LP_EINVAL, "grid_tv: n_grids %d outside [1, %d]", gl.n_grids, LP_MAX_GRIDS);
+  if (gl.channels < 1 || gl.channels > LP_MAX_WIDTH)
+    return set_error(LP_EUNSUPPORTED, "grid_tv: %d channels outside [1, %d]", gl.channels, LP_MAX_WIDTH);
+  for (int g = 0; g < gl.n_grids; ++g) {
+    const LpGrid& d = gl.grids[g];
+    if (d.B < 1 || d.D < 1 || d.H < 1 || d.W < 1)
+      return set_error(LP_EINVAL, "grid_tv: grid[%d]: non-positive extent [%d,%d,%d,%d]", g, d.B, d.D, d.H, d.W);
+    if (d.row_offset < 0) return set_error(LP_EINVAL, "grid_tv: grid[%d]: negative row_offset", g);
+    const int64_t rows = (int64_t)d.B * d.D * d.H * d.W;
+    if (d.row_offset + rows >= ((int64_t)1 << 31))
+      return set_error(LP_EUNSUPPORTED, "grid_tv: grid[%d] ends at row %lld: at most 2^31 - 1 rows per tensor", g,
+                       (long long)(d.row_offset + rows));
+    if (!d.data && d.row_offset + rows > gl.n_rows)
+      return set_error(LP_EINVAL, "grid_tv: grid[%d]: rows [%lld, %lld) outside the flat tensor (%lld rows)", g,
+                       (long long)d.row_offset, (long long)(d.row_offset + rows), (long long)gl.n_rows);
+  }
+  return LP_OK;
+}
+
+// everything lp_grid_tv_forward / _backward / _fused share; fills the normalised list and the per-grid gradient pointers
+static int check_grid_tv(const char* what, const LpGridList* grid, const float* grid_weights, int n_weights, int p, bool want_loss,
+                         float* loss, void* workspace, int64_t workspace_bytes, bool want_grad, float* grad, float* const* grad_list,
+                         int n_grad_list, LpGridList& gl, float** grads) {
+  int rc;
+  if ((rc = check_tv_grid_list(grid))) return rc;
+  if (p != 1 && p != 2) return set_error(LP_EINVAL, "%s: p = %d, has to be 1 (|d|) or 2 (d^2)", what, p);
+  if (grid_weights ? n_weights != grid->n_grids : n_weights != 0)
+    return set_error(LP_EINVAL, "%s: %d grid weights for %d grids (NULL / 0 = all 1)", what, n_weights, grid->n_grids);
+  gl = *grid;
+  if (!normalize_grid_list(gl)) return set_error(LP_ENULL, "%s: a grid has neither its own data pointer nor a flat tensor", what);
+  if (want_loss) {
+    if (!loss) return set_error(LP_ENULL, "%s: loss is NULL", what);
+    if (!workspace) return set_error(LP_ENULL, "%s: workspace is NULL", what);
+    const int64_t need = grid_tv_workspace_bytes(gl);
+    if (workspace_bytes < need)
+      return set_error(LP_EINVAL, "%s: workspace of %lld bytes, lp_grid_tv_workspace_bytes() asks for %lld", what,
+                       (long long)workspace_bytes, (long long)need);
+    if (((uintptr_t)workspace & 7) != 0) return set_error(LP_EINVAL, "%s: workspace has to be 8-byte aligned", what);
+  }
+  if (want_grad) {
+    if (grad_list ? (n_grad_list != gl.n_grids) : (n_grad_list != 0))
+      return set_error(LP_EINVAL, "%s: gradient list of %d entries for %d grids", what, n_grad_list, gl.n_grids);
+    if (!grad && !grad_list) return set_error(LP_ENULL, "%s: neither a flat gradient tensor nor a gradient list", what);
+    for (int g = 0; g < gl.n_grids; ++g) {
+      grads[g] = grad_list ? grad_list[g] : nullptr;
+      // as for the Renderer's grad_grid_list: a grid without its own entry takes the flat buffer -- which mirrors the flat TENSOR, so
+      // only a grid that lives there can use it
+      if (!grads[g] && !grid->grids[g].data) grads[g] = grad;
+      if (!grads[g])
+        return set_error(LP_EINVAL, "%s: the gradient list does not match the grid list: no gradient buffer for grid %d%s", what, g,
+                         grid->grids[g].data ? " (it has its own data pointer and needs its own gradient entry)" : "");
+      if (grads[g] == gl.grids[g].data) return set_error(LP_EINVAL, "%s: the gradient of grid %d aliases the grid", what, g);
+    }
+  }
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -233,10 +296,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -550,6 +613,42 @@ int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, i
   if (n < 0) return set_error(LP_EINVAL, "n < 0");
   if (n > 0 && (!x1 || !x2 || !out)) return set_error(LP_ENULL, "hash_randn: NULL buffer");
   return hash_randn_launch(x1, x2, out, n, seed, (hipStream_t)stream);
+}
+
+int64_t lp_grid_tv_workspace_bytes(const LpGridList* grid) {
+  const int rc = check_tv_grid_list(grid);
+  if (rc) return rc;
+  return grid_tv_workspace_bytes(*grid);
+}
+
+int lp_grid_tv_forward(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, float* loss, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  LpGridList gl;
+  const int rc = check_grid_tv("lp_grid_tv_forward", grid, grid_weights, n_weights, p, true, loss, workspace, workspace_bytes, false,
+                               nullptr, nullptr, 0, gl, nullptr);
+  if (rc) return rc;
+  return grid_tv_launch(gl, grid_weights, p, loss, (double*)workspace, nullptr, 1.0f, nullptr, false, (hipStream_t)stream);
+}
+
+int lp_grid_tv_backward(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, const float* grad_loss,
+                        float scale, float* grad, float* const* grad_list, int32_t n_grad_list, int32_t accumulate, void* stream) {
+  LpGridList gl;
+  float* grads[LP_MAX_GRIDS];
+  const int rc = check_grid_tv("lp_grid_tv_backward", grid, grid_weights, n_weights, p, false, nullptr, nullptr, 0, true, grad,
+                               grad_list, n_grad_list, gl, grads);
+  if (rc) return rc;
+  return grid_tv_launch(gl, grid_weights, p, nullptr, nullptr, grad_loss, scale, grads, accumulate != 0, (hipStream_t)stream);
+}
+
+int lp_grid_tv_fused(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, float* loss, void* workspace,
+                     int64_t workspace_bytes, const float* grad_loss, float scale, float* grad, float* const* grad_list,
+                     int32_t n_grad_list, void* stream) {
+  LpGridList gl;
+  float* grads[LP_MAX_GRIDS];
+  const int rc = check_grid_tv("lp_grid_tv_fused", grid, grid_weights, n_weights, p, true, loss, workspace, workspace_bytes, true, grad,
+                               grad_list, n_grad_list, gl, grads);
+  if (rc) return rc;
+  return grid_tv_launch(gl, grid_weights, p, loss, (double*)workspace, grad_loss, scale, grads, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

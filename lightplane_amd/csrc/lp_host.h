@@ -108,6 +108,12 @@ int splatter_normalize_launch(float* feature, const float* weight, int64_t n_row
 // ray-direction embedding of the module front-end: lp_ray_embedding.hip
 int ray_embedding_forward_launch(const LpRayEmbedArgs& a, hipStream_t stream);
 int ray_embedding_backward_launch(const LpRayEmbedArgs& a, hipStream_t stream);
+// total-variation regulariser of a grid-list: lp_grid_tv.hip (loss != NULL: value into *loss through `workspace`; grads != NULL: gradient,
+// overwritten or accumulated; both: the fused sweep)
+int64_t grid_tv_workspace_bytes(const LpGridList& gl);
+int grid_tv_launch(const LpGridList& gl, const float* weights, int p, float* loss, double* workspace, const float* grad_loss, float scale,
+                   float* const* grads, bool accumulate, hipStream_t stream);
+const char* build_info_grid_tv();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 
