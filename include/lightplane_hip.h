@@ -26,6 +26,15 @@
  *   - the library never allocates device memory and keeps no state besides a
  *     thread-local error string; the caller owns every buffer.
  *   - all tensors are fp32, contiguous, resident on the device of `stream`.
+ *   - every non-NULL device pointer of LpRendererArgs, LpSplatterArgs and LpRayEmbedArgs (per-grid
+ *     LpGrid.data and the gradient lists included) and `feature` / `weight` of
+ *     lp_splatter_normalize is 16-byte aligned: the kernels read and write caller memory
+ *     16 and 8 bytes at a time.  Checked on the host for every pointer, whatever n_rays
+ *     is, before anything touches the device: LP_EINVAL, the message names the field.
+ *     Row offsets inside a flat grid tensor are not pointers and carry no such rule.
+ *     (hipMalloc and every framework allocator return at least 256-byte alignment; what
+ *     needs care is a view at an element offset into a larger buffer: copy it.)  The
+ *     lp_grid_tv_* entry points take any 4-byte-aligned grid (scalar path when under-aligned).
  *   - accumulation targets (grad_*, splat feature/weight grids) MUST be zeroed by
  *     the caller: kernels accumulate with atomics (reference does the same:
  *     lightplane_renderer.py:470-476, 642-651; lightplane_splatter.py:404-410).
@@ -78,7 +87,11 @@ extern "C" {
                                   the MLP-Splatter test hooks lp_mlp_splatter_backward_relu_dump() and
                                   lp_mlp_splatter_relu_dump_words(), the launch-shape query lp_mlp_splatter_launch_shape(); the total-variation
                                   regulariser of a grid-list, lp_grid_tv_workspace_bytes() / _forward() / _backward() / _fused()
-                                  (lp_build_info() then has a "grid_tv" entry) */
+                                  (lp_build_info() then has a "grid_tv" entry)
+                                  later still, again without a version change (no struct change; every call whose pointers come from an
+                                  allocator answers as before): a device pointer of LpRendererArgs / LpSplatterArgs / LpRayEmbedArgs or
+                                  of lp_splatter_normalize() that is not 16-byte aligned is refused with LP_EINVAL (Conventions above;
+                                  the kernels always assumed it, nothing checked it) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */

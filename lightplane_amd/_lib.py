@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from typing import Optional, Sequence
 
 import torch
@@ -239,6 +240,31 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
         return None
     assert t.is_contiguous(), "tensors handed to the HIP library must be contiguous"
     return t.data_ptr()
+
+
+_grid_clone_warned = False
+
+
+def aligned(t: Optional[torch.Tensor], grid: bool = False) -> Optional[torch.Tensor]:
+    """``t`` itself when its base is 16-byte aligned -- every fresh allocation is -- and otherwise a fresh contiguous clone.  Every
+    device pointer of the C ABI has to be 16-byte aligned (include/lightplane_hip.h: the kernels move caller memory as float4 /
+    float2, and the entry points refuse anything else); ``x.contiguous()`` does not move a view that is already dense, so
+    ``buf[1:].view(shape)``, a parameter carved out of a flat parameter vector or ``rays.encoding[1:]`` would reach them at a 4-byte
+    aligned base.  Applied after ``.contiguous()`` wherever a tensor's pointer goes to the library; inside the autograd functions, so
+    that autograd still sees the caller's view.  ``grid=True``: the clone of a grid warns once per process -- for a multi-GB grid it is
+    a cost the caller should hear about."""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    if grid:
+        global _grid_clone_warned
+        if not _grid_clone_warned:
+            _grid_clone_warned = True
+            warnings.warn(
+                f"lightplane_amd: a grid tensor of shape {tuple(t.shape)} starts at an address that is not 16-byte aligned (a view at an "
+                "element offset into a larger buffer?) and is copied to an aligned buffer on every call (the copy stays allocated until the "
+                "backward has run); allocate the grid on its own, or "
+                "at a multiple of 4 floats into the buffer, to avoid the copy.  (Warned once per process.)", stacklevel=2)
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 def check_tensors(device: torch.device, float32: dict, any_dtype: Optional[dict] = None) -> None:

@@ -99,8 +99,47 @@ static int normalize_grad_list(const char* name, float** list, float* flat, int 
   return LP_OK;
 }
 
+// Every non-NULL device pointer of an argument block is 16-byte aligned (lightplane_hip.h, Conventions): the kernels read and write
+// caller memory as float4 / float2 and an under-aligned vector access is undefined.  One rule for every pointer, whatever n_rays is and
+// whether today's kernels vectorise that field or not -- it cannot go stale when a kernel gains a vector access.  Host arithmetic only:
+// runs before anything touches the device.  The message begins with the field as the header spells it.
+static int check_aligned(const char* field, const void* p) {
+  if (((uintptr_t)p & 15) == 0) return LP_OK;
+  return set_error(LP_EINVAL, "%s = %p has to be 16-byte aligned (every device pointer of the ABI is)", field, p);
+}
+#define LP_ALIGNED(obj, field)                                        \
+  do {                                                                \
+    if (int rc_ = check_aligned(#field, (obj).field)) return rc_;     \
+  } while (0)
+
+// (row offsets inside the flat tensor are not pointers: a C % 4 != 0 list keeps the kernels' scalar path)
+static int check_grid_list_aligned(const char* name, const LpGridList& gl) {
+  char field[64];
+  snprintf(field, sizeof(field), "%s.data", name);
+  if (int rc = check_aligned(field, gl.data)) return rc;
+  for (int g = 0; g < LP_MAX_GRIDS; ++g) {
+    snprintf(field, sizeof(field), "%s.grids[%d].data", name, g);
+    if (int rc = check_aligned(field, gl.grids[g].data)) return rc;
+  }
+  return LP_OK;
+}
+
+static int check_ptr_list_aligned(const char* name, float* const* list) {
+  char field[64];
+  for (int g = 0; g < LP_MAX_GRIDS; ++g) {
+    snprintf(field, sizeof(field), "%s[%d]", name, g);
+    if (int rc = check_aligned(field, list[g])) return rc;
+  }
+  return LP_OK;
+}
+
 static int check_rays(const LpRays& r, bool need_encoding) {
   if (r.n_rays < 0) return set_error(LP_EINVAL, "n_rays %lld < 0", (long long)r.n_rays);
+  const struct { const char* field; const void* p; } ptrs[] = {
+      {"rays.directions", r.directions}, {"rays.origins", r.origins}, {"rays.grid_idx", r.grid_idx},
+      {"rays.near_t", r.near_t},         {"rays.far_t", r.far_t},     {"rays.encoding", r.encoding}};
+  for (const auto& f : ptrs)
+    if (int rc = check_aligned(f.field, f.p)) return rc;
   if (r.n_rays == 0) return LP_OK;
   if (!r.directions || !r.origins || !r.grid_idx || !r.near_t || !r.far_t)
     return set_error(LP_ENULL, "rays: directions/origins/grid_idx/near/far must be non-NULL");
@@ -120,6 +159,28 @@ static int check_march(const LpMarch& m) {
 static int check_renderer(const LpRendererArgs& a, bool backward) {
   int rc;
   if ((rc = check_rays(a.rays, true))) return rc;
+  if ((rc = check_grid_list_aligned("grid", a.grid))) return rc;
+  if ((rc = check_grid_list_aligned("color_grid", a.color_grid))) return rc;
+  LP_ALIGNED(a, scaffold);
+  LP_ALIGNED(a, scaffold_shape.data);
+  LP_ALIGNED(a, mlp_params);
+  LP_ALIGNED(a, ray_length);
+  LP_ALIGNED(a, neg_log_t);
+  LP_ALIGNED(a, feature);
+  LP_ALIGNED(a, neg_log_t_ckpt);
+  LP_ALIGNED(a, grad_ray_length);
+  LP_ALIGNED(a, grad_neg_log_t);
+  LP_ALIGNED(a, grad_feature);
+  LP_ALIGNED(a, grad_grid);
+  LP_ALIGNED(a, grad_color_grid);
+  LP_ALIGNED(a, grad_mlp_params);
+  LP_ALIGNED(a, grad_encoding);
+  if ((rc = check_ptr_list_aligned("grad_grid_list", a.grad_grid_list))) return rc;
+  if ((rc = check_ptr_list_aligned("grad_color_grid_list", a.grad_color_grid_list))) return rc;
+  LP_ALIGNED(a, bg_color);
+  LP_ALIGNED(a, alpha);
+  LP_ALIGNED(a, grad_alpha);
+  LP_ALIGNED(a, seg_prefix);
   if ((rc = check_march(a.march))) return rc;
   if ((rc = check_grid_list("grid", a.grid, true))) return rc;
   if ((rc = check_grid_list("color_grid", a.color_grid, false))) return rc;
@@ -184,6 +245,17 @@ static int check_splatter(const LpSplatterArgs& a, bool backward) {
   if (a.march_order != LP_MARCH_RAYS_PER_WAVE && a.march_order != LP_MARCH_SAMPLES_PER_WAVE)
     return set_error(LP_EINVAL, "march_order %d is neither LP_MARCH_RAYS_PER_WAVE nor LP_MARCH_SAMPLES_PER_WAVE", a.march_order);
   if ((rc = check_rays(a.rays, true))) return rc;
+  if ((rc = check_grid_list_aligned("out", a.out))) return rc;
+  if ((rc = check_grid_list_aligned("input_grid", a.input_grid))) return rc;
+  LP_ALIGNED(a, out_feature);
+  LP_ALIGNED(a, out_weight);
+  LP_ALIGNED(a, mlp_params);
+  LP_ALIGNED(a, grad_out);
+  LP_ALIGNED(a, weight);
+  LP_ALIGNED(a, grad_encoding);
+  LP_ALIGNED(a, grad_input_grid);
+  LP_ALIGNED(a, grad_mlp_params);
+  if ((rc = check_ptr_list_aligned("grad_input_grid_list", a.grad_input_grid_list))) return rc;
   if ((rc = check_march(a.march))) return rc;
   if ((rc = check_grid_list("out", a.out, true))) return rc;
   const bool use_mlp = a.mlp.n_layers > 0;
@@ -518,6 +590,8 @@ int lp_splatter_forward(const LpSplatterArgs* args_, void* stream) {
 
 int lp_splatter_normalize(float* feature, const float* weight, int64_t n_rows, int32_t channels, void* stream) {
   if (n_rows < 0 || channels < 1) return set_error(LP_EINVAL, "normalize: bad shape [%lld, %d]", (long long)n_rows, channels);
+  int rc;
+  if ((rc = check_aligned("feature", feature)) || (rc = check_aligned("weight", weight))) return rc;
   if (n_rows > 0 && (!feature || !weight)) return set_error(LP_ENULL, "normalize: NULL buffer");
   return splatter_normalize_launch(feature, weight, n_rows, channels, (hipStream_t)stream);
 }
@@ -587,6 +661,13 @@ static int check_ray_embed(const LpRayEmbedArgs& a, bool backward) {
   if (a.n_rays < 0) return set_error(LP_EINVAL, "n_rays %lld < 0", (long long)a.n_rays);
   if (a.n_harmonics < 0 || a.n_harmonics > 10) return set_error(LP_EUNSUPPORTED, "n_harmonics %d outside [0, 10]", a.n_harmonics);
   if (a.out_dim < 1 || a.out_dim > LP_MAX_WIDTH) return set_error(LP_EUNSUPPORTED, "out_dim %d outside [1, %d]", a.out_dim, LP_MAX_WIDTH);
+  LP_ALIGNED(a, directions);
+  LP_ALIGNED(a, weight);
+  LP_ALIGNED(a, bias);
+  LP_ALIGNED(a, out);
+  LP_ALIGNED(a, grad_out);
+  LP_ALIGNED(a, grad_weight);
+  LP_ALIGNED(a, grad_bias);
   if (a.n_rays == 0) return LP_OK;
   if (!a.directions) return set_error(LP_ENULL, "directions is NULL");
   if (!backward && (!a.weight || !a.bias || !a.out)) return set_error(LP_ENULL, "weight / bias / out must be non-NULL");

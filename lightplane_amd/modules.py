@@ -50,7 +50,7 @@ class _RayEmbeddingFunction(torch.autograd.Function):
     def forward(ctx, directions, weight, bias, n_harmonics: int):
         dev = directions.device
         stream = _lib.current_stream(dev)
-        directions, weight, bias = directions.contiguous(), weight.contiguous(), bias.contiguous()
+        directions, weight, bias = (_lib.aligned(t.contiguous()) for t in (directions, weight, bias))
         _lib.check_tensors(dev, {"rays.directions": directions, "harmonic_ray_embedding_linear.weight": weight,
                                  "harmonic_ray_embedding_linear.bias": bias})
         n, e = directions.shape[0], weight.shape[0]
@@ -73,7 +73,7 @@ class _RayEmbeddingFunction(torch.autograd.Function):
             return None, None, None, None
         dev = directions.device
         stream = _lib.current_stream(dev)
-        grad_out = grad_out.contiguous()
+        grad_out = _lib.aligned(grad_out.contiguous())
         gw = torch.zeros_like(weight) if need_w else None
         gb = torch.zeros(weight.shape[0], device=dev, dtype=torch.float32) if need_b else None
         a = _lib.LpRayEmbedArgs()

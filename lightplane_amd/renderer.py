@@ -283,11 +283,13 @@ class LightplaneFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg: _RendererCfg, mlp_params, encoding, directions, origins, grid_idx, near, far, scaffold,
                 bg_color, *grid_tensors):
-        grids = tuple(g.contiguous() for g in grid_tensors[: cfg.n_grid_tensors])
-        color_grids = tuple(g.contiguous() for g in grid_tensors[cfg.n_grid_tensors:])
+        # (_lib.aligned: a dense view at an element offset into a larger buffer is copied to a 16-byte aligned base -- here, so that
+        # autograd routes the gradient through the caller's view)
+        grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[: cfg.n_grid_tensors])
+        color_grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[cfg.n_grid_tensors:])
         dev = grids[0].device
         stream = _lib.current_stream(dev)
-        mlp_params, encoding = mlp_params.contiguous(), encoding.contiguous()
+        mlp_params, encoding = _lib.aligned(mlp_params.contiguous()), _lib.aligned(encoding.contiguous())
         n = directions.shape[0]
         ray_length = torch.empty(n, device=dev, dtype=torch.float32)
         nlt = torch.empty(n, device=dev, dtype=torch.float32)
@@ -371,11 +373,11 @@ class LightplaneFunction(torch.autograd.Function):
             a.grid.data = _lib.ptr(grids[0])
             if color_grids:
                 a.color_grid.data = _lib.ptr(color_grids[0])
-        g_len = None if g_len is None else g_len.contiguous()
-        g_nlt = None if g_nlt is None else g_nlt.contiguous()
-        g_feat = None if g_feat is None else g_feat.contiguous()
+        g_len = None if g_len is None else _lib.aligned(g_len.contiguous())
+        g_nlt = None if g_nlt is None else _lib.aligned(g_nlt.contiguous())
+        g_feat = None if g_feat is None else _lib.aligned(g_feat.contiguous())
         a.grad_ray_length, a.grad_neg_log_t, a.grad_feature = _lib.ptr(g_len), _lib.ptr(g_nlt), _lib.ptr(g_feat)
-        g_alpha = g_alpha.contiguous() if (cfg.alpha_mode and g_alpha is not None) else None
+        g_alpha = _lib.aligned(g_alpha.contiguous()) if (cfg.alpha_mode and g_alpha is not None) else None
         a.grad_alpha = _lib.ptr(g_alpha)
         # the kernels scatter into every grid of a list or into none: allocate all buffers if any grid needs one
         grad_grids = [torch.zeros_like(g) for g in grids] if any(need_g) else None
@@ -623,17 +625,17 @@ def _render(rays: Rays, grid, decoder_params: DecoderParams, num_samples, gain, 
         inject_noise_seed = 0
 
     B = descs[0].B
-    grid_idx = rays.grid_idx.to(torch.int32).contiguous()
+    grid_idx = _lib.aligned(rays.grid_idx.to(torch.int32).contiguous())
     march, row_length = check_inputs_and_plan(rays, grid_idx, B, march_order, rays_per_row)
 
     scaffold_shape = None
     if scaffold is not None:
         assert scaffold.ndim == 4 and scaffold.shape[0] == B, "scaffold has to be [B, D, H, W]"
         scaffold_shape = tuple(int(v) for v in scaffold.shape)
-        scaffold = scaffold.to(torch.float32).contiguous()
+        scaffold = _lib.aligned(scaffold.to(torch.float32).contiguous())
     if bg_color is not None:
         assert bg_color.ndim == 1 and bg_color.numel() == int(decoder_params.color_chn)
-        bg_color = bg_color.contiguous()
+        bg_color = _lib.aligned(bg_color.contiguous())
 
     cfg = _RendererCfg(
         descs=descs, channels=channels, n_rows=n_rows, color_descs=color_descs, color_n_rows=color_n_rows,
@@ -647,8 +649,8 @@ def _render(rays: Rays, grid, decoder_params: DecoderParams, num_samples, gain, 
         arithmetic=int(config.arithmetic if arithmetic is None else arithmetic), march_order=int(march), row_length=int(row_length),
     )
     return LightplaneFunction.apply(
-        cfg, mlp_params, rays.encoding, rays.directions.contiguous(), rays.origins.contiguous(), grid_idx,
-        rays.near.contiguous(), rays.far.contiguous(), scaffold, bg_color, *grid_tensors, *color_tensors)
+        cfg, mlp_params, rays.encoding, _lib.aligned(rays.directions.contiguous()), _lib.aligned(rays.origins.contiguous()), grid_idx,
+        _lib.aligned(rays.near.contiguous()), _lib.aligned(rays.far.contiguous()), scaffold, bg_color, *grid_tensors, *color_tensors)
 
 
 def renderer_corner_rows(rays: Rays, grid_sizes, num_samples: int, num_samples_inf: int = 0,
@@ -662,9 +664,9 @@ def renderer_corner_rows(rays: Rays, grid_sizes, num_samples: int, num_samples_i
     s_tot = num_samples + num_samples_inf
     out = torch.empty(rays.n_rays, s_tot, k_tot, dtype=torch.int64, device=dev)
     a = _lib.LpRendererArgs()
-    a.rays = _lib.make_rays(rays.directions.contiguous(), rays.origins.contiguous(),
-                            rays.grid_idx.to(torch.int32).contiguous(), rays.near.contiguous(),
-                            rays.far.contiguous(), None)
+    a.rays = _lib.make_rays(_lib.aligned(rays.directions.contiguous()), _lib.aligned(rays.origins.contiguous()),
+                            _lib.aligned(rays.grid_idx.to(torch.int32).contiguous()), _lib.aligned(rays.near.contiguous()),
+                            _lib.aligned(rays.far.contiguous()), None)
     a.grid = _lib.make_grid_list(None, descs, channels, n_rows)
     a.march = _lib.make_march(num_samples, num_samples_inf, False, contract_coords, disparity_at_inf)
     keep = (a, out)  # noqa: F841  (keep tensors alive across the async launch)

@@ -79,7 +79,7 @@ class LightplaneSplatterFunction(torch.autograd.Function):
     def forward(ctx, feature, cfg: _SplatterCfg, directions, origins, grid_idx, near, far):
         dev = feature.device
         stream = _lib.current_stream(dev)
-        feature = feature.contiguous()
+        feature = _lib.aligned(feature.contiguous())  # (16-byte aligned base: a copy for a dense view at an element offset)
         out = torch.zeros(cfg.n_rows, cfg.channels, device=dev, dtype=torch.float32)
         weight = torch.zeros(cfg.n_rows, device=dev, dtype=torch.float32)
         a = _fill_args(cfg, directions, origins, grid_idx, near, far, feature)
@@ -105,7 +105,7 @@ class LightplaneSplatterFunction(torch.autograd.Function):
             return (None,) * 7
         dev = feature.device
         stream = _lib.current_stream(dev)
-        grad_out = grad_out.contiguous()
+        grad_out = _lib.aligned(grad_out.contiguous())
         grad_feature = torch.zeros_like(feature)
         a = _fill_args(cfg, directions, origins, grid_idx, near, far, feature)
         a.grad_out, a.weight, a.grad_encoding = _lib.ptr(grad_out), _lib.ptr(weight), _lib.ptr(grad_feature)
@@ -125,8 +125,8 @@ class LightplaneMLPSplatterFunction(torch.autograd.Function):
     def forward(ctx, feature, mlp_params, cfg: _SplatterCfg, directions, origins, grid_idx, near, far, *input_grids):
         dev = feature.device
         stream = _lib.current_stream(dev)
-        feature, mlp_params = feature.contiguous(), mlp_params.contiguous()
-        input_grids = tuple(g.contiguous() for g in input_grids)
+        feature, mlp_params = _lib.aligned(feature.contiguous()), _lib.aligned(mlp_params.contiguous())
+        input_grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in input_grids)
         out = torch.zeros(cfg.n_rows, cfg.channels, device=dev, dtype=torch.float32)
         weight = torch.zeros(cfg.n_rows, device=dev, dtype=torch.float32)
         a = _fill_args(cfg, directions, origins, grid_idx, near, far, feature, mlp_params, input_grids)
@@ -155,7 +155,7 @@ class LightplaneMLPSplatterFunction(torch.autograd.Function):
             return (None,) * (8 + len(input_grids))
         dev = feature.device
         stream = _lib.current_stream(dev)
-        grad_out = grad_out.contiguous()
+        grad_out = _lib.aligned(grad_out.contiguous())
         grad_feature = torch.zeros_like(feature) if need_feat else None
         grad_params = torch.zeros_like(mlp_params) if need_params else None
         grad_in = [torch.zeros_like(g) for g in input_grids] if any(need_grids) else None
@@ -199,10 +199,10 @@ def _prep_rays(rays: Rays, B: int, march_order: Optional[str] = "rays", rays_per
         {"rays.directions": rays.directions, "rays.origins": rays.origins, "rays.near": rays.near,
          "rays.far": rays.far, "rays.encoding": rays.encoding},
         {"rays.grid_idx": rays.grid_idx})
-    grid_idx = rays.grid_idx.to(torch.int32).contiguous()
+    grid_idx = _lib.aligned(rays.grid_idx.to(torch.int32).contiguous())
     march = check_inputs_and_plan(rays, grid_idx, B, march_order, rays_per_row)
-    return march, (rays.directions.contiguous(), rays.origins.contiguous(), grid_idx, rays.near.contiguous(),
-                   rays.far.contiguous())
+    return march, (_lib.aligned(rays.directions.contiguous()), _lib.aligned(rays.origins.contiguous()), grid_idx,
+                   _lib.aligned(rays.near.contiguous()), _lib.aligned(rays.far.contiguous()))
 
 
 def lightplane_splatter(
