@@ -7,10 +7,14 @@ plane grids as parameters, optimised with Adam on random rays.  The role of the 
 examples/fit_single_scene.py training loop (:282-334) as a convergence check, on synthetic data because the
 GPU boxes have no datasets.
 
-    python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0]
+    python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
+
+``--upsample-steps 100,200`` fits coarse to fine (the reference example's schedule, examples/fit_single_scene.py): the planes start at
+``res / 2^k`` for ``k`` listed steps, and before each of those steps ``lp.grid_up_sample`` doubles them -- one HIP sweep per plane on
+the planes' own layout -- and the optimiser is rebuilt for the new tensors.  Without it the run is as it always was.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -58,18 +62,42 @@ def random_rays(n, gen, dev):
                    near=near.to(dev), far=far.to(dev), encoding=None)
 
 
-def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0):
+def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev):
+    rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
+    with torch.no_grad():
+        tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
+        _, _, rgb = renderer(rays, list(grids))
+        mse = float(((rgb - tgt_rgb) ** 2).mean())
+    return -10.0 * math.log10(mse)
+
+
+def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
+        upsample_steps=()):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
     lp.config.stop_transmittance = float(stop_transmittance)
     renderer = lp.LightplaneRenderer(num_samples=num_samples, color_chn=3, grid_chn=chn, mlp_hidden_chn=32,
                                      opacity_init_bias=-2.0, gain=1.0, bg_color=0.0).to(dev)
-    shapes = [(1, 1, res, res, chn), (1, res, 1, res, chn), (1, res, res, 1, chn)]
+    upsample_steps = sorted(int(v) for v in upsample_steps)
+    start_res = res >> len(upsample_steps)
+    assert start_res >= 2 and start_res << len(upsample_steps) == res, f"res {res} cannot be halved {len(upsample_steps)} times"
+    shapes = [(1, 1, start_res, start_res, chn), (1, start_res, 1, start_res, chn), (1, start_res, start_res, 1, chn)]
     grids = torch.nn.ParameterList([torch.nn.Parameter(0.1 * torch.randn(*s, generator=gen).to(dev)) for s in shapes])
-    opt = torch.optim.Adam([{"params": grids.parameters(), "lr": 3e-2}, {"params": renderer.parameters(), "lr": 3e-3}])
-    losses, tvs = [], []
+
+    def make_opt():
+        return torch.optim.Adam([{"params": grids.parameters(), "lr": 3e-2}, {"params": renderer.parameters(), "lr": 3e-3}])
+
+    opt = make_opt()
+    losses, tvs, psnr_at_upsample = [], [], []
     for it in range(steps):
+        if it in upsample_steps:
+            psnr_at_upsample.append(heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev))
+            new = lp.grid_up_sample([g.detach() for g in grids], upsample_factor=2.0)
+            grids = torch.nn.ParameterList([torch.nn.Parameter(g) for g in new])
+            opt = make_opt()  # new tensors: new optimiser state, as the reference example does
+            if verbose:
+                print(f"step {it:4d}  planes -> {tuple(grids[0].shape)}  held-out PSNR before {psnr_at_upsample[-1]:.2f} dB", flush=True)
         rays = random_rays(n_rays, gen, dev)
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
@@ -83,13 +111,12 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         losses.append(float(loss.detach()))
         if verbose and (it % 50 == 0 or it == steps - 1):
             print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
-    rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
-    with torch.no_grad():
-        tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
-        _, _, rgb = renderer(rays, list(grids))
-        mse = float(((rgb - tgt_rgb) ** 2).mean())
-    out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": -10.0 * math.log10(mse),
+    out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5,
+           "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev),
            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
+    if upsample_steps:
+        out.update(upsample_steps=upsample_steps, start_res=start_res, psnr_at_upsample_db=psnr_at_upsample,
+                   grid_shapes=[list(g.shape) for g in grids])
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
                    grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
@@ -102,5 +129,8 @@ if __name__ == "__main__":
     ap.add_argument("--rays", type=int, default=8192)
     ap.add_argument("--stop-transmittance", type=float, default=0.0)
     ap.add_argument("--tv-weight", type=float, default=0.0)
+    ap.add_argument("--upsample-steps", type=lambda v: tuple(int(x) for x in v.split(",") if x), default=(),
+                    help="comma-separated steps before which the planes are doubled; they start at res / 2^k")
     a = ap.parse_args()
-    print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight)))
+    print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
+                         upsample_steps=a.upsample_steps)))

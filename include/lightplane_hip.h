@@ -34,7 +34,7 @@
  *     Row offsets inside a flat grid tensor are not pointers and carry no such rule.
  *     (hipMalloc and every framework allocator return at least 256-byte alignment; what
  *     needs care is a view at an element offset into a larger buffer: copy it.)  The
- *     lp_grid_tv_* entry points take any 4-byte-aligned grid (scalar path when under-aligned).
+ *     lp_grid_tv_* and lp_grid_resample_* entry points take any 4-byte-aligned grid (scalar path when under-aligned).
  *   - accumulation targets (grad_*, splat feature/weight grids) MUST be zeroed by
  *     the caller: kernels accumulate with atomics (reference does the same:
  *     lightplane_renderer.py:470-476, 642-651; lightplane_splatter.py:404-410).
@@ -91,7 +91,9 @@ extern "C" {
                                   later still, again without a version change (no struct change; every call whose pointers come from an
                                   allocator answers as before): a device pointer of LpRendererArgs / LpSplatterArgs / LpRayEmbedArgs or
                                   of lp_splatter_normalize() that is not 16-byte aligned is refused with LP_EINVAL (Conventions above;
-                                  the kernels always assumed it, nothing checked it) */
+                                  the kernels always assumed it, nothing checked it); and, additive again: resampling of a grid-list
+                                  to new spatial sizes, lp_grid_resample_forward() / _backward() (lp_build_info() then has a
+                                  "grid_resample" entry) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -414,6 +416,33 @@ int lp_grid_tv_backward(const LpGridList* grid, const float* grid_weights, int32
 int lp_grid_tv_fused(const LpGridList* grid, const float* grid_weights, int32_t n_weights, int32_t p, float* loss, void* workspace,
                      int64_t workspace_bytes, const float* grad_loss, float scale, float* grad, float* const* grad_list,
                      int32_t n_grad_list, void* stream);
+
+/* Resampling of a grid-list to new spatial sizes, on the channels-last layout (lp_grid_resample.hip; the role of the reference's
+ * examples/utils/util/grid_util.py grid_up_sample = permute + torch.nn.functional.interpolate + permute, without the copies).
+ * `src` and `dst` are grid-lists as everywhere in this header (flat tensor + row offsets, or per-grid base pointers; any positive
+ * extents, as for lp_grid_tv_*) with the same number of grids, the same channel count and, grid by grid, the same B: grid g of `src`
+ * [B, D, H, W, C] is resampled to the extents of grid g of `dst` [B, D', H', W', C].  Batch and channels are never resampled.
+ * Per spatial axis with input extent n_in, output extent n_out and one fp32 coefficient a:
+ *   align_corners == 1: src(o) = a * o;   align_corners == 0: src(o) = max(0, a * (o + 0.5) - 0.5)
+ *   i0 = min(floor(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), lambda = clamp(src - i0, 0, 1)
+ * and an output cell is the tensor product over the three axes: the sum of 8 input rows with weights prod (1 - lambda | lambda) --
+ * torch's trilinear interpolation (bilinear for a plane: an axis with n_in == 1 replicates).  fp32, every operation individually rounded.
+ * `coeffs`: HOST array of 3 * n_grids floats, a of grid g and axis D, H, W at [3 g], [3 g + 1], [3 g + 2] -- torch takes
+ * (float)(1.0 / scale_factor) when it is given a scale factor and align_corners is off -- or NULL: derived from the sizes, with
+ * align_corners (n_in - 1) / (n_out - 1) (0 for n_out == 1), without n_in / n_out, both as fp32 divisions.
+ *   lp_grid_resample_forward:  dst = R src.  The memory `dst` describes is WRITTEN (the struct's pointers are const for the readers).
+ *   lp_grid_resample_backward: the adjoint.  `grad_dst` (read) is shaped like the forward's dst, `grad_src` (WRITTEN) like its src:
+ *     grad_src[i] = sum_o w(o, i) grad_dst[o] with exactly the forward's weights, stored (accumulate == 0) or added to what the
+ *     buffer holds (accumulate != 0).  A gather per input cell in a fixed order: no atomics, bit-reproducible, any size ratio.
+ * 1 .. LP_MAX_WIDTH channels: rows move 16 bytes at a time where C % 4 == 0 and every pointer is 16-byte aligned, float by float
+ * otherwise (any 4-byte-aligned pointer is accepted).  No allocation, no state, no host synchronisation: graph-capturable.
+ * Before anything touches the device: LP_ENULL for a NULL list or a grid without a data pointer; LP_EINVAL for lists that differ in
+ * the number of grids, in channels or in a grid's B, an empty extent, align_corners outside {0, 1}, a coefficient that is not finite
+ * and positive, a tensor of 2^31 rows or more, a source that overlaps its destination, a pointer that is not 4-byte aligned;
+ * LP_EUNSUPPORTED for a channel count outside [1, LP_MAX_WIDTH]. */
+int lp_grid_resample_forward(const LpGridList* src, const LpGridList* dst, int32_t align_corners, const float* coeffs, void* stream);
+int lp_grid_resample_backward(const LpGridList* grad_src, const LpGridList* grad_dst, int32_t align_corners, const float* coeffs,
+                              int32_t accumulate, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

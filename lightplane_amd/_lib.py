@@ -116,6 +116,7 @@ EXPORTS = (
     "lp_ray_embedding_forward", "lp_ray_embedding_backward",
     "lp_mlp_splatter_backward_relu_dump", "lp_mlp_splatter_relu_dump_words", "lp_mlp_splatter_launch_shape",
     "lp_grid_tv_forward", "lp_grid_tv_backward", "lp_grid_tv_fused",  # (+ lp_grid_tv_workspace_bytes, which returns int64_t)
+    "lp_grid_resample_forward", "lp_grid_resample_backward",
 )
 
 
@@ -188,6 +189,11 @@ def lib() -> C.CDLL:
     L.lp_grid_tv_backward.argtypes = _tv + _tv_grad + [C.c_int32, C.c_void_p]
     L.lp_grid_tv_fused.restype = C.c_int
     L.lp_grid_tv_fused.argtypes = _tv + [C.c_void_p, C.c_void_p, C.c_int64] + _tv_grad + [C.c_void_p]
+    # resampling of a grid-list: source list, destination list, align_corners, HOST coefficient array (or NULL), ...
+    L.lp_grid_resample_forward.restype = C.c_int
+    L.lp_grid_resample_forward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_void_p]
+    L.lp_grid_resample_backward.restype = C.c_int
+    L.lp_grid_resample_backward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in enumerate((LpGrid, LpGridList, LpRays, LpMarch, LpMlp, LpRendererArgs, LpSplatterArgs,

@@ -1,6 +1,7 @@
 // lp_api.hip -- the extern "C" surface of liblightplane_hip.so (see include/lightplane_hip.h).
 // Argument validation, kernel selection and error reporting; no device code here.
 #include <stdarg.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -353,6 +354,69 @@ static int check_grid_tv(const char* what, const LpGridList* grid, const float* 
   return LP_OK;
 }
 
+// One list of lp_grid_resample_*: any positive extents, as for the regulariser; every tensor below 2^31 rows.
+static int check_resample_list(const char* what, const char* name, const LpGridList* glp) {
+  if (!glp) return set_error(LP_ENULL, "%s: the %s grid-list is NULL", what, name);
+  const LpGridList& gl = *glp;
+  if (gl.n_grids < 1 || gl.n_grids > LP_MAX_GRIDS)
+    return set_error(LP_EINVAL, "%s: %s n_grids %d outside [1, %d]", what, name, gl.n_grids, LP_MAX_GRIDS);
+  if (gl.channels < 1 || gl.channels > LP_MAX_WIDTH)
+    return set_error(LP_EUNSUPPORTED, "%s: %s has %d channels, outside [1, %d]", what, name, gl.channels, LP_MAX_WIDTH);
+  for (int g = 0; g < gl.n_grids; ++g) {
+    const LpGrid& d = gl.grids[g];
+    if (d.B < 1 || d.D < 1 || d.H < 1 || d.W < 1)
+      return set_error(LP_EINVAL, "%s: %s grid[%d]: empty extent [%d,%d,%d,%d]", what, name, g, d.B, d.D, d.H, d.W);
+    if (d.row_offset < 0) return set_error(LP_EINVAL, "%s: %s grid[%d]: negative row_offset", what, name, g);
+    const int64_t rows = (int64_t)d.B * d.D * d.H * d.W;
+    if (d.row_offset + rows >= ((int64_t)1 << 31))
+      return set_error(LP_EINVAL, "%s: %s grid[%d] ends at row %lld: at most 2^31 - 1 rows per tensor", what, name, g,
+                       (long long)(d.row_offset + rows));
+    if (!d.data && d.row_offset + rows > gl.n_rows)
+      return set_error(LP_EINVAL, "%s: %s grid[%d]: rows [%lld, %lld) outside the flat tensor (%lld rows)", what, name, g,
+                       (long long)d.row_offset, (long long)(d.row_offset + rows), (long long)gl.n_rows);
+  }
+  return LP_OK;
+}
+
+// everything lp_grid_resample_forward / _backward check; fills the normalised lists
+static int check_grid_resample(const char* what, const LpGridList* src, const LpGridList* dst, int align_corners, const float* coeffs,
+                               LpGridList& s, LpGridList& d) {
+  int rc;
+  if ((rc = check_resample_list(what, "source", src))) return rc;
+  if ((rc = check_resample_list(what, "destination", dst))) return rc;
+  if (src->n_grids != dst->n_grids)
+    return set_error(LP_EINVAL, "%s: %d source grids for %d destination grids", what, src->n_grids, dst->n_grids);
+  if (src->channels != dst->channels)
+    return set_error(LP_EINVAL, "%s: %d source channels for %d destination channels", what, src->channels, dst->channels);
+  for (int g = 0; g < src->n_grids; ++g)
+    if (src->grids[g].B != dst->grids[g].B)
+      return set_error(LP_EINVAL, "%s: grid[%d]: batch size %d of the source, %d of the destination (the batch axis is not resampled)",
+                       what, g, src->grids[g].B, dst->grids[g].B);
+  if (align_corners != 0 && align_corners != 1) return set_error(LP_EINVAL, "%s: align_corners = %d, has to be 0 or 1", what, align_corners);
+  if (coeffs)
+    for (int i = 0; i < 3 * src->n_grids; ++i)
+      if (!(coeffs[i] > 0.0f) || !std::isfinite(coeffs[i]))
+        return set_error(LP_EINVAL, "%s: coordinate coefficient %d (grid %d, axis %c) is %g: has to be finite and positive", what, i, i / 3,
+                         "DHW"[i % 3], (double)coeffs[i]);
+  s = *src, d = *dst;
+  if (!normalize_grid_list(s) || !normalize_grid_list(d))
+    return set_error(LP_ENULL, "%s: a grid has neither its own data pointer nor a flat tensor", what);
+  const int64_t C = s.channels;
+  for (int g = 0; g < s.n_grids; ++g)
+    if ((((uintptr_t)s.grids[g].data | (uintptr_t)d.grids[g].data) & 3) != 0)
+      return set_error(LP_EINVAL, "%s: grid[%d]: fp32 data has to be 4-byte aligned", what, g);
+  for (int i = 0; i < s.n_grids; ++i) {
+    const LpGrid& a = s.grids[i];
+    const uintptr_t a0 = (uintptr_t)(a.data + a.row_offset * C), a1 = a0 + (uintptr_t)((int64_t)a.B * a.D * a.H * a.W * C * 4);
+    for (int j = 0; j < d.n_grids; ++j) {
+      const LpGrid& b = d.grids[j];
+      const uintptr_t b0 = (uintptr_t)(b.data + b.row_offset * C), b1 = b0 + (uintptr_t)((int64_t)b.B * b.D * b.H * b.W * C * 4);
+      if (a0 < b1 && b0 < a1) return set_error(LP_EINVAL, "%s: source grid %d aliases destination grid %d", what, i, j);
+    }
+  }
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -368,10 +432,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -730,6 +794,21 @@ int lp_grid_tv_fused(const LpGridList* grid, const float* grid_weights, int32_t 
                                grad_list, n_grad_list, gl, grads);
   if (rc) return rc;
   return grid_tv_launch(gl, grid_weights, p, loss, (double*)workspace, grad_loss, scale, grads, true, (hipStream_t)stream);
+}
+
+int lp_grid_resample_forward(const LpGridList* src, const LpGridList* dst, int32_t align_corners, const float* coeffs, void* stream) {
+  LpGridList s, d;
+  const int rc = check_grid_resample("lp_grid_resample_forward", src, dst, align_corners, coeffs, s, d);
+  if (rc) return rc;
+  return grid_resample_launch(s, d, align_corners, coeffs, false, false, (hipStream_t)stream);
+}
+
+int lp_grid_resample_backward(const LpGridList* grad_src, const LpGridList* grad_dst, int32_t align_corners, const float* coeffs,
+                              int32_t accumulate, void* stream) {
+  LpGridList s, d;
+  const int rc = check_grid_resample("lp_grid_resample_backward", grad_src, grad_dst, align_corners, coeffs, s, d);
+  if (rc) return rc;
+  return grid_resample_launch(s, d, align_corners, coeffs, true, accumulate != 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

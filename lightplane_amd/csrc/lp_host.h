@@ -114,6 +114,12 @@ int64_t grid_tv_workspace_bytes(const LpGridList& gl);
 int grid_tv_launch(const LpGridList& gl, const float* weights, int p, float* loss, double* workspace, const float* grad_loss, float scale,
                    float* const* grads, bool accumulate, hipStream_t stream);
 const char* build_info_grid_tv();
+// resampling of a grid-list to new spatial sizes: lp_grid_resample.hip (backward == false: dst = R src; true: src (= | +=) R^T dst;
+// coeffs: HOST array of 3 * n_grids coordinate coefficients in D, H, W order, or NULL = grid_resample_coeff() of the sizes)
+float grid_resample_coeff(int n_in, int n_out, bool align);
+int grid_resample_launch(const LpGridList& src, const LpGridList& dst, int align, const float* coeffs, bool backward, bool accumulate,
+                         hipStream_t stream);
+const char* build_info_grid_resample();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 
