@@ -8,6 +8,7 @@ examples/fit_single_scene.py training loop (:282-334) as a convergence check, on
 GPU boxes have no datasets.
 
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
+                                            [--scaffold-steps 150,250] [--scaffold-size 64]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -15,6 +16,12 @@ planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv
 ``--upsample-steps 100,200`` fits coarse to fine (the reference example's schedule, examples/fit_single_scene.py): the planes start at
 ``res / 2^k`` for ``k`` listed steps, and before each of those steps ``lp.grid_up_sample`` doubles them -- one HIP sweep per plane on
 the planes' own layout -- and the optimiser is rebuilt for the new tensors.  Without it the run is as it always was.
+
+``--scaffold-steps 150,250`` rebuilds the occupancy scaffold before each of those steps, as the reference's training recipe does
+periodically (examples/fit_single_scene.py ``update_scaffold_step``): ``renderer.calculate_scaffold`` on a ``--scaffold-size``^3 lattice
+-- one fused lattice kernel plus a byte dilation -- and every render from then on, held-out evaluation included, skips the samples
+the scaffold marks empty.  ``--scaffold-threshold`` is the opacity above which a lattice point counts as occupied (the module's default
+1e-7 keeps nearly everything).  Without ``--scaffold-steps`` no scaffold is built or passed.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -62,17 +69,17 @@ def random_rays(n, gen, dev):
                    near=near.to(dev), far=far.to(dev), encoding=None)
 
 
-def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev):
+def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None):
     rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
     with torch.no_grad():
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
-        _, _, rgb = renderer(rays, list(grids))
+        _, _, rgb = renderer(rays, list(grids), scaffold=scaffold)
         mse = float(((rgb - tgt_rgb) ** 2).mean())
     return -10.0 * math.log10(mse)
 
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
-        upsample_steps=()):
+        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -89,19 +96,27 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         return torch.optim.Adam([{"params": grids.parameters(), "lr": 3e-2}, {"params": renderer.parameters(), "lr": 3e-3}])
 
     opt = make_opt()
+    scaffold_steps = sorted(int(v) for v in scaffold_steps)
+    scaffold, occupancy = None, []
     losses, tvs, psnr_at_upsample = [], [], []
     for it in range(steps):
         if it in upsample_steps:
-            psnr_at_upsample.append(heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev))
+            psnr_at_upsample.append(heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold))
             new = lp.grid_up_sample([g.detach() for g in grids], upsample_factor=2.0)
             grids = torch.nn.ParameterList([torch.nn.Parameter(g) for g in new])
             opt = make_opt()  # new tensors: new optimiser state, as the reference example does
             if verbose:
                 print(f"step {it:4d}  planes -> {tuple(grids[0].shape)}  held-out PSNR before {psnr_at_upsample[-1]:.2f} dB", flush=True)
+        if it in scaffold_steps:
+            scaffold = renderer.calculate_scaffold(list(grids), [1, scaffold_size, scaffold_size, scaffold_size], dev,
+                                                   threshold=scaffold_threshold)
+            occupancy.append(float(scaffold.mean()))
+            if verbose:
+                print(f"step {it:4d}  scaffold {tuple(scaffold.shape)}  occupied {occupancy[-1]:.3f}", flush=True)
         rays = random_rays(n_rays, gen, dev)
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
-        _, alpha, rgb = renderer(rays, list(grids))
+        _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -112,11 +127,14 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         if verbose and (it % 50 == 0 or it == steps - 1):
             print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
     out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5,
-           "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev),
+           "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold),
            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
     if upsample_steps:
         out.update(upsample_steps=upsample_steps, start_res=start_res, psnr_at_upsample_db=psnr_at_upsample,
                    grid_shapes=[list(g.shape) for g in grids])
+    if scaffold_steps:
+        out.update(scaffold_steps=scaffold_steps, scaffold_shape=list(scaffold.shape) if scaffold is not None else None,
+                   scaffold_threshold=scaffold_threshold, scaffold_occupancy=occupancy)
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
                    grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
@@ -131,6 +149,11 @@ if __name__ == "__main__":
     ap.add_argument("--tv-weight", type=float, default=0.0)
     ap.add_argument("--upsample-steps", type=lambda v: tuple(int(x) for x in v.split(",") if x), default=(),
                     help="comma-separated steps before which the planes are doubled; they start at res / 2^k")
+    ap.add_argument("--scaffold-steps", type=lambda v: tuple(int(x) for x in v.split(",") if x), default=(),
+                    help="comma-separated steps before which the occupancy scaffold is rebuilt (none: no scaffold)")
+    ap.add_argument("--scaffold-size", type=int, default=64, help="points per axis of the scaffold's lattice")
+    ap.add_argument("--scaffold-threshold", type=float, default=1e-7, help="opacity above which a lattice point is occupied")
     a = ap.parse_args()
     print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
-                         upsample_steps=a.upsample_steps)))
+                         upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
+                         scaffold_threshold=a.scaffold_threshold)))

@@ -93,7 +93,11 @@ extern "C" {
                                   of lp_splatter_normalize() that is not 16-byte aligned is refused with LP_EINVAL (Conventions above;
                                   the kernels always assumed it, nothing checked it); and, additive again: resampling of a grid-list
                                   to new spatial sizes, lp_grid_resample_forward() / _backward() (lp_build_info() then has a
-                                  "grid_resample" entry) */
+                                  "grid_resample" entry)
+                                  and once more without a version change (additive: a new struct and three new entry points, nothing
+                                  existing touched): the occupancy scaffold of a grid-list, LpScaffoldArgs with
+                                  lp_scaffold_workspace_bytes() / lp_scaffold_opacity() / lp_scaffold_build() (lp_build_info() then
+                                  has a "scaffold" entry; lp_abi_sizeof(8) answers for the new struct) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -325,7 +329,7 @@ const char* lp_build_info(void);
 const char* lp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * which = 0 LpGrid, 1 LpGridList, 2 LpRays, 3 LpMarch, 4 LpMlp, 5 LpRendererArgs,
- * 6 LpSplatterArgs, 7 LpRayEmbedArgs; anything else returns -1. */
+ * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs; anything else returns -1. */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the
@@ -443,6 +447,46 @@ int lp_grid_tv_fused(const LpGridList* grid, const float* grid_weights, int32_t 
 int lp_grid_resample_forward(const LpGridList* src, const LpGridList* dst, int32_t align_corners, const float* coeffs, void* stream);
 int lp_grid_resample_backward(const LpGridList* grad_src, const LpGridList* grad_dst, int32_t align_corners, const float* coeffs,
                               int32_t accumulate, void* stream);
+
+/* Occupancy scaffold of a grid-list (lp_scaffold.hip; the role of the reference's LightplaneRenderer.calculate_scaffold,
+ * renderer_module.py:349-417, without the lattice of points, the encoding and the float max-pool).  The decoder's opacity is evaluated
+ * on the regular lattice of a [B, D, H, W] scaffold -- x along W, y along H, z along D; the coordinate of index i on an axis of n points
+ * is the fp32 value of torch.linspace(0, 1, n)[i] * 2 - 1 (torch's two-sided formula; n == 1 gives -1) --:
+ *   features = sum over the grids of `grid` of their tri- / bi-linear sample at the point (the Renderer's gather: align_corners off,
+ *              zero padding; all zero at a point outside [-1, 1]^3 when mask_out_of_bounds is set)
+ *   raw      = opacity MLP(ReLU(trunk MLP(features)))   (ReLU after every trunk layer and between the head's layers), or, with
+ *              trunk.n_layers == 0 (the two-grid decoder), opacity MLP(ReLU(features))
+ *   opacity  = gain * softplus(raw)
+ * in plain fp32 FMA arithmetic.  `mlp_params` is the decoder's flat vector as LpRendererArgs takes it (trunk | opacity | colour);
+ * trunk.offset is 0, opacity.offset the trunk's size, and the colour MLP behind them is never read: n_mlp_params only has to cover
+ * the two MLPs that are.  Any layer counts, widths up to LP_MAX_WIDTH, 1 .. LP_MAX_WIDTH grid channels.
+ *   lp_scaffold_opacity: opacity[b, z, y, x] = that value (the raw lattice; threshold and dilate are ignored).
+ *   lp_scaffold_build:   scaffold = max_pool3d(opacity, 2 * dilate + 1, stride 1, padding dilate) > threshold as 0 / 1 floats, computed as
+ *     the binary OR-dilation of (opacity > threshold) -- the same thing: the pool's padding never wins and max commutes with a monotone
+ *     threshold -- in three separable byte passes.  `workspace`: device memory of lp_scaffold_workspace_bytes() bytes (one byte per
+ *     lattice point when dilate > 0, else 0 and the pointer may be NULL), free to reuse once the call's work on `stream` is done.  The
+ *     result tensor itself serves as the second byte buffer.  A window at least as wide as an axis covers the whole axis.
+ *   lp_scaffold_workspace_bytes: shapes only (shape and dilate; no device), or a negative LP_E* code.
+ * One launch for the lattice and three for the dilation, all on `stream`: no atomics, no allocation, no host synchronisation
+ * (graph-capturable).  Every device pointer -- the grids, mlp_params, the result, the workspace -- is 16-byte aligned (Conventions).
+ * Before anything touches the device: LP_ENULL for NULL args / mlp_params / result or a grid without data; LP_EINVAL for a scaffold
+ * extent < 1, shape.B different from the grid-list's batch, dilate < 0, a threshold that is NaN, MLPs that do not chain (trunk input
+ * != grid channels, head input != trunk output, head output != 1) or do not fit n_mlp_params, an under-aligned pointer, a workspace
+ * that is NULL, short or misaligned when bytes are needed; LP_EUNSUPPORTED for widths or channels outside [1, LP_MAX_WIDTH]. */
+typedef struct LpScaffoldArgs {
+  LpGridList grid;             /* feature grid-list, as in LpRendererArgs */
+  const float* mlp_params;     /* the decoder's flat parameter vector */
+  int64_t n_mlp_params;
+  LpMlp trunk, opacity;        /* as in LpRendererArgs; trunk.n_layers == 0: two-grid decoder */
+  float gain;
+  int32_t mask_out_of_bounds;  /* zero the features of a lattice point outside [-1, 1]^3 (fp32 round-off at the faces only) */
+  LpGrid shape;                /* B, D, H, W of the scaffold (row_offset and data ignored) */
+  float threshold;             /* occupied: opacity > threshold */
+  int32_t dilate;              /* radius r of the dilation window 2 r + 1; 0 = none */
+} LpScaffoldArgs;
+int64_t lp_scaffold_workspace_bytes(const LpScaffoldArgs* args);
+int lp_scaffold_opacity(const LpScaffoldArgs* args, float* opacity, void* stream);
+int lp_scaffold_build(const LpScaffoldArgs* args, float* scaffold, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

@@ -28,6 +28,7 @@ from .splatter import (LightplaneMLPSplatterFunction, LightplaneSplatterFunction
 from .modules import LightplaneMLPSplatter, LightplaneRenderer, LightplaneSplatter  # noqa: E402
 from .regularizers import add_grid_tv_grad_, grid_tv_loss, grid_tv_workspace_bytes  # noqa: E402
 from .resample import grid_resample, grid_up_sample, resampled_sizes  # noqa: E402
+from .scaffold import calculate_scaffold, scaffold_opacity, scaffold_workspace_bytes  # noqa: E402
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -49,6 +50,7 @@ __all__ = [
     "unflatten_grid", "calc_harmonic_embedding", "calc_harmonic_embedding_dim", "jitter_near_far",
     "grid_tv_loss", "add_grid_tv_grad_", "grid_tv_workspace_bytes",
     "grid_resample", "grid_up_sample", "resampled_sizes",
+    "calculate_scaffold", "scaffold_opacity", "scaffold_workspace_bytes",
 ]
 
 _NOT_PROVIDED = {

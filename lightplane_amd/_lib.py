@@ -103,6 +103,14 @@ class LpRayEmbedArgs(C.Structure):
     ]
 
 
+class LpScaffoldArgs(C.Structure):
+    _fields_ = [
+        ("grid", LpGridList), ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64),
+        ("trunk", LpMlp), ("opacity", LpMlp), ("gain", C.c_float), ("mask_out_of_bounds", C.c_int32),
+        ("shape", LpGrid), ("threshold", C.c_float), ("dilate", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -117,6 +125,7 @@ EXPORTS = (
     "lp_mlp_splatter_backward_relu_dump", "lp_mlp_splatter_relu_dump_words", "lp_mlp_splatter_launch_shape",
     "lp_grid_tv_forward", "lp_grid_tv_backward", "lp_grid_tv_fused",  # (+ lp_grid_tv_workspace_bytes, which returns int64_t)
     "lp_grid_resample_forward", "lp_grid_resample_backward",
+    "lp_scaffold_opacity", "lp_scaffold_build",  # (+ lp_scaffold_workspace_bytes, which returns int64_t)
 )
 
 
@@ -194,10 +203,17 @@ def lib() -> C.CDLL:
     L.lp_grid_resample_forward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_void_p]
     L.lp_grid_resample_backward.restype = C.c_int
     L.lp_grid_resample_backward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    # occupancy scaffold of a grid-list: args, result (, workspace, workspace bytes), stream
+    L.lp_scaffold_workspace_bytes.restype = C.c_int64
+    L.lp_scaffold_workspace_bytes.argtypes = [C.POINTER(LpScaffoldArgs)]
+    L.lp_scaffold_opacity.restype = C.c_int
+    L.lp_scaffold_opacity.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p]
+    L.lp_scaffold_build.restype = C.c_int
+    L.lp_scaffold_build.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in enumerate((LpGrid, LpGridList, LpRays, LpMarch, LpMlp, LpRendererArgs, LpSplatterArgs,
-                                LpRayEmbedArgs)):
+                                LpRayEmbedArgs, LpScaffoldArgs)):
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -417,6 +417,52 @@ static int check_grid_resample(const char* what, const LpGridList* src, const Lp
   return LP_OK;
 }
 
+// shape and dilation of a scaffold: all lp_scaffold_workspace_bytes() looks at
+static int check_scaffold_shape(const char* what, const LpScaffoldArgs* args) {
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const LpGrid& s = args->shape;
+  if (s.B < 1 || s.D < 1 || s.H < 1 || s.W < 1)
+    return set_error(LP_EINVAL, "%s: scaffold shape [%d,%d,%d,%d] has an extent < 1", what, s.B, s.D, s.H, s.W);
+  if (args->dilate < 0) return set_error(LP_EINVAL, "%s: dilate = %d, has to be >= 0", what, args->dilate);
+  return LP_OK;
+}
+
+// everything lp_scaffold_opacity / lp_scaffold_build share; fills the normalised copy
+static int check_scaffold(const char* what, const LpScaffoldArgs* args, const float* out, LpScaffoldArgs& a) {
+  int rc;
+  if ((rc = check_scaffold_shape(what, args))) return rc;
+  if ((rc = check_grid_list_aligned("grid", args->grid))) return rc;
+  LP_ALIGNED(*args, mlp_params);
+  if ((rc = check_aligned("scaffold / opacity (the result)", out))) return rc;
+  if ((rc = check_grid_list("grid", args->grid, true))) return rc;
+  if (args->shape.B != args->grid.grids[0].B)
+    return set_error(LP_EINVAL, "%s: scaffold batch %d != grid batch %d", what, args->shape.B, args->grid.grids[0].B);
+  if (args->threshold != args->threshold) return set_error(LP_EINVAL, "%s: threshold is NaN", what);
+  if ((rc = check_mlp("trunk", args->trunk, true))) return rc;
+  if ((rc = check_mlp("opacity", args->opacity, false))) return rc;
+  const int C = args->grid.channels;
+  int head_in = C;
+  if (args->trunk.n_layers > 0) {
+    if (args->trunk.dims[0] != C)
+      return set_error(LP_EINVAL, "%s: trunk MLP input width %d != grid channels %d", what, args->trunk.dims[0], C);
+    head_in = args->trunk.dims[args->trunk.n_layers];
+  }
+  if (args->opacity.dims[0] != head_in)
+    return set_error(LP_EINVAL, "%s: opacity MLP input width %d != %d", what, args->opacity.dims[0], head_in);
+  if (args->opacity.dims[args->opacity.n_layers] != 1)
+    return set_error(LP_EINVAL, "%s: opacity MLP must end in 1 output, got %d", what, args->opacity.dims[args->opacity.n_layers]);
+  if (args->trunk.offset != 0 || args->opacity.offset != mlp_numel(args->trunk))
+    return set_error(LP_EINVAL, "%s: MLP offsets do not follow the trunk|opacity|color flat layout", what);
+  if (args->opacity.offset + mlp_numel(args->opacity) > args->n_mlp_params)
+    return set_error(LP_EINVAL, "%s: trunk and opacity MLPs take %lld floats, mlp_params has %lld", what,
+                     (long long)(args->opacity.offset + mlp_numel(args->opacity)), (long long)args->n_mlp_params);
+  if (!args->mlp_params) return set_error(LP_ENULL, "%s: mlp_params is NULL", what);
+  if (!out) return set_error(LP_ENULL, "%s: the result pointer is NULL", what);
+  a = *args;
+  if (!normalize_grid_list(a.grid)) return set_error(LP_ENULL, "%s: grid.data is NULL (and a grid has no pointer of its own)", what);
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -432,10 +478,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -452,6 +498,7 @@ int lp_abi_sizeof(int which) {
     case 5: return (int)sizeof(LpRendererArgs);
     case 6: return (int)sizeof(LpSplatterArgs);
     case 7: return (int)sizeof(LpRayEmbedArgs);
+    case 8: return (int)sizeof(LpScaffoldArgs);
     default: return -1;
   }
 }
@@ -809,6 +856,37 @@ int lp_grid_resample_backward(const LpGridList* grad_src, const LpGridList* grad
   const int rc = check_grid_resample("lp_grid_resample_backward", grad_src, grad_dst, align_corners, coeffs, s, d);
   if (rc) return rc;
   return grid_resample_launch(s, d, align_corners, coeffs, true, accumulate != 0, (hipStream_t)stream);
+}
+
+int64_t lp_scaffold_workspace_bytes(const LpScaffoldArgs* args) {
+  const int rc = check_scaffold_shape("lp_scaffold_workspace_bytes", args);
+  if (rc) return rc;
+  return scaffold_workspace_bytes(args->shape, args->dilate);
+}
+
+int lp_scaffold_opacity(const LpScaffoldArgs* args, float* opacity, void* stream) {
+  LpScaffoldArgs a;
+  const int rc = check_scaffold("lp_scaffold_opacity", args, opacity, a);
+  if (rc) return rc;
+  return scaffold_launch(a, opacity, nullptr, false, (hipStream_t)stream);
+}
+
+int lp_scaffold_build(const LpScaffoldArgs* args, float* scaffold, void* workspace, int64_t workspace_bytes, void* stream) {
+  LpScaffoldArgs a;
+  int rc = check_scaffold("lp_scaffold_build", args, scaffold, a);
+  if (rc) return rc;
+  const int64_t need = scaffold_workspace_bytes(a.shape, a.dilate);
+  if (need > 0) {
+    if (!workspace) return set_error(LP_EINVAL, "lp_scaffold_build: workspace is NULL, lp_scaffold_workspace_bytes() asks for %lld bytes", (long long)need);
+    if (workspace_bytes < need)
+      return set_error(LP_EINVAL, "lp_scaffold_build: workspace of %lld bytes, lp_scaffold_workspace_bytes() asks for %lld",
+                       (long long)workspace_bytes, (long long)need);
+    if ((rc = check_aligned("workspace", workspace))) return rc;
+    const uintptr_t w0 = (uintptr_t)workspace, s0 = (uintptr_t)scaffold;
+    if (w0 < s0 + (uintptr_t)need * 4 && s0 < w0 + (uintptr_t)need)
+      return set_error(LP_EINVAL, "lp_scaffold_build: the workspace overlaps the result");
+  }
+  return scaffold_launch(a, scaffold, workspace, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -120,6 +120,11 @@ float grid_resample_coeff(int n_in, int n_out, bool align);
 int grid_resample_launch(const LpGridList& src, const LpGridList& dst, int align, const float* coeffs, bool backward, bool accumulate,
                          hipStream_t stream);
 const char* build_info_grid_resample();
+// occupancy scaffold of a grid-list: lp_scaffold.hip (occupancy == false: the raw opacity lattice; true: dilate(opacity > threshold) as
+// 0 / 1 floats through one byte per point of `workspace`)
+int64_t scaffold_workspace_bytes(const LpGrid& shape, int dilate);
+int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool occupancy, hipStream_t stream);
+const char* build_info_scaffold();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -30,6 +30,7 @@ import ctypes
 
 from . import _lib, config
 from .renderer import _render, lightplane_renderer
+from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
 
 logger = logging.getLogger(__name__)
@@ -89,6 +90,17 @@ def _fused_embedding_supported(n_harmonics: int, out_dim: int) -> bool:
     # (out_dim: check_ray_embed's LP_MAX_WIDTH; beyond it the PyTorch op chain runs, as the docstring promises)
     return (0 <= n_harmonics <= 10 and 1 <= out_dim <= 128
             and 256 * (6 * n_harmonics + 3 + 1 + out_dim + 1) * 4 <= 150 * 1024)
+
+
+def _fused_scaffold_supported(feature_grid, device) -> bool:
+    # what lp_scaffold_build takes as it is: fp32 grid tensors on the GPU the caller names, dense and 16-byte aligned (anything else
+    # keeps the Renderer path, whose front-end copies such tensors)
+    tensors = list(feature_grid) if isinstance(feature_grid, (list, tuple)) else [feature_grid]
+    dev = torch.device(device)
+    if dev.type != "cuda" or not tensors or not all(torch.is_tensor(t) for t in tensors):
+        return False
+    return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+               and (dev.index is None or t.device.index == dev.index) for t in tensors)
 
 
 class LightplaneRenderer(torch.nn.Module):
@@ -270,8 +282,15 @@ class LightplaneRenderer(torch.nn.Module):
         """Occupancy scaffold ``[B, D, H, W]`` (0/1 floats): the decoder's opacity on the regular lattice
         ``x = linspace(-1, 1, W)``, ``y = linspace(-1, 1, H)``, ``z = linspace(-1, 1, D)``, dilated by a
         max-pool of ``2 * dilate_scaffold + 1`` and thresholded (reference :349-417, which walks the lattice
-        slice by slice through the naive decoder; here one HIP launch per batch element)."""
+        slice by slice through the naive decoder).  With ``config.fused_module_ops`` and the grid on the GPU this is
+        :func:`lightplane_amd.calculate_scaffold` -- one lattice kernel that forms its own coordinates plus a dilation of
+        occupancy bytes, one byte per point of scratch; otherwise the lattice goes through the Renderer
+        as single-sample rays, one launch per batch element, and ``max_pool3d`` runs on the float lattice."""
         B, D, H, W = (int(v) for v in scaffold_size)
+        if config.fused_module_ops and dilate_scaffold >= 0 and _fused_scaffold_supported(feature_grid, device):
+            return _fused_calculate_scaffold(
+                feature_grid, self.get_decoder_params(), [B, D, H, W], gain=self.gain, threshold=threshold,
+                dilate_scaffold=dilate_scaffold, mask_out_of_bounds_samples=self.mask_out_of_bounds_samples, grid_sizes=grid_sizes)
         lin = lambda n: torch.linspace(0, 1, n, device=device) * 2.0 - 1.0  # noqa: E731
         zz, yy, xx = torch.meshgrid(lin(D), lin(H), lin(W), indexing="ij")
         pts = torch.stack([xx, yy, zz], dim=-1).reshape(1, D * H * W, 3)
