@@ -7,6 +7,7 @@
 #include "lp_device.h"
 #include "lp_splat_walk.h"
 #include "lp_host.h"
+#include "lp_plane_range.h"
 
 namespace lp {
 
@@ -89,6 +90,63 @@ LP_DEV f32x16 load_bias(const float* lds, int which, int h, int zo) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Per-wave sample ranges of the grids (tuned kernels, GM_TRIPLANE / GM_VOXEL).  Callers bracket the scene's bounding sphere with
+// near / far while the grid covers the cube: the samples before and behind the cube, and for a plane every sample at which one of
+// its two coordinates is outside, gather and scatter exact zeros.  lp_plane_range.h gives each ray the ONE interval of samples at
+// which a grid can carry weight; here the hull over the wave's 32 rays is formed once before the sample loop and kept in scalar
+// registers: lo[g], hi[g] for the planes xy, xz, yz (a voxel grid: g = 0).  Per sample the kernels ask mask(s) -- scalar compares,
+// no ballot, nothing live in vector registers.  `plain` = the march lp_plane_range.h describes (regular samples only, no
+// contraction; the callers also leave out scaffold and noise); anything else, and a wave with lanes beyond the batch, keeps every
+// sample.
+// ---------------------------------------------------------------------------------------
+LP_DEV int wave_min_i(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(v, m); v = o < v ? o : v; }
+  return __builtin_amdgcn_readfirstlane(v);
+}
+struct WaveRanges {
+  // TWO scalar registers and six scalar instructions per sample (the backward runs out of scalar registers as it is: it spills ten).
+  // Ten bits per plane: nine of value -- lo3 the first sample, hi3 the last one -- under a guard bit that a packed subtraction
+  // turns into the comparison of all three planes at once: field (512 + s) - lo keeps its guard bit iff s >= lo, field
+  // (512 + hi) - s iff s <= hi; neither borrows from its neighbour.  "No sample" is lo = 511, hi = 0.
+  unsigned lo3, hi3;
+  static constexpr unsigned G = 0x20080200u;  // guard bits (bit 9 of every field)
+  LP_DEV unsigned mask(int s) const {  // bit 9 + 10 g set: plane g can carry weight at sample s
+    s = __builtin_amdgcn_readfirstlane(s);  // (the sample index is wave-uniform: scalar branches)
+    const unsigned sss = (unsigned)(s < 511 ? s : 511) * 0x00100401u;
+    return ((sss | G) - lo3) & ((hi3 | G) - sss) & G;
+  }
+  static constexpr unsigned bit(int g) { return 0x200u << (10 * g); }
+};
+constexpr int RANGE_MAX_S = 511;  // marches of more samples keep every sample
+LP_DEV WaveRanges wave_ranges_full() { return WaveRanges{0u, 0x1ff7fdffu}; }
+template <int GM>
+LP_DEV WaveRanges wave_plane_ranges(const LpRendererArgs& a, const Ray& ray, bool valid, bool plain) {
+  WaveRanges w = wave_ranges_full();
+  if (GM == GM_GENERIC) return w;
+  const int S = a.march.num_samples;
+  if (!plain || S > RANGE_MAX_S || __ballot(!valid) != 0) return w;  // (wave-uniform)
+  const LpGrid* g = a.grid.grids;
+  const int W = g[0].W, H = g[0].H, D = (GM == GM_TRIPLANE) ? g[1].D : g[0].D;
+  const AxisSpans ax = ray_axis_spans(ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, ray.near_t, ray.far_t, S, W, H, D);
+#pragma unroll
+  for (int p = 0; p < (GM == GM_TRIPLANE ? 3 : 1); ++p) {
+    const SampleSpan sp = (GM == GM_TRIPLANE) ? plane_span(ax, p, S) : voxel_span(ax, S);
+    const int lo = wave_min_i(sp.lo), hi = -wave_min_i(-sp.hi);  // hull over the wave: 0 <= lo <= S, -1 <= hi < S
+    if (p == 0) w.lo3 = w.hi3 = 0u;
+    w.lo3 |= (unsigned)(hi < lo ? 511 : lo) << (10 * p);
+    w.hi3 |= (unsigned)(hi < lo ? 0 : hi) << (10 * p);
+  }
+  if (GM == GM_VOXEL) {  // one grid: all three fields alike
+    w.lo3 *= 0x00100401u;
+    w.hi3 *= 0x00100401u;
+  }
+  w.lo3 = (unsigned)__builtin_amdgcn_readfirstlane((int)w.lo3);
+  w.hi3 = (unsigned)__builtin_amdgcn_readfirstlane((int)w.hi3);
+  return w;
+}
+
+// ---------------------------------------------------------------------------------------
 // grid-list gather: interpolated feature of this lane's ray, channels feat(q,h), q < C/2
 // ---------------------------------------------------------------------------------------
 template <int C>
@@ -152,21 +210,29 @@ LP_DEV void gather_list(const LpGridList& gl, bool mask_oob, const Ray& ray, flo
   }
 }
 
+// pm (GM_TRIPLANE / GM_VOXEL): bit g clear = no ray of this wave has a tap of non-zero weight in grid g at this sample
+// (WaveRanges::mask below, wave-uniform): its loads are not issued -- they would add exact zeros.
 template <int C, int GM, bool FENCED = false>
 LP_DEV void gather_features(const LpRendererArgs& a, const Ray& ray, float x, float y, float z, int h,
-                            float (&x0)[C / 2]) {
+                            float (&x0)[C / 2], unsigned pm = WaveRanges::G) {
 #pragma unroll
   for (int q = 0; q < C / 2; ++q) x0[q] = 0.0f;
   const float keep = (a.march.mask_out_of_bounds && !point_in_bounds(x, y, z)) ? 0.0f : 1.0f;
   if (GM == GM_TRIPLANE) {
     if (FENCED) {
-      // taps of the three planes first, then one plane's loads in flight at a time
-      Taps t[3];
-      triplane_taps<false>(a.grid.grids, ray.b, x, y, z, t);
+      // the three axes first, then one plane's taps and loads in flight at a time
+      AxisTap ax, ay, az;
+      triplane_axes<false>(a.grid.grids, x, y, z, ax, ay, az);
+      const int W = a.grid.grids[0].W, H = a.grid.grids[0].H, D = a.grid.grids[1].D;
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         __builtin_amdgcn_sched_barrier(0);
-        gather_taps4<C>(a.grid.grids[g].data, t[g].row, t[g].w, keep, h, x0);
+        if (pm & WaveRanges::bit(g)) {
+          Taps t;
+          plane_taps_from_axes((int)a.grid.grids[g].row_offset + ray.b * ((g == 0 ? H : D) * (g == 2 ? H : W)), g == 2 ? H : W,
+                               g == 2 ? ay : ax, g == 0 ? ay : az, t);
+          gather_taps4<C>(a.grid.grids[g].data, t.row, t.w, keep, h, x0);
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
     } else {
@@ -174,11 +240,13 @@ LP_DEV void gather_features(const LpRendererArgs& a, const Ray& ray, float x, fl
       triplane_taps<false>(a.grid.grids, ray.b, x, y, z, t);
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
+        if (!(pm & WaveRanges::bit(g))) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) gather_tap<C>(a.grid.grids[g].data, t[g].row[k], t[g].w[k] * keep, h, x0);
       }
     }
   } else if (GM == GM_VOXEL) {
+    if (!(pm & WaveRanges::bit(0))) return;
     Taps t;
     voxel_taps<false>(a.grid.grids[0], ray.b, x, y, z, t);
     if (FENCED) {
@@ -304,9 +372,9 @@ LP_DEV void sample_geometry(const LpRendererArgs& a, const float* lds, const Ray
 }
 
 template <int C, int GM, bool FENCED = false, bool PLAIN = false>
-LP_DEV void fetch_sample(const LpRendererArgs& a, const float* lds, const Ray& ray, int s, int h, Sample<C>& o) {
+LP_DEV void fetch_sample(const LpRendererArgs& a, const float* lds, const Ray& ray, int s, int h, Sample<C>& o, unsigned pm = WaveRanges::G) {
   sample_geometry<C, PLAIN>(a, lds, ray, s, o);
-  gather_features<C, GM, FENCED>(a, ray, o.x, o.y, o.z, h, o.x0);
+  gather_features<C, GM, FENCED>(a, ray, o.x, o.y, o.z, h, o.x0, pm);
 }
 
 // Gradient scatter, row-contiguous and run-length merged.
@@ -466,9 +534,10 @@ LP_DEV AxisNorm axis_norm(float c, int size) {
   n.dead = !(t.ok[0] | t.ok[1]);
   return n;
 }
+// pm: planes this wave-sample can reach (WaveRanges::mask); the others are not walked
 template <int C>
 LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b, float x, float y, float z, bool live, int lane,
-                             const float* dxT, float* wT) {
+                             const float* dxT, float* wT, unsigned pm = WaveRanges::G) {
   constexpr int CPL = C / 16;
   const int h = lane >> 5, r = lane & 31, sub = lane & 15, grp = lane >> 4;
   const int W = gl.grids[0].W, H = gl.grids[0].H, D = gl.grids[1].D;
@@ -496,6 +565,7 @@ LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b,
   // ---- the walk, one plane at a time (the code of the walk exists once) ----
 #pragma unroll 1
   for (int g = 0; g < 3; ++g) {
+    if (!(pm & WaveRanges::bit(g))) continue;
     const int row0 = g == 0 ? row_xy : (g == 1 ? row_xz : row_yz);
     const unsigned mask = g == 0 ? m_xy : (g == 1 ? m_xz : m_yz);
     const int U = g == 2 ? H : W;

@@ -79,12 +79,15 @@ __global__ void __launch_bounds__(256, OCC) renderer_fwd_bf3(const LpRendererArg
   Act<C> t;
   const int s_lo = SEGF ? seg * seg_len : 0;
   const int s_hi = SEGF ? ((s_lo + seg_len < s_tot) ? s_lo + seg_len : s_tot) : s_tot;
+  // samples at which this wave's rays can reach each plane (lp_mfma_common.h); the segmented march keeps every sample
+  const bool plain_march = !SEGF && a.march.num_samples_inf == 0 && !a.march.contract_coords && !a.scaffold && !(a.noise_sigma > 0.0f);
+  const WaveRanges rg = wave_plane_ranges<GM>(a, ray, valid, plain_march);
   if (SEGF && s_lo > 0) {  // interval length of the segment's first sample
     sample_geometry<C>(a, sm, ray, s_lo - 1, nx);
     depth_prev = nx.depth;
   }
   for (int s = s_lo; s < s_hi; ++s) {
-    fetch_sample<C, GM, true>(a, sm, ray, s, h, nx);
+    fetch_sample<C, GM, true>(a, sm, ray, s, h, nx, rg.mask(s));
     const float depth = nx.depth, occ = nx.occ;
 #pragma unroll
     for (int q = 0; q < C / 2; ++q) t.x0[q] = nx.x0[q];

@@ -305,10 +305,17 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       suffix = -rest;
     }
   }
+  // samples at which this wave's rays can reach each plane (lp_mfma_common.h: scalar registers); the non-PLAIN and the segmented
+  // instantiations keep every sample
+  const WaveRanges rg = wave_plane_ranges<GM>(a, ray, valid, PLAIN && !SEG);
   Sample<C> nx;
+  // (the first fetch gathers every plane: with scalar branches in it the allocator spills ~20 loop-invariant registers that the sample
+  // loop then reloads -- scripts/isa_loop_scratch.py: 23 scratch instructions per sample instead of none)
   fetch_sample<C, GM, false, PLAIN>(a, sm, ray, s_begin, h, nx);
   for (int s = s_begin; s >= s_lo; --s) {
     const bool on = PLAIN || s <= s_last_w;
+    const unsigned pm = rg.mask(s);  // planes this wave-sample reaches; 0: its grid gradient is zero -- no dX chain of trunk layer 1, no scatter
+    const bool ggs = gg && pm != 0u;
     const float depth = nx.depth, occ = nx.occ, x = nx.x, y = nx.y, z = nx.z;
     float x0[C / 2];
 #pragma unroll
@@ -576,7 +583,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     {
       if constexpr (DWB) {
         if (want_params) limb_tile_store<C / 16>(xrow, x0);
-        if (gg) {
+        if (ggs) {
           acc = layer_dxv<2, DXL>(Ab(I0{}), lane, dh1, (f32x16){0}, want_params ? yrow : nullptr);  // rows >= C of the result are unused
         } else if (want_params) {
           limb_tile_store<2>(yrow, dh1);
@@ -587,7 +594,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
           for (int q = 0; q < C / 2; ++q) xt[featq(q, h) * T_LD + r] = x0[q];
           tile_store_fm(yt, r, h, dh1);
         }
-        if (gg) {
+        if (ggs) {
           acc = layer_dxv<2, DXL>(Ab(I0{}), lane, dh1, (f32x16){0});  // rows >= C of the result are unused
         }
       }
@@ -598,7 +605,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
         lds_barrier();
       }
     }
-    if (gg) {
+    if (ggs) {
 #pragma unroll
       for (int q = 0; q < C / 2; ++q) xt[featq(q, h) * DX_LD + r] = acc[q];
     }
@@ -607,12 +614,12 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     LP_MARK("fetch");
     __builtin_amdgcn_s_setprio(0);
     const bool live = valid && on && !(a.march.mask_out_of_bounds && !point_in_bounds(x, y, z));
-    if (s > s_lo) fetch_sample<C, GM, true, PLAIN>(a, sm, ray, s - 1, h, nx);
+    if (s > s_lo) fetch_sample<C, GM, true, PLAIN>(a, sm, ray, s - 1, h, nx, rg.mask(s - 1));
     LP_SCHED_FENCE();
     LP_MARK("scatter");
-    if (gg) {
+    if (ggs) {
       if constexpr (GM == GM_TRIPLANE) {
-        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, yt);
+        scatter_triplane<C>(a.grad_grid_list, a.grid, ray.b, x, y, z, live, lane, xt, yt, pm);
       } else {
         const int ng = (GM == GM_VOXEL) ? 1 : a.grid.n_grids;
 #pragma unroll 1
