@@ -8,7 +8,7 @@ examples/fit_single_scene.py training loop (:282-334) as a convergence check, on
 GPU boxes have no datasets.
 
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
-                                            [--scaffold-steps 150,250] [--scaffold-size 64]
+                                            [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -23,6 +23,11 @@ periodically (examples/fit_single_scene.py ``update_scaffold_step``): ``renderer
 the scaffold marks empty.  ``--scaffold-threshold`` is the opacity above which a lattice point counts as occupied (the module's default
 1e-7 keeps nearly everything).  Without ``--scaffold-steps`` no scaffold is built or passed.
 
+``--export-pointcloud FILE.npy`` writes the fitted scene as a point cloud after the fit: the occupancy scaffold of a
+``--scaffold-size``^3 lattice at ``--scaffold-threshold`` (no dilation) picks the occupied lattice points, ``renderer.eval_decoder_at_points``
+-- one fused kernel, ``lp.lightplane_eval_mlp`` -- gives their opacity and their colour seen along ``-z``, and the file holds one
+float32 row ``x y z | r g b | opacity`` per point.
+
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
 import argparse
@@ -31,6 +36,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -79,7 +85,7 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None)
 
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
-        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7):
+        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -138,10 +144,29 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
                    grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
+    if export_pointcloud:
+        cloud = pointcloud(renderer, list(grids), scaffold_size, scaffold_threshold, dev)
+        np.save(export_pointcloud, cloud.cpu().numpy())
+        out.update(pointcloud_file=export_pointcloud, pointcloud_points=int(cloud.shape[0]))
     return out
 
 
-if __name__ == "__main__":
+@torch.no_grad()
+def pointcloud(renderer, grids, size, threshold, dev):
+    """[M, 7] float32 rows ``x y z | r g b | opacity``: the decoder at the lattice points of a size^3 scaffold whose opacity exceeds
+    ``threshold``, colours seen along -z"""
+    occupied = renderer.calculate_scaffold(grids, [1, size, size, size], dev, threshold=threshold, dilate_scaffold=0)[0]
+    lin = torch.linspace(0, 1, size, device=dev) * 2.0 - 1.0
+    iz, iy, ix = occupied.nonzero(as_tuple=True)
+    xyz = torch.stack([lin[ix], lin[iy], lin[iz]], dim=-1)
+    if xyz.shape[0] == 0:
+        return torch.zeros(0, 7, device=dev)
+    opacity, rgb = renderer.eval_decoder_at_points(xyz[None], torch.zeros(1, dtype=torch.int32, device=dev), None, grids,
+                                                   directions=torch.tensor([[0.0, 0.0, -1.0]], device=dev))
+    return torch.cat([xyz, rgb[0], opacity[0, :, None]], dim=-1)
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--rays", type=int, default=8192)
@@ -153,7 +178,16 @@ if __name__ == "__main__":
                     help="comma-separated steps before which the occupancy scaffold is rebuilt (none: no scaffold)")
     ap.add_argument("--scaffold-size", type=int, default=64, help="points per axis of the scaffold's lattice")
     ap.add_argument("--scaffold-threshold", type=float, default=1e-7, help="opacity above which a lattice point is occupied")
-    a = ap.parse_args()
-    print(json.dumps(fit(a.steps, a.rays, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
-                         upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
-                         scaffold_threshold=a.scaffold_threshold)))
+    ap.add_argument("--export-pointcloud", default=None, metavar="FILE.npy",
+                    help="after the fit, write xyz | rgb | opacity of the occupied lattice points of a scaffold")
+    ap.add_argument("--res", type=int, default=64, help="resolution of the planes")
+    a = ap.parse_args(argv)
+    out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
+              upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
+              scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud)
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

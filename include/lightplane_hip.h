@@ -97,7 +97,10 @@ extern "C" {
                                   and once more without a version change (additive: a new struct and three new entry points, nothing
                                   existing touched): the occupancy scaffold of a grid-list, LpScaffoldArgs with
                                   lp_scaffold_workspace_bytes() / lp_scaffold_opacity() / lp_scaffold_build() (lp_build_info() then
-                                  has a "scaffold" entry; lp_abi_sizeof(8) answers for the new struct) */
+                                  has a "scaffold" entry; lp_abi_sizeof(8) answers for the new struct)
+                                  and again (additive: a new struct and two new entry points): the decoder at arbitrary points,
+                                  LpPointsArgs with lp_points_forward() / lp_points_backward() (lp_build_info() then has a "points"
+                                  entry; lp_abi_sizeof(10) answers for the new struct) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -329,7 +332,8 @@ const char* lp_build_info(void);
 const char* lp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * which = 0 LpGrid, 1 LpGridList, 2 LpRays, 3 LpMarch, 4 LpMlp, 5 LpRendererArgs,
- * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs; anything else returns -1. */
+ * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs; anything else returns -1 -- 9 among them: the scaffold's
+ * tests pin that answer as "the first selector that does not exist", so the point evaluation took the next one. */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the
@@ -487,6 +491,76 @@ typedef struct LpScaffoldArgs {
 int64_t lp_scaffold_workspace_bytes(const LpScaffoldArgs* args);
 int lp_scaffold_opacity(const LpScaffoldArgs* args, float* opacity, void* stream);
 int lp_scaffold_build(const LpScaffoldArgs* args, float* scaffold, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The decoder at arbitrary 3-D points (lp_points.hip; the role of the reference's lightplane_eval_mlp / lightplane_eval_mlp_opacity_only,
+ * naive_renderer.py:328-598, as its LightplaneRenderer.eval_decoder_at_points / eval_opacity_at_points call them).  For point
+ * p = points[r, n] of ray r, batch element b = grid_idx[r] (clamped to the grid-list's batch) and encoding e = encoding[r]:
+ *   q        = p, or with contract_coords the Renderer's contraction of p (LpMarch.contract_coords: MeRF contraction, then x 0.5)
+ *   features = sum over the grids of `grid` of their tri- / bi-linear sample at q (the Renderer's gather: align_corners off, zero
+ *              padding; all zero outside [-1, 1]^3 when mask_out_of_bounds is set); cfeatures the same of `color_grid`
+ *   single grid-list:  t = ReLU(trunk MLP(features)) (ReLU(features) without trunk layers), raw = opacity MLP(t), craw = colour MLP(t + e)
+ *   two-grid decoder (color_grid.n_grids > 0, no trunk layers): raw = opacity MLP(ReLU(features)), craw = colour MLP(ReLU(cfeatures) + e)
+ *   opacity_out[r, n]   = gain * softplus(raw) * occ,   color_out[r, n, c] = sigmoid(craw[c]) * occ, c < color_chn
+ *   occ = 1, or with a scaffold its nearest-neighbour value at q (0 outside [-1, 1]^3), as in LpRendererArgs.
+ * lp_points_forward: one lane per point, activations in LDS column tiles, weights through wave-uniform scalar loads, plain fp32 FMA
+ *   chains (the lattice kernel of lp_scaffold_opacity with points read from memory).  color_out == NULL: opacity only -- the colour
+ *   MLP, the colour grid-list and the encoding are never read (color.n_layers may then be 0 and encoding NULL; n_mlp_params has to cover
+ *   the MLPs that are read).  The grad_* fields are ignored.
+ * lp_points_backward: the shape-generic Renderer backward without the march.  It reads nothing the forward wrote: it recomputes the
+ *   decoder of every point (fp32 matrix-core products for the wide layers: the same values to fp32 round-off, and the gradient
+ *   returned is that of the branch of every ReLU this recompute took), forms d raw = grad_opacity * gain * occ * softplus'(raw) and
+ *   d craw[c] = grad_color[c] * occ * sigmoid'(craw[c]), and goes back through the heads, the trunk and the gather.  grad_opacity /
+ *   grad_color: NULL = zeros; with grad_color == NULL the colour head is not evaluated (its parameters and the colour grid-list get no
+ *   contribution; color.n_layers may be 0 and encoding NULL).  Every result pointer may be NULL (that gradient is skipped); all but
+ *   grad_points are ACCUMULATED with atomics into buffers the caller has zeroed, as in lp_renderer_backward:
+ *   grad_grid / grad_grid_list, grad_color_grid / grad_color_grid_list (as in LpRendererArgs), grad_mlp_params [n_mlp_params],
+ *   grad_encoding [n_rays, encoding_dim] (a ray's points span wavefronts), and grad_points [n_rays, n_pts, 3] (WRITTEN):
+ *   d L / d p = J^T sum over both grid-lists, their grids and corners k of (d w_k / d q) <row_k, d features>, with d w_k / d q the
+ *   derivative of the tri- / bi-linear weight times size / 2 and J the Jacobian of the contraction; the out-of-bounds mask and the
+ *   scaffold are piecewise constant and contribute nothing.  The opacity_out / color_out fields are ignored.
+ * Any layer counts, widths and channels up to LP_MAX_WIDTH (backward: layer widths summing to at most 1024, as the generic Renderer).
+ * n_rays * n_pts == 0 launches nothing.  No allocation, no host synchronisation: graph-capturable.  Every device pointer is 16-byte
+ * aligned (Conventions).  Before anything touches the device: LP_ENULL for NULL args / points / grid_idx / mlp_params / opacity_out
+ * (forward), a grid without data, or a NULL encoding where the colour head runs; LP_EINVAL for negative n_rays / n_pts, MLPs that do
+ * not chain or do not fit n_mlp_params, encoding_dim != the colour head's input width, color_chn outside the colour head's output, a
+ * colour grid-list with trunk layers or with another batch size / channel count than `grid`, a scaffold of another batch size or an
+ * extent < 1, gradient buffers for some grids of a list only, an under-aligned pointer; LP_EUNSUPPORTED for widths or channels
+ * outside [1, LP_MAX_WIDTH], more than 2^31 x 64 points, or (backward) layer widths beyond 1024 in total. */
+typedef struct LpPointsArgs {
+  LpGridList grid;             /* feature grid-list */
+  LpGridList color_grid;       /* n_grids == 0: single grid-list (trunk MLP used) */
+  const float* mlp_params;     /* the decoder's flat parameter vector: trunk | opacity | colour */
+  int64_t n_mlp_params;
+  LpMlp trunk, opacity, color; /* as in LpRendererArgs */
+  int32_t color_chn;           /* real colour channels (<= color.dims[last]) */
+  float gain;
+  int32_t mask_out_of_bounds;
+  int32_t contract_coords;
+  const float* points;         /* [n_rays, n_pts, 3] */
+  const int32_t* grid_idx;     /* [n_rays] batch element of each ray's points, as LpRays.grid_idx */
+  const float* encoding;       /* [n_rays, encoding_dim] */
+  int32_t encoding_dim;        /* == the colour head's input width */
+  int32_t reserved;            /* 0 */
+  int64_t n_rays, n_pts;
+  const float* scaffold;       /* NULL or [B, D, H, W] occupancy (0 / 1 floats) */
+  LpGrid scaffold_shape;       /* B, D, H, W of the scaffold (row_offset and data ignored) */
+  /* forward results (written).  (The MLP fields above carry the names `opacity` and `color`, as in every struct here.) */
+  float* opacity_out;          /* [n_rays, n_pts] */
+  float* color_out;            /* [n_rays, n_pts, color_chn]; NULL = opacity only */
+  /* backward: upstream gradients (NULL = zeros) */
+  const float* grad_opacity;   /* [n_rays, n_pts] */
+  const float* grad_color;     /* [n_rays, n_pts, color_chn] */
+  /* backward results (NULL = skip) */
+  float* grad_grid;            /* like grid.data */
+  float* grad_color_grid;      /* like color_grid.data */
+  float* grad_grid_list[LP_MAX_GRIDS];        /* per-grid buffers, as in LpRendererArgs */
+  float* grad_color_grid_list[LP_MAX_GRIDS];
+  float* grad_mlp_params;      /* [n_mlp_params] */
+  float* grad_encoding;        /* [n_rays, encoding_dim] (accumulated) */
+  float* grad_points;          /* [n_rays, n_pts, 3] (written) */
+} LpPointsArgs;
+int lp_points_forward(const LpPointsArgs* args, void* stream);
+int lp_points_backward(const LpPointsArgs* args, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

@@ -111,6 +111,20 @@ class LpScaffoldArgs(C.Structure):
     ]
 
 
+class LpPointsArgs(C.Structure):
+    _fields_ = [
+        ("grid", LpGridList), ("color_grid", LpGridList), ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64),
+        ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("color_chn", C.c_int32), ("gain", C.c_float), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32),
+        ("points", C.c_void_p), ("grid_idx", C.c_void_p), ("encoding", C.c_void_p), ("encoding_dim", C.c_int32), ("reserved", C.c_int32),
+        ("n_rays", C.c_int64), ("n_pts", C.c_int64), ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("opacity_out", C.c_void_p), ("color_out", C.c_void_p), ("grad_opacity", C.c_void_p), ("grad_color", C.c_void_p),
+        ("grad_grid", C.c_void_p), ("grad_color_grid", C.c_void_p),
+        ("grad_grid_list", C.c_void_p * LP_MAX_GRIDS), ("grad_color_grid_list", C.c_void_p * LP_MAX_GRIDS),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p), ("grad_points", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -126,6 +140,7 @@ EXPORTS = (
     "lp_grid_tv_forward", "lp_grid_tv_backward", "lp_grid_tv_fused",  # (+ lp_grid_tv_workspace_bytes, which returns int64_t)
     "lp_grid_resample_forward", "lp_grid_resample_backward",
     "lp_scaffold_opacity", "lp_scaffold_build",  # (+ lp_scaffold_workspace_bytes, which returns int64_t)
+    "lp_points_forward", "lp_points_backward",
 )
 
 
@@ -210,10 +225,15 @@ def lib() -> C.CDLL:
     L.lp_scaffold_opacity.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p]
     L.lp_scaffold_build.restype = C.c_int
     L.lp_scaffold_build.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    # the decoder at arbitrary points: args, stream
+    for name in ("lp_points_forward", "lp_points_backward"):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(LpPointsArgs), C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
-    for which, st in enumerate((LpGrid, LpGridList, LpRays, LpMarch, LpMlp, LpRendererArgs, LpSplatterArgs,
-                                LpRayEmbedArgs, LpScaffoldArgs)):
+    for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
+                      (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs)):  # (selector 9 does not exist: lightplane_hip.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

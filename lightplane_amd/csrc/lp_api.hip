@@ -463,6 +463,100 @@ static int check_scaffold(const char* what, const LpScaffoldArgs* args, const fl
   return LP_OK;
 }
 
+// everything lp_points_forward / lp_points_backward share; fills the normalised copy.  `color`: the colour head takes part (forward:
+// color_out given; backward: grad_color given) -- only then are the colour MLP, the colour grid-list's data and the encoding looked at.
+static int check_points(const char* what, const LpPointsArgs* args, bool backward, LpPointsArgs& a) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_color != nullptr : args->color_out != nullptr;
+  if ((rc = check_grid_list_aligned("grid", args->grid))) return rc;
+  if ((rc = check_grid_list_aligned("color_grid", args->color_grid))) return rc;
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, opacity_out);
+  LP_ALIGNED(*args, color_out);
+  LP_ALIGNED(*args, grad_opacity);
+  LP_ALIGNED(*args, grad_color);
+  LP_ALIGNED(*args, grad_grid);
+  LP_ALIGNED(*args, grad_color_grid);
+  if ((rc = check_ptr_list_aligned("grad_grid_list", args->grad_grid_list))) return rc;
+  if ((rc = check_ptr_list_aligned("grad_color_grid_list", args->grad_color_grid_list))) return rc;
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  LP_ALIGNED(*args, grad_points);
+  if (args->n_rays < 0 || args->n_pts < 0)
+    return set_error(LP_EINVAL, "%s: n_rays %lld / n_pts %lld < 0", what, (long long)args->n_rays, (long long)args->n_pts);
+  if (args->n_pts > 0 && args->n_rays > (((int64_t)1 << 37) - 64) / args->n_pts)
+    return set_error(LP_EUNSUPPORTED, "%s: %lld x %lld points are more than 2^31 wavefronts", what, (long long)args->n_rays,
+                     (long long)args->n_pts);
+  if ((rc = check_grid_list("grid", args->grid, true))) return rc;
+  if ((rc = check_grid_list("color_grid", args->color_grid, false))) return rc;
+  const bool two = args->color_grid.n_grids > 0;
+  if (two) {
+    if (args->color_grid.channels != args->grid.channels || args->color_grid.grids[0].B != args->grid.grids[0].B)
+      return set_error(LP_EINVAL, "%s: color_grid must share batch size and channel count with grid", what);
+    if (args->trunk.n_layers != 0)
+      return set_error(LP_EINVAL, "%s: the trunk MLP has to have 0 layers with a separate colour grid-list", what);
+  }
+  if ((rc = check_mlp("trunk", args->trunk, true))) return rc;
+  if ((rc = check_mlp("opacity", args->opacity, false))) return rc;
+  if ((rc = check_mlp("color", args->color, !color))) return rc;
+  const int C = args->grid.channels;
+  int head_in = C;
+  if (args->trunk.n_layers > 0) {
+    if (args->trunk.dims[0] != C)
+      return set_error(LP_EINVAL, "%s: trunk MLP input width %d != grid channels %d", what, args->trunk.dims[0], C);
+    head_in = args->trunk.dims[args->trunk.n_layers];
+  }
+  if (args->opacity.dims[0] != head_in)
+    return set_error(LP_EINVAL, "%s: opacity MLP input width %d != %d", what, args->opacity.dims[0], head_in);
+  if (args->opacity.dims[args->opacity.n_layers] != 1)
+    return set_error(LP_EINVAL, "%s: opacity MLP must end in 1 output, got %d", what, args->opacity.dims[args->opacity.n_layers]);
+  if (args->trunk.offset != 0 || args->opacity.offset != mlp_numel(args->trunk))
+    return set_error(LP_EINVAL, "%s: MLP offsets do not follow the trunk|opacity|color flat layout", what);
+  int64_t need = args->opacity.offset + mlp_numel(args->opacity);
+  if (args->color.n_layers > 0) {
+    if (args->color.dims[0] != head_in)
+      return set_error(LP_EINVAL, "%s: colour MLP input width %d != %d", what, args->color.dims[0], head_in);
+    if (args->color.offset != need) return set_error(LP_EINVAL, "%s: MLP offsets do not follow the trunk|opacity|color flat layout", what);
+    need += mlp_numel(args->color);
+  }
+  if (color) {
+    if (args->color_chn < 1 || args->color_chn > args->color.dims[args->color.n_layers])
+      return set_error(LP_EINVAL, "%s: color_chn %d outside [1, %d]", what, args->color_chn, args->color.dims[args->color.n_layers]);
+    if (args->encoding_dim != head_in)
+      return set_error(LP_EINVAL, "%s: encoding_dim %d != the colour head's input width %d", what, args->encoding_dim, head_in);
+  }
+  if (need > args->n_mlp_params)
+    return set_error(LP_EINVAL, "%s: the MLPs take %lld floats, mlp_params has %lld", what, (long long)need, (long long)args->n_mlp_params);
+  if (args->scaffold) {
+    const LpGrid& s = args->scaffold_shape;
+    if (s.B != args->grid.grids[0].B || s.D < 1 || s.H < 1 || s.W < 1)
+      return set_error(LP_EINVAL, "%s: scaffold shape [%d,%d,%d,%d] incompatible with grid batch %d", what, s.B, s.D, s.H, s.W,
+                       args->grid.grids[0].B);
+  }
+  if (!args->mlp_params) return set_error(LP_ENULL, "%s: mlp_params is NULL", what);
+  if (args->n_rays > 0 && args->n_pts > 0) {  // (an empty batch has no tensors to point at)
+    if (!args->points || !args->grid_idx) return set_error(LP_ENULL, "%s: points / grid_idx is NULL", what);
+    if (color && !args->encoding) return set_error(LP_ENULL, "%s: encoding is NULL and the colour head is evaluated", what);
+    if (!backward && !args->opacity_out) return set_error(LP_ENULL, "%s: opacity_out is NULL", what);
+  }
+  a = *args;
+  if (!normalize_grid_list(a.grid)) return set_error(LP_ENULL, "%s: grid.data is NULL (and a grid has no pointer of its own)", what);
+  if (color && !normalize_grid_list(a.color_grid))
+    return set_error(LP_ENULL, "%s: color_grid.data is NULL (and a grid has no pointer of its own)", what);
+  if (backward) {
+    if ((rc = normalize_grad_list("grad_grid", a.grad_grid_list, a.grad_grid, a.grid.n_grids))) return rc;
+    if ((rc = normalize_grad_list("grad_color_grid", a.grad_color_grid_list, a.grad_color_grid, a.color_grid.n_grids))) return rc;
+    const int total = points_backward_total_width(a);
+    if (total > 1024) return set_error(LP_EUNSUPPORTED, "%s: sum of layer widths %d exceeds 1024", what, total);
+  }
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -474,14 +568,14 @@ int lp_version(void) { return LP_VERSION; }
 const char* lp_last_error(void) { return g_err; }
 
 const char* lp_build_info(void) {
-  static char info[4096];
+  static char info[8192];
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -499,6 +593,7 @@ int lp_abi_sizeof(int which) {
     case 6: return (int)sizeof(LpSplatterArgs);
     case 7: return (int)sizeof(LpRayEmbedArgs);
     case 8: return (int)sizeof(LpScaffoldArgs);
+    case 10: return (int)sizeof(LpPointsArgs);  // (9 stays unanswered: lightplane_hip.h)
     default: return -1;
   }
 }
@@ -856,6 +951,20 @@ int lp_grid_resample_backward(const LpGridList* grad_src, const LpGridList* grad
   const int rc = check_grid_resample("lp_grid_resample_backward", grad_src, grad_dst, align_corners, coeffs, s, d);
   if (rc) return rc;
   return grid_resample_launch(s, d, align_corners, coeffs, true, accumulate != 0, (hipStream_t)stream);
+}
+
+int lp_points_forward(const LpPointsArgs* args, void* stream) {
+  LpPointsArgs a;
+  const int rc = check_points("lp_points_forward", args, false, a);
+  if (rc) return rc;
+  return points_forward_launch(a, (hipStream_t)stream);
+}
+
+int lp_points_backward(const LpPointsArgs* args, void* stream) {
+  LpPointsArgs a;
+  const int rc = check_points("lp_points_backward", args, true, a);
+  if (rc) return rc;
+  return points_backward_launch(a, (hipStream_t)stream);
 }
 
 int64_t lp_scaffold_workspace_bytes(const LpScaffoldArgs* args) {

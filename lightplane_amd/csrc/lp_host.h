@@ -125,6 +125,11 @@ const char* build_info_grid_resample();
 int64_t scaffold_workspace_bytes(const LpGrid& shape, int dilate);
 int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool occupancy, hipStream_t stream);
 const char* build_info_scaffold();
+// the decoder at arbitrary points: lp_points.hip (`a` normalised and checked by lp_api.hip)
+int points_forward_launch(const LpPointsArgs& a, hipStream_t stream);
+int points_backward_launch(const LpPointsArgs& a, hipStream_t stream);
+int points_backward_total_width(const LpPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
+const char* build_info_points();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

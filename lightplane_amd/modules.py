@@ -29,6 +29,7 @@ from .rays import Rays, calc_harmonic_embedding, calc_harmonic_embedding_dim, ji
 import ctypes
 
 from . import _lib, config
+from .points import lightplane_eval_mlp as _fused_eval_mlp, lightplane_eval_mlp_opacity_only as _fused_eval_mlp_opacity_only
 from .renderer import _render, lightplane_renderer
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
@@ -101,6 +102,20 @@ def _fused_scaffold_supported(feature_grid, device) -> bool:
         return False
     return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
                and (dev.index is None or t.device.index == dev.index) for t in tensors)
+
+
+def _fused_points_supported(pts, feature_grid, color_feature_grid=None, scaffold=None, rays_encoding=None) -> bool:
+    # what lp_points_forward takes as it is: the rule of _fused_scaffold_supported for the grids, and fp32 points / scaffold / encoding
+    # on the same GPU (anything else keeps the Renderer path, whose front-end converts and copies)
+    if not (torch.is_tensor(pts) and pts.is_cuda and pts.dtype == torch.float32 and pts.ndim == 3):
+        return False
+    if not _fused_scaffold_supported(feature_grid, pts.device):
+        return False
+    if color_feature_grid is not None and not (type(color_feature_grid) is type(feature_grid)
+                                               and _fused_scaffold_supported(color_feature_grid, pts.device)):
+        return False
+    return all(t is None or (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == pts.device)
+               for t in (scaffold, rays_encoding))
 
 
 class LightplaneRenderer(torch.nn.Module):
@@ -239,7 +254,14 @@ class LightplaneRenderer(torch.nn.Module):
 
     def eval_opacity_at_points(self, pts, pts_to_grid_idx, feature_grid, scaffold=None, gain=None,
                                mask_out_of_bounds_samples=None, grid_sizes=None):
-        """Opacities ``[n_rays, n_pts]`` of the decoder at ``pts [n_rays, n_pts, 3]`` (reference :302-347)."""
+        """Opacities ``[n_rays, n_pts]`` of the decoder at ``pts [n_rays, n_pts, 3]`` (reference :302-347).  With
+        ``config.fused_module_ops`` and fp32 tensors on the GPU this is :func:`lightplane_amd.lightplane_eval_mlp_opacity_only`
+        (one kernel); otherwise a single-sample render."""
+        gain = if_not_none_else(gain, self.gain)
+        mask = if_not_none_else(mask_out_of_bounds_samples, self.mask_out_of_bounds_samples)
+        if config.fused_module_ops and _fused_points_supported(pts, feature_grid, None, scaffold):
+            return _fused_eval_mlp_opacity_only(pts, feature_grid, pts_to_grid_idx, self.get_decoder_params(), gain, mask,
+                                                scaffold=scaffold, grid_sizes=grid_sizes)
         out = self._render_points(
             pts, pts_to_grid_idx, feature_grid, None, scaffold, if_not_none_else(gain, self.gain),
             if_not_none_else(mask_out_of_bounds_samples, self.mask_out_of_bounds_samples), False, grid_sizes, None)
@@ -247,11 +269,16 @@ class LightplaneRenderer(torch.nn.Module):
 
     def eval_decoder_at_points(self, pts, pts_to_grid_idx, rays_encoding, feature_grid, color_feature_grid=None,
                                scaffold=None, gain=None, mask_out_of_bounds_samples=None, contract_coords=None,
-                               directions=None):
+                               directions=None, grid_sizes=None, color_grid_sizes=None):
         """(opacity ``[n_rays, n_pts]``, colour ``[n_rays, n_pts, color_chn]``) at ``pts`` (reference
         :183-241).
 
-        Implementation: two single-sample renders through the HIP Renderer (a ray with ``near = far = 0`` and one
+        With ``config.fused_module_ops`` and fp32 tensors on the GPU this is :func:`lightplane_amd.lightplane_eval_mlp`: one
+        evaluation of the decoder per point, opacity and colour differentiated jointly (also with respect to ``pts``), the
+        reference's colour ``sigmoid(raw)`` at empty points, and grids as a list or -- with ``grid_sizes`` /
+        ``color_grid_sizes`` -- as flat tensors.  Of the deviations below only the ``color_chn`` channels remain.
+
+        Otherwise (``config.fused_module_ops`` off, or tensors the fused kernels do not take as they are): two single-sample renders through the HIP Renderer (a ray with ``near = far = 0`` and one
         sample sits at its origin; the interval length of a single-sample march is 1, so ``-log T`` is the opacity;
         with gain 1e30 the compositing weight ``1 - exp(-x)`` is 1, so the rendered feature is the colour).
         Documented deviations from the reference's naive decoder:
@@ -271,6 +298,11 @@ class LightplaneRenderer(torch.nn.Module):
         enc = self._get_ray_encoding(rays_encoding, directions)
         mask = if_not_none_else(mask_out_of_bounds_samples, self.mask_out_of_bounds_samples)
         contract = if_not_none_else(contract_coords, self.contract_coords)
+        if config.fused_module_ops and _fused_points_supported(pts, feature_grid, color_feature_grid, scaffold, enc):
+            return _fused_eval_mlp(pts, feature_grid, pts_to_grid_idx, self.get_decoder_params(), enc, if_not_none_else(gain, self.gain),
+                                   mask, scaffold=scaffold, color_grid=color_feature_grid, contract_coords=contract,
+                                   grid_sizes=grid_sizes, color_grid_sizes=color_grid_sizes)
+        assert grid_sizes is None and color_grid_sizes is None, "the Renderer path of eval_decoder_at_points takes grids as lists"
         args = (pts, pts_to_grid_idx, feature_grid, color_feature_grid, scaffold)
         opacity = self._render_points(*args, if_not_none_else(gain, self.gain), mask, contract, None, enc)[1]
         color = self._render_points(*args, 1e30, mask, contract, None, enc)[2]
