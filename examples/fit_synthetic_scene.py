@@ -8,7 +8,7 @@ examples/fit_single_scene.py training loop (:282-334) as a convergence check, on
 GPU boxes have no datasets.
 
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
-                                            [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy]
+                                            [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -22,6 +22,13 @@ periodically (examples/fit_single_scene.py ``update_scaffold_step``): ``renderer
 -- one fused lattice kernel plus a byte dilation -- and every render from then on, held-out evaluation included, skips the samples
 the scaffold marks empty.  ``--scaffold-threshold`` is the opacity above which a lattice point counts as occupied (the module's default
 1e-7 keeps nearly everything).  Without ``--scaffold-steps`` no scaffold is built or passed.
+
+``--clip-rays`` clips every ray batch -- training and held-out -- to the span it can contribute on before the target and the student
+are rendered: ``renderer.clip_rays`` walks the rays through the scaffold's cells (one fused kernel, ``lp.clip_rays_to_scaffold``) and
+shrinks ``near`` / ``far`` to the occupied span, half a cell wider; before a scaffold exists the rays are clipped to the scene box.  Rays
+that cross no occupied cell stay in the batch and render background in both.  The sample count stays, so the sample density rises by
+``1 / mean_span_ratio``; the JSON line gains ``mean_span_ratio`` (mean of ``(far' - near') / (far - near)`` over the last training
+batch) and ``hit_fraction``.  Without the flag the run is bit for bit what it is without this option.
 
 ``--export-pointcloud FILE.npy`` writes the fitted scene as a point cloud after the fit: the occupancy scaffold of a
 ``--scaffold-size``^3 lattice at ``--scaffold-threshold`` (no dilation) picks the occupied lattice points, ``renderer.eval_decoder_at_points``
@@ -75,8 +82,10 @@ def random_rays(n, gen, dev):
                    near=near.to(dev), far=far.to(dev), encoding=None)
 
 
-def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None):
+def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None, clip_rays=False):
     rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
+    if clip_rays:
+        rays, _ = renderer.clip_rays(rays, scaffold)
     with torch.no_grad():
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         _, _, rgb = renderer(rays, list(grids), scaffold=scaffold)
@@ -85,7 +94,7 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None)
 
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
-        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None):
+        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False):
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -107,7 +116,7 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     losses, tvs, psnr_at_upsample = [], [], []
     for it in range(steps):
         if it in upsample_steps:
-            psnr_at_upsample.append(heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold))
+            psnr_at_upsample.append(heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold, clip_rays))
             new = lp.grid_up_sample([g.detach() for g in grids], upsample_factor=2.0)
             grids = torch.nn.ParameterList([torch.nn.Parameter(g) for g in new])
             opt = make_opt()  # new tensors: new optimiser state, as the reference example does
@@ -120,6 +129,9 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
             if verbose:
                 print(f"step {it:4d}  scaffold {tuple(scaffold.shape)}  occupied {occupancy[-1]:.3f}", flush=True)
         rays = random_rays(n_rays, gen, dev)
+        if clip_rays:
+            span = rays.far - rays.near
+            rays, hit = renderer.clip_rays(rays, scaffold)
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
@@ -133,7 +145,7 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         if verbose and (it % 50 == 0 or it == steps - 1):
             print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
     out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5,
-           "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold),
+           "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold, clip_rays),
            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
     if upsample_steps:
         out.update(upsample_steps=upsample_steps, start_res=start_res, psnr_at_upsample_db=psnr_at_upsample,
@@ -141,6 +153,8 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     if scaffold_steps:
         out.update(scaffold_steps=scaffold_steps, scaffold_shape=list(scaffold.shape) if scaffold is not None else None,
                    scaffold_threshold=scaffold_threshold, scaffold_occupancy=occupancy)
+    if clip_rays and steps > 0:
+        out.update(mean_span_ratio=float(((rays.far - rays.near) / span).mean()), hit_fraction=float(hit.float().mean()))
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
                    grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
@@ -180,11 +194,13 @@ def main(argv=None):
     ap.add_argument("--scaffold-threshold", type=float, default=1e-7, help="opacity above which a lattice point is occupied")
     ap.add_argument("--export-pointcloud", default=None, metavar="FILE.npy",
                     help="after the fit, write xyz | rgb | opacity of the occupied lattice points of a scaffold")
+    ap.add_argument("--clip-rays", action="store_true",
+                    help="clip every ray batch to the scaffold's occupied span (to the scene box before a scaffold exists)")
     ap.add_argument("--res", type=int, default=64, help="resolution of the planes")
     a = ap.parse_args(argv)
     out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
               upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
-              scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud)
+              scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays)
     print(json.dumps(out))
     return out
 

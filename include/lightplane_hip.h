@@ -100,7 +100,10 @@ extern "C" {
                                   has a "scaffold" entry; lp_abi_sizeof(8) answers for the new struct)
                                   and again (additive: a new struct and two new entry points): the decoder at arbitrary points,
                                   LpPointsArgs with lp_points_forward() / lp_points_backward() (lp_build_info() then has a "points"
-                                  entry; lp_abi_sizeof(10) answers for the new struct) */
+                                  entry; lp_abi_sizeof(10) answers for the new struct)
+                                  and again (additive: a new struct and one new entry point): rays clipped to the occupied span of a
+                                  scaffold, LpRayClipArgs with lp_rays_clip() (lp_build_info() then has a "ray_clip" entry;
+                                  lp_abi_sizeof(12) answers for the new struct) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -332,8 +335,9 @@ const char* lp_build_info(void);
 const char* lp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * which = 0 LpGrid, 1 LpGridList, 2 LpRays, 3 LpMarch, 4 LpMlp, 5 LpRendererArgs,
- * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs; anything else returns -1 -- 9 among them: the scaffold's
- * tests pin that answer as "the first selector that does not exist", so the point evaluation took the next one. */
+ * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs, 12 LpRayClipArgs; anything else returns -1 -- 9 and 11 among
+ * them: the scaffold's and the point evaluation's tests pin those answers as "the first selector that does not exist", so the next
+ * addition took the one after. */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the
@@ -561,6 +565,31 @@ typedef struct LpPointsArgs {
 } LpPointsArgs;
 int lp_points_forward(const LpPointsArgs* args, void* stream);
 int lp_points_backward(const LpPointsArgs* args, void* stream);
+
+/* Rays clipped to the occupied span of a scaffold (lp_ray_clip.hip).  The Renderer reads a scaffold with nearest-neighbour,
+ * align_corners = False indexing: scene b is tiled by W x H x D axis-aligned boxes, cell i along x covering
+ * [-1 + 2 i / W, -1 + 2 (i + 1) / W], and a cell is occupied iff its value != 0.  For ray r (any direction length; a zero component is
+ * legal) the kernel intersects [near, far] with the box [-1, 1]^3 (slab test), walks the cells the ray crosses (3-D DDA, one lane per
+ * ray) forward to the first occupied cell (near*) and backward from the far end to the last (far*), and writes
+ *   near_out[r] = max(near, near* - pad_t - e),  far_out[r] = min(far, far* + pad_t + e),  hit_out[r] = 1
+ * with pad_t = pad * h / |d|, h = 2 / max(D, H, W), and e >= 0 the kernel's bound on the fp32 rounding of the crossing it stopped at
+ * (14 * 2^-24 * (1 + |o_a|) / |d_a| for a crossing of axis a): no sample of the Renderer on [near, far] outside
+ * [near_out, far_out] has a non-zero scaffold value.  A ray without an occupied cell on [near, far] -- also one with far < near, a NaN
+ * or Inf entry, or grid_idx outside [0, B) -- is a miss: hit_out[r] = 0 and near_out / far_out carry near / far bit for bit.
+ * scaffold == NULL: the box alone (one occupied cell, h = 2; scaffold_shape is ignored, any grid_idx >= 0 is in range).
+ * rays.encoding, encoding_dim and row_length are ignored.  near_out / far_out may be rays.near_t / rays.far_t (a lane reads its
+ * values before it writes).  No atomics, no workspace, no host synchronisation: graph-capturable and bit-reproducible.
+ * Every device pointer except hit_out (bytes) is 16-byte aligned (Conventions).  Before anything touches the device: LP_ENULL for
+ * NULL args / results or, with n_rays > 0, a NULL ray field; LP_EINVAL for an under-aligned pointer, n_rays < 0, a pad that is
+ * negative or not finite, or (with a scaffold) a shape with an extent < 1.  n_rays == 0 succeeds without a launch. */
+typedef struct LpRayClipArgs {
+  LpRays rays;             /* directions, origins, grid_idx, near_t, far_t */
+  const float* scaffold;   /* NULL or [B, D, H, W] occupancy (!= 0: occupied) */
+  LpGrid scaffold_shape;   /* B, D, H, W of the scaffold (row_offset and data ignored) */
+  float pad;               /* margin in cells of the finest axis, >= 0 */
+  int32_t reserved;        /* 0 */
+} LpRayClipArgs;
+int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

@@ -125,6 +125,10 @@ class LpPointsArgs(C.Structure):
     ]
 
 
+class LpRayClipArgs(C.Structure):
+    _fields_ = [("rays", LpRays), ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid), ("pad", C.c_float), ("reserved", C.c_int32)]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -141,6 +145,7 @@ EXPORTS = (
     "lp_grid_resample_forward", "lp_grid_resample_backward",
     "lp_scaffold_opacity", "lp_scaffold_build",  # (+ lp_scaffold_workspace_bytes, which returns int64_t)
     "lp_points_forward", "lp_points_backward",
+    "lp_rays_clip",
 )
 
 
@@ -230,10 +235,13 @@ def lib() -> C.CDLL:
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(LpPointsArgs), C.c_void_p]
+    # rays clipped to the occupied span of a scaffold: args, near_out, far_out, hit_out, stream
+    L.lp_rays_clip.restype = C.c_int
+    L.lp_rays_clip.argtypes = [C.POINTER(LpRayClipArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
-                      (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs)):  # (selector 9 does not exist: lightplane_hip.h)
+                      (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs)):  # (selectors 9 and 11 do not exist: lightplane_hip.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

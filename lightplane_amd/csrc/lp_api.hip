@@ -557,6 +557,31 @@ static int check_points(const char* what, const LpPointsArgs* args, bool backwar
   return LP_OK;
 }
 
+// everything lp_rays_clip checks
+static int check_ray_clip(const LpRayClipArgs* args, const float* near_out, const float* far_out, const uint8_t* hit_out) {
+  if (!args) return set_error(LP_ENULL, "lp_rays_clip: args is NULL");
+  const LpRays& r = args->rays;
+  if (r.n_rays < 0) return set_error(LP_EINVAL, "lp_rays_clip: n_rays %lld < 0", (long long)r.n_rays);
+  const struct { const char* field; const void* p; } ptrs[] = {
+      {"rays.directions", r.directions}, {"rays.origins", r.origins}, {"rays.grid_idx", r.grid_idx}, {"rays.near_t", r.near_t},
+      {"rays.far_t", r.far_t},           {"scaffold", args->scaffold}, {"near_out", near_out},       {"far_out", far_out}};
+  for (const auto& f : ptrs)
+    if (int rc = check_aligned(f.field, f.p)) return rc;
+  if (!(args->pad >= 0.0f) || args->pad > 3.4028234663852886e38f)
+    return set_error(LP_EINVAL, "lp_rays_clip: pad = %g, has to be >= 0 and finite", (double)args->pad);
+  if (args->scaffold) {
+    const LpGrid& s = args->scaffold_shape;
+    if (s.B < 1 || s.D < 1 || s.H < 1 || s.W < 1)
+      return set_error(LP_EINVAL, "lp_rays_clip: scaffold shape [%d,%d,%d,%d] has an extent < 1", s.B, s.D, s.H, s.W);
+    if ((int64_t)s.D + s.H + s.W >= ((int64_t)1 << 30))
+      return set_error(LP_EUNSUPPORTED, "lp_rays_clip: scaffold shape [%d,%d,%d,%d]: D + H + W has to stay below 2^30", s.B, s.D, s.H, s.W);
+  }
+  if (!near_out || !far_out || !hit_out) return set_error(LP_ENULL, "lp_rays_clip: near_out / far_out / hit_out must be non-NULL");
+  if (r.n_rays > 0 && (!r.directions || !r.origins || !r.grid_idx || !r.near_t || !r.far_t))
+    return set_error(LP_ENULL, "lp_rays_clip: rays: directions/origins/grid_idx/near/far must be non-NULL");
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -572,10 +597,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"ray_clip\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), build_info_ray_clip(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -594,6 +619,7 @@ int lp_abi_sizeof(int which) {
     case 7: return (int)sizeof(LpRayEmbedArgs);
     case 8: return (int)sizeof(LpScaffoldArgs);
     case 10: return (int)sizeof(LpPointsArgs);  // (9 stays unanswered: lightplane_hip.h)
+    case 12: return (int)sizeof(LpRayClipArgs);  // (and so does 11)
     default: return -1;
   }
 }
@@ -965,6 +991,13 @@ int lp_points_backward(const LpPointsArgs* args, void* stream) {
   const int rc = check_points("lp_points_backward", args, true, a);
   if (rc) return rc;
   return points_backward_launch(a, (hipStream_t)stream);
+}
+
+int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream) {
+  const int rc = check_ray_clip(args, near_out, far_out, hit_out);
+  if (rc) return rc;
+  if (args->rays.n_rays == 0) return LP_OK;
+  return rays_clip_launch(*args, near_out, far_out, hit_out, (hipStream_t)stream);
 }
 
 int64_t lp_scaffold_workspace_bytes(const LpScaffoldArgs* args) {

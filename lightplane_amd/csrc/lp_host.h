@@ -130,6 +130,9 @@ int points_forward_launch(const LpPointsArgs& a, hipStream_t stream);
 int points_backward_launch(const LpPointsArgs& a, hipStream_t stream);
 int points_backward_total_width(const LpPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
 const char* build_info_points();
+// rays clipped to the occupied span of a scaffold: lp_ray_clip.hip (`a` checked by lp_api.hip; n_rays > 0)
+int rays_clip_launch(const LpRayClipArgs& a, float* near_out, float* far_out, uint8_t* hit_out, hipStream_t stream);
+const char* build_info_ray_clip();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -31,6 +31,7 @@ import ctypes
 from . import _lib, config
 from .points import lightplane_eval_mlp as _fused_eval_mlp, lightplane_eval_mlp_opacity_only as _fused_eval_mlp_opacity_only
 from .renderer import _render, lightplane_renderer
+from .ray_clip import clip_rays_to_scaffold as _clip_rays_to_scaffold
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
 
@@ -334,6 +335,19 @@ class LightplaneRenderer(torch.nn.Module):
             ks = dilate_scaffold * 2 + 1
             scaffold = torch.nn.functional.max_pool3d(scaffold, kernel_size=ks, padding=dilate_scaffold, stride=1)
         return (scaffold > threshold) * 1.0
+
+    @torch.no_grad()
+    def clip_rays(self, rays: Rays, scaffold=None, pad: float = 0.5):
+        """``(clipped rays, hit)`` of :func:`lightplane_amd.clip_rays_to_scaffold`: ``rays`` with ``near`` / ``far`` shrunk to the span
+        of the scaffold's occupied cells each ray crosses (``scaffold=None``: of the scene box), ``pad`` cells wider, and a bool ``[R]``
+        tensor that is False for the rays that cross none (they keep their span and render background).  Render the result with
+        proportionally fewer samples for the same sample density, or with as many for a higher one; with ``num_samples_inf > 0`` the
+        beyond-far samples start at the new ``far``.  Contracted coordinates bend the rays, which a straight walk does not follow: a
+        module with ``contract_coords=True`` raises."""
+        if self.contract_coords:
+            raise NotImplementedError("clip_rays walks straight rays through the scaffold's cells; with contract_coords=True the "
+                                      "Renderer bends them (MeRF contraction), so the clipped span would be wrong")
+        return _clip_rays_to_scaffold(rays, scaffold, pad=pad)
 
     # -- ray encoding ---------------------------------------------------------------------
     def _get_ray_embedding(self, ray_directions: torch.Tensor) -> torch.Tensor:
