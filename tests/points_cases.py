@@ -38,6 +38,9 @@ CASES = {
     "triplane_c16_222x128": ("triplane", (2, 6, 5, 7, 16), (2, 2, 2, 128), (3, 70), "list", False, False, None),
     "triplane_c16_222x32_one_point": ("triplane", (2, 6, 5, 7, 16), (2, 2, 2, 32), (1, 1), "list", False, False, None),
     "voxel_c16_112x32_one_wave": ("voxel", (1, 4, 3, 5, 16), (1, 1, 2, 32), (1, 64), "list", False, False, None),
+    # ragged widths (tests/ragged_cases.py): scalar grid rows and layers narrower than a block of eight; full blocks and one output
+    "voxel_c5_222x7_mask": ("voxel", (2, 4, 3, 5, 5), (2, 2, 2, 7), (7, 37), "list", False, True, None),
+    "triplane_c20_222x33_scaffold": ("triplane", (1, 6, 5, 7, 20), (2, 2, 2, 33), (7, 37), "flat", False, False, (1, 5, 4, 6)),
 }
 SEEDS = {name: 300 + i for i, name in enumerate(CASES)}
 _CACHE = {}

@@ -82,7 +82,8 @@ def test_module_splatter_matches_reference_module(golden_dir):
     _assert_close("grad_encoding", r.encoding.grad, z["grad_encoding"])
 
 
-@pytest.mark.parametrize("n_h,e,n", [(3, 32, 1000), (0, 16, 257), (10, 64, 33), (2, 20, 5)])
+# (the last four: tests/ragged_cases.py EMBEDDING_CASES -- widths that are no multiple of 4, the narrowest one, the largest LDS tile)
+@pytest.mark.parametrize("n_h,e,n", [(3, 32, 1000), (0, 16, 257), (10, 64, 33), (2, 20, 5), (3, 3, 257), (1, 1, 5), (0, 33, 64), (10, 85, 300)])
 def test_ray_embedding_kernel_matches_torch_ops(n_h, e, n):
     """lp_ray_embedding_{forward,backward} == Linear(calc_harmonic_embedding(normalize(d))) and its autograd gradients."""
     dev = _dev()

@@ -48,6 +48,9 @@ CASES = {
     "triplane_c16_44x64_r3": ((2, 9, 1, 5), "triplane", (2, 6, 5, 7, 16), (4, 4, 64), 3, True, "list"),
     "mixed_c32_11x64_r0_flat": ((2, 6, 5, 7), "mixed", (2, 3, 4, 5, 32), (1, 1, 64), 0, True, "flat"),
     "voxel_c16_22x128_r1": ((1, 3, 2, 70), "voxel", (1, 4, 3, 5, 16), (2, 2, 128), 1, False, "list"),  # the widest layers: 64 KB of LDS
+    # ragged widths (tests/ragged_cases.py; the names sort after every other one: the seeds of the rows above depend on the sorted order)
+    "width7_voxel_c5_22_r1": ((2, 6, 5, 7), "voxel", (2, 4, 3, 5, 5), (2, 2, 7), 1, True, "list"),
+    "width33_triplane_c20_22_r3": ((1, 3, 2, 70), "triplane", (1, 6, 5, 7, 20), (2, 2, 33), 3, False, "flat"),
 }
 GAIN = 1.7
 _CACHE = {}
