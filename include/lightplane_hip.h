@@ -103,7 +103,11 @@ extern "C" {
                                   entry; lp_abi_sizeof(10) answers for the new struct)
                                   and again (additive: a new struct and one new entry point): rays clipped to the occupied span of a
                                   scaffold, LpRayClipArgs with lp_rays_clip() (lp_build_info() then has a "ray_clip" entry;
-                                  lp_abi_sizeof(12) answers for the new struct) */
+                                  lp_abi_sizeof(12) answers for the new struct)
+                                  and again (additive: a new struct and four new entry points): gather and splat of a grid-list at
+                                  arbitrary points, LpPointGridArgs with lp_point_gather() / lp_point_splat() / lp_point_normalize() /
+                                  lp_point_grad_points() (lp_build_info() then has a "point_grid" entry; lp_abi_sizeof(14) answers
+                                  for the new struct) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -335,9 +339,9 @@ const char* lp_build_info(void);
 const char* lp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * which = 0 LpGrid, 1 LpGridList, 2 LpRays, 3 LpMarch, 4 LpMlp, 5 LpRendererArgs,
- * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs, 12 LpRayClipArgs; anything else returns -1 -- 9 and 11 among
- * them: the scaffold's and the point evaluation's tests pin those answers as "the first selector that does not exist", so the next
- * addition took the one after. */
+ * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs, 12 LpRayClipArgs, 14 LpPointGridArgs; anything else returns
+ * -1 -- 9, 11 and 13 among them: the scaffold's, the point evaluation's and the ray clip's tests pin those answers as "the first
+ * selector that does not exist", so the next addition took the one after. */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the
@@ -590,6 +594,56 @@ typedef struct LpRayClipArgs {
   int32_t reserved;        /* 0 */
 } LpRayClipArgs;
 int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream);
+
+/* Gather and splat of a grid-list at arbitrary 3-D points, without a decoder (lp_point_grid.hip; an extension: the counterpart at
+ * points of the Renderer's gather and the Splatter's scatter along rays).  For the grid-list G (C channels), points P [n_rays, n_pts, 3],
+ * per-point vectors U [n_rays, n_pts, C], q = p or, with contract_coords, the Renderer's contraction of p, and batch element
+ * b = grid_idx[r] (clamped to the grid-list's batch) for every point of row r, the four entry points are the partial derivatives of
+ *   B(G, P, U) = sum over points, grids g and corners k of  w_k(q) <G_g[row_k(q)], U[point]>
+ * with row_k / w_k the Renderer's corner rows and tri- / bi-linear weights (align_corners off, zero padding: a corner outside its grid
+ * contributes nothing; with mask_out_of_bounds a point outside [-1, 1]^3 -- after the contraction -- contributes nothing at all):
+ *   lp_point_gather:      out_features[r, n, :] = dB/dU = sum_g sum_k w_k G_g[row_k]  (WRITTEN; no atomics: bit-reproducible).  With
+ *                         row_weight[g] != NULL a row of grid g is divided by max(row_weight[g][row_k], 1e-5) as it is read.  A
+ *                         sub-group of C / 4 lanes per point moves whole rows 16 bytes per lane where C % 4 == 0; one lane per point
+ *                         and float by float otherwise.  `vectors` is ignored.
+ *   lp_point_splat:       dB/dG: vectors[r, n, :] * w_k is ADDED atomically to row row_k of every grid -- the memory `grid` describes is
+ *                         accumulated into (the struct's pointers are const for the readers) and zeroed by the caller.  Lanes =
+ *                         channels: one atomic instruction writes 64 / CW whole rows, CW = 16 / 32 / 64 lanes per row; channels
+ *                         64 .. 127 take a second pass.  With row_weight[g] != NULL for EVERY grid, w_k is also added to
+ *                         row_weight[g][row_k] (the Splatter's weight grid; zeroed by the caller).
+ *   lp_point_normalize:   the epilogue of lp_point_splat with the same arguments: grid g row i /= max(row_weight[g][i], 1e-5) for every
+ *                         row of every grid, in place, one pass (the Splatter's epilogue; true division).  row_weight is required for
+ *                         every grid; the point, vector and result pointers are not looked at.
+ *   lp_point_grad_points: grad_points[r, n, :] = dB/dP = J^T sum_g sum_k (d w_k / d q) <G_g[row_k], vectors[r, n]>  (WRITTEN, one lane
+ *                         per point, no atomics), J the Jacobian of the contraction, as lp_points_backward forms grad_points; the mask is
+ *                         piecewise constant and contributes nothing.  row_weight is ignored.
+ * row_weight[g] indexes rows as grids[g] does: entry i belongs to row i of the tensor that holds grid g (its own allocation, or the
+ * flat tensor -- then every entry may be one [n_rows] buffer).  Rows are 64-bit: grid-lists beyond 4 GB index correctly.
+ * 1 .. LP_MAX_GRIDS grids, 1 .. LP_MAX_WIDTH channels.  No workspace, no allocation, no host synchronisation: graph-capturable.
+ * Every device pointer is 16-byte aligned (Conventions).  Before anything touches the device: LP_ENULL for NULL args, a grid without
+ * data, a NULL points / grid_idx / vectors / result the call uses (with n_rays * n_pts > 0), or (normalize) a grid without row_weight;
+ * LP_EINVAL for negative n_rays / n_pts, a malformed grid-list, channels != grid.channels, row_weight for some grids only (splat), an
+ * under-aligned pointer;
+ * LP_EUNSUPPORTED for channels outside [1, LP_MAX_WIDTH] or more than 2^31 x 64 points.  n_rays * n_pts == 0 returns LP_OK without
+ * a launch (lp_point_normalize too: a splat of no points added nothing, and a zero row divided by the clamp stays zero). */
+typedef struct LpPointGridArgs {
+  LpGridList grid;                 /* read (gather, grad_points), accumulated into (splat), divided in place (normalize) */
+  float* row_weight[LP_MAX_GRIDS]; /* per-grid [rows] fp32 or NULL: read (gather, normalize), accumulated into (splat) */
+  const float* points;             /* [n_rays, n_pts, 3] */
+  const int32_t* grid_idx;         /* [n_rays] batch element of each row's points, as LpRays.grid_idx */
+  int64_t n_rays, n_pts;
+  const float* vectors;            /* U [n_rays, n_pts, C]: the features to splat / the upstream gradient of the gather */
+  float* out_features;             /* gather: [n_rays, n_pts, C] (written) */
+  float* grad_points;              /* grad_points: [n_rays, n_pts, 3] (written) */
+  int32_t channels;                /* C of vectors / out_features as the caller laid them out: has to equal grid.channels */
+  int32_t mask_out_of_bounds;
+  int32_t contract_coords;
+  int32_t reserved;                /* 0 */
+} LpPointGridArgs;
+int lp_point_gather(const LpPointGridArgs* args, void* stream);
+int lp_point_splat(const LpPointGridArgs* args, void* stream);
+int lp_point_normalize(const LpPointGridArgs* args, void* stream);
+int lp_point_grad_points(const LpPointGridArgs* args, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

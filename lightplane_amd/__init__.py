@@ -31,6 +31,7 @@ from .resample import grid_resample, grid_up_sample, resampled_sizes  # noqa: E4
 from .scaffold import calculate_scaffold, scaffold_opacity, scaffold_workspace_bytes  # noqa: E402
 from .points import lightplane_eval_mlp, lightplane_eval_mlp_opacity_only  # noqa: E402
 from .ray_clip import clip_rays_to_scaffold  # noqa: E402
+from .point_grid import sample_grid_at_points, splat_points  # noqa: E402
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -55,6 +56,7 @@ __all__ = [
     "calculate_scaffold", "scaffold_opacity", "scaffold_workspace_bytes",
     "lightplane_eval_mlp", "lightplane_eval_mlp_opacity_only",
     "clip_rays_to_scaffold",
+    "sample_grid_at_points", "splat_points",
 ]
 
 _NOT_PROVIDED = {

@@ -129,6 +129,14 @@ class LpRayClipArgs(C.Structure):
     _fields_ = [("rays", LpRays), ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid), ("pad", C.c_float), ("reserved", C.c_int32)]
 
 
+class LpPointGridArgs(C.Structure):
+    _fields_ = [
+        ("grid", LpGridList), ("row_weight", C.c_void_p * LP_MAX_GRIDS), ("points", C.c_void_p), ("grid_idx", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_pts", C.c_int64), ("vectors", C.c_void_p), ("out_features", C.c_void_p), ("grad_points", C.c_void_p),
+        ("channels", C.c_int32), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -146,6 +154,7 @@ EXPORTS = (
     "lp_scaffold_opacity", "lp_scaffold_build",  # (+ lp_scaffold_workspace_bytes, which returns int64_t)
     "lp_points_forward", "lp_points_backward",
     "lp_rays_clip",
+    "lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points",
 )
 
 
@@ -238,10 +247,16 @@ def lib() -> C.CDLL:
     # rays clipped to the occupied span of a scaffold: args, near_out, far_out, hit_out, stream
     L.lp_rays_clip.restype = C.c_int
     L.lp_rays_clip.argtypes = [C.POINTER(LpRayClipArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # gather / splat of a grid-list at arbitrary points: args, stream
+    for name in ("lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points"):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(LpPointGridArgs), C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
-                      (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs)):  # (selectors 9 and 11 do not exist: lightplane_hip.h)
+                      (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
+                      (14, LpPointGridArgs)):  # (selectors 9, 11 and 13 do not exist: lightplane_hip.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

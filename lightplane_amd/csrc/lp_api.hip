@@ -557,6 +557,43 @@ static int check_points(const char* what, const LpPointsArgs* args, bool backwar
   return LP_OK;
 }
 
+// everything the four lp_point_* entry points check; fills the normalised copy.  mode: 0 gather, 1 splat, 2 normalize, 3 grad_points
+static int check_point_grid(const char* what, const LpPointGridArgs* args, int mode, LpPointGridArgs& a) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  if ((rc = check_grid_list_aligned("grid", args->grid))) return rc;
+  if ((rc = check_ptr_list_aligned("row_weight", args->row_weight))) return rc;
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, vectors);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_points);
+  if (args->n_rays < 0 || args->n_pts < 0)
+    return set_error(LP_EINVAL, "%s: n_rays %lld / n_pts %lld < 0", what, (long long)args->n_rays, (long long)args->n_pts);
+  if (args->n_pts > 0 && args->n_rays > (((int64_t)1 << 37) - 64) / args->n_pts)
+    return set_error(LP_EUNSUPPORTED, "%s: %lld x %lld points are more than 2^31 wavefronts", what, (long long)args->n_rays,
+                     (long long)args->n_pts);
+  if ((rc = check_grid_list("grid", args->grid, true))) return rc;
+  if (args->channels != args->grid.channels)
+    return set_error(LP_EINVAL, "%s: channels %d of the per-point vectors != grid channels %d", what, args->channels, args->grid.channels);
+  int have = 0;
+  for (int g = 0; g < args->grid.n_grids; ++g) have += args->row_weight[g] != nullptr;
+  if (mode == 1 && have != 0 && have != args->grid.n_grids)
+    return set_error(LP_EINVAL, "%s: row_weight given for %d of %d grids (all or none)", what, have, args->grid.n_grids);
+  if (mode == 2 && have != args->grid.n_grids)
+    return set_error(LP_ENULL, "%s: row_weight is NULL for %d of %d grids", what, args->grid.n_grids - have, args->grid.n_grids);
+  if (mode != 2 && args->n_rays > 0 && args->n_pts > 0) {  // (an empty batch has no tensors to point at)
+    if (!args->points || !args->grid_idx) return set_error(LP_ENULL, "%s: points / grid_idx is NULL", what);
+    if (mode == 0 && !args->out_features) return set_error(LP_ENULL, "%s: out_features is NULL", what);
+    if (mode != 0 && !args->vectors) return set_error(LP_ENULL, "%s: vectors is NULL", what);
+    if (mode == 3 && !args->grad_points) return set_error(LP_ENULL, "%s: grad_points is NULL", what);
+  }
+  a = *args;
+  if (!normalize_grid_list(a.grid)) return set_error(LP_ENULL, "%s: grid.data is NULL (and a grid has no pointer of its own)", what);
+  for (int g = a.grid.n_grids; g < LP_MAX_GRIDS; ++g) a.row_weight[g] = nullptr;
+  return LP_OK;
+}
+
 // everything lp_rays_clip checks
 static int check_ray_clip(const LpRayClipArgs* args, const float* near_out, const float* far_out, const uint8_t* hit_out) {
   if (!args) return set_error(LP_ENULL, "lp_rays_clip: args is NULL");
@@ -597,10 +634,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"ray_clip\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"ray_clip\": %s, \"point_grid\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), build_info_ray_clip(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), build_info_ray_clip(), build_info_point_grid(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -620,6 +657,7 @@ int lp_abi_sizeof(int which) {
     case 8: return (int)sizeof(LpScaffoldArgs);
     case 10: return (int)sizeof(LpPointsArgs);  // (9 stays unanswered: lightplane_hip.h)
     case 12: return (int)sizeof(LpRayClipArgs);  // (and so does 11)
+    case 14: return (int)sizeof(LpPointGridArgs);  // (and 13)
     default: return -1;
   }
 }
@@ -991,6 +1029,34 @@ int lp_points_backward(const LpPointsArgs* args, void* stream) {
   const int rc = check_points("lp_points_backward", args, true, a);
   if (rc) return rc;
   return points_backward_launch(a, (hipStream_t)stream);
+}
+
+int lp_point_gather(const LpPointGridArgs* args, void* stream) {
+  LpPointGridArgs a;
+  const int rc = check_point_grid("lp_point_gather", args, 0, a);
+  if (rc != LP_OK) return rc;
+  return point_gather_launch(a, (hipStream_t)stream);
+}
+
+int lp_point_splat(const LpPointGridArgs* args, void* stream) {
+  LpPointGridArgs a;
+  const int rc = check_point_grid("lp_point_splat", args, 1, a);
+  if (rc != LP_OK) return rc;
+  return point_splat_launch(a, (hipStream_t)stream);
+}
+
+int lp_point_normalize(const LpPointGridArgs* args, void* stream) {
+  LpPointGridArgs a;
+  const int rc = check_point_grid("lp_point_normalize", args, 2, a);
+  if (rc != LP_OK) return rc;
+  return point_normalize_launch(a, (hipStream_t)stream);
+}
+
+int lp_point_grad_points(const LpPointGridArgs* args, void* stream) {
+  LpPointGridArgs a;
+  const int rc = check_point_grid("lp_point_grad_points", args, 3, a);
+  if (rc != LP_OK) return rc;
+  return point_grad_points_launch(a, (hipStream_t)stream);
 }
 
 int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream) {

@@ -133,6 +133,12 @@ const char* build_info_points();
 // rays clipped to the occupied span of a scaffold: lp_ray_clip.hip (`a` checked by lp_api.hip; n_rays > 0)
 int rays_clip_launch(const LpRayClipArgs& a, float* near_out, float* far_out, uint8_t* hit_out, hipStream_t stream);
 const char* build_info_ray_clip();
+// gather / splat of a grid-list at arbitrary points: lp_point_grid.hip (`a` normalised and checked by lp_api.hip)
+int point_gather_launch(const LpPointGridArgs& a, hipStream_t stream);
+int point_splat_launch(const LpPointGridArgs& a, hipStream_t stream);
+int point_normalize_launch(const LpPointGridArgs& a, hipStream_t stream);
+int point_grad_points_launch(const LpPointGridArgs& a, hipStream_t stream);
+const char* build_info_point_grid();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 
