@@ -118,7 +118,10 @@ extern "C" {
  * subtractions.  Every checkpoint is a float PAIR (hi, lo): -log T is accumulated as an unevaluated sum so
  * that the backward's subtraction of the same products recovers the intermediate values exactly.
  * One more pair per ray closes the list: (index of the last sample the forward marched, low word of
- * the final -log T) -- the backward starts there (see stop_neg_log_t).
+ * the final -log T) -- the backward starts there (see stop_neg_log_t).  The forward writes every pair of a ray up to the one of
+ * that sample and the closing pair; with early termination the pairs of checkpoints BEHIND the last marched sample are not
+ * written, and the backward never reads them (it takes no sample behind that index).  Without early termination every pair of
+ * every ray is written.
  * O(N) memory: 2 * (ceil(S/LP_NLT_CKPT) + S_inf + 1) floats per ray. */
 #define LP_NLT_CKPT 32
 /* samples per state record of the segment-parallel march of a small batch (LpRendererArgs.seg_prefix); a workgroup marches one or more
@@ -378,7 +381,10 @@ int lp_renderer_backward(const LpRendererArgs* args, void* stream);
  *     for it): 0/3/3 x 64 still fits whole and reports 3 (four-wave resident kernel), 0/4/4 x 64 reports 4 (its last layers pass
  *     through the ring) although its 20 block images alone would fit the LDS.
  *   lp_renderer_forward_workspace_bytes: 0 unless the family is 4; then the bytes of the streamed layers' pre-split block images,
- *     back to back, no header (per layer ceil(rows_in / 32) * ceil(cols / 32) * 6528).  Depends on shapes only.
+ *     back to back, no header (per layer ceil(rows_in / 32) * ceil(cols / 32) * 6528).  Depends on shapes only.  A block image is
+ *     three limbs of 2176 bytes in the LDS layout: 32 rows of 64 bytes, every group of four rows 16 bytes further on; the 8 x 16
+ *     bytes of that skew are padding -- the packing pass does not write them, and nothing that is computed reads them (the copy into
+ *     LDS carries them along).
  *   lp_renderer_forward_ws: packs the images into `workspace` (device memory, 16-byte aligned, at least that many bytes; owned by the
  *     caller, free to reuse once the call's work on `stream` is done) and runs the forward on `stream`.  LP_EINVAL, before any launch, when
  *     the family is 4 and the workspace is NULL, short or misaligned. */
@@ -413,7 +419,9 @@ int lp_ray_embedding_backward(const LpRayEmbedArgs* args, void* stream);
  *   lp_grid_tv_workspace_bytes: bytes of device workspace the loss needs for this list (one fp64 partial per workgroup of the sweep;
  *     shapes only, no device; never decreases when an extent grows), or a negative LP_E* code for a malformed list.
  *   lp_grid_tv_forward:  *loss (device, fp32) = loss.  `workspace`: device memory, 8-byte aligned, >= that many bytes, free to reuse
- *     once the call's work on `stream` is done.
+ *     once the call's work on `stream` is done.  It is scratch: the call writes one partial per workgroup it launches, from the
+ *     start of the buffer, and reads back exactly those; the query sizes for the float-by-float sweep, so with 16-byte rows the tail
+ *     of the buffer is neither written nor read.  The contents before the call do not matter.
  *   lp_grid_tv_backward: gradient = scale * (*grad_loss) * d loss / d grid, computed per element from its six neighbours and written
  *     (accumulate == 0) or added to what the buffer holds (accumulate != 0).  grad_loss: DEVICE scalar (the upstream gradient; NULL =
  *     1).  Where the gradient goes: `grad_list` -- a HOST array of n_grad_list == n_grids device pointers, entry g shaped like the
