@@ -240,6 +240,29 @@ class relu_mask_forcer:
         return x * m.to(x.dtype)
 
 
+_VALUE_RECORDER = None
+
+
+class value_recorder:
+    """Test diagnostics (no effect on any result): while active, the Renderer oracle and ``eval_decoder`` leave the values the
+    compositing arithmetic sees -- ``raw_o`` (the opacity head's output, before the injected noise), ``softplus_in`` (with it: the
+    argument of the softplus), ``raw_c`` (the argument of the sigmoid, every column of the last colour layer) and ``nlt`` (``[R, S + 1]``:
+    -log T before the first sample and after every sample) -- detached, of the last evaluation.  tests/value_regime_cases.py reads
+    which branch of the kernels' ``softplus_f`` / ``__expf`` / ``sigmoid_f`` a scene reaches from them."""
+
+    def __init__(self):
+        self.raw_o = self.softplus_in = self.raw_c = self.nlt = None
+
+    def __enter__(self):
+        global _VALUE_RECORDER
+        self._prev, _VALUE_RECORDER = _VALUE_RECORDER, self
+        return self
+
+    def __exit__(self, *exc):
+        global _VALUE_RECORDER
+        _VALUE_RECORDER = self._prev
+
+
 def _relu(x):
     if _RELU_RECORDER is not None:
         _RELU_RECORDER.update(x)
@@ -480,8 +503,12 @@ def eval_decoder(points, grids, grid_idx, decoder_params, rays_encoding, gain,
         color_raw = mlp_forward(_relu(cfeat) + rays_encoding[:, None], wc, bc)
     assert opacity_raw.shape[-1] == 1
     opacity_raw = opacity_raw[..., 0]
+    if _VALUE_RECORDER is not None:
+        _VALUE_RECORDER.raw_o, _VALUE_RECORDER.raw_c = opacity_raw.detach(), color_raw.detach()
     if noise is not None:
         opacity_raw = opacity_raw + noise
+    if _VALUE_RECORDER is not None:
+        _VALUE_RECORDER.softplus_in = opacity_raw.detach()
     opacity = gain * torch.nn.functional.softplus(opacity_raw)
     color = torch.sigmoid(color_raw)
     if scaffold is not None:
@@ -534,6 +561,8 @@ def lightplane_renderer_naive(
         color_grids=color_grids, contract_coords=contract_coords,
     )
     nlt = torch.cumsum(torch.nn.functional.pad(opacity * delta, (1, 0)), dim=-1)
+    if _VALUE_RECORDER is not None:
+        _VALUE_RECORDER.nlt = nlt.detach()
     transmittance = torch.exp(-nlt)
     w = transmittance[:, :-1] - transmittance[:, 1:]
     ray_length = (depths * w).sum(dim=-1)

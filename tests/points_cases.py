@@ -63,9 +63,13 @@ def _double_decoder(dec, params):
     return lp.DecoderParams(params, dec.n_hidden_trunk, dec.n_hidden_opacity, dec.n_hidden_color, dec.color_chn)
 
 
-def case(name):
-    if name in _CACHE:
-        return _CACHE[name]
+def case(name, decoder_transform=None, key=None):
+    """``decoder_transform`` (tests/value_regime_cases.py): the case with ``decoder_transform(decoder)`` in place of its decoder, cached
+    under ``key``; everything else -- grids, points, encoding, upstream gradients -- is the case's own."""
+    assert (decoder_transform is None) == (key is None)
+    key = name if key is None else key
+    if key in _CACHE:
+        return _CACHE[key]
     kind, base, (n_t, n_o, n_c, hidden), (R, N), form, contract, mask, sc_shape = CASES[name]
     gen = torch.Generator().manual_seed(SEEDS[name])
     B, C = base[0], base[4]
@@ -74,6 +78,8 @@ def case(name):
     grids = [0.5 * torch.randn(s, generator=gen) for s in sizes]
     cgrids = [0.5 * torch.randn(s, generator=gen) for s in sizes] if two else None
     dec = random_decoder(gen, n_t, n_o, n_c, C, hidden, 3, use_separate_color_grid=two, std=(2.0 / hidden) ** 0.5)
+    if decoder_transform is not None:
+        dec = decoder_transform(dec)
     half = 3.0 if contract else 1.2
     pts = (torch.rand(R, N, 3, generator=gen) * 2 - 1) * half
     gidx = torch.randint(0, B, (R,), generator=gen)
@@ -105,7 +111,7 @@ def case(name):
     leaves = dict(points=p64.clone().requires_grad_(True), params=dec.mlp_params.double().requires_grad_(True),
                   enc=enc.double().requires_grad_(True), grids=[g.double().requires_grad_(True) for g in grids],
                   cgrids=None if cgrids is None else [g.double().requires_grad_(True) for g in cgrids])
-    with O.relu_margin_recorder() as rec:
+    with O.relu_margin_recorder() as rec, O.value_recorder() as seen:
         op, col = O.eval_decoder(leaves["points"], leaves["grids"], gidx, _double_decoder(dec, leaves["params"]), leaves["enc"], GAIN,
                                  mask_out_of_bounds_samples=mask, scaffold=None if scaffold is None else scaffold.double(),
                                  color_grids=leaves["cgrids"], contract_coords=contract)
@@ -119,12 +125,12 @@ def case(name):
     (op * u_op.double()).sum().add((col * u_col.double()).sum()).backward()
     grads = dict(points=leaves["points"].grad, params=leaves["params"].grad, enc=leaves["enc"].grad,
                  grids=[g.grad for g in leaves["grids"]], cgrids=None if cgrids is None else [g.grad for g in leaves["cgrids"]])
-    _CACHE[name] = dict(name=name, grids=grids, cgrids=cgrids, dec=dec, pts=pts, gidx=gidx, enc=enc, scaffold=scaffold, form=form,
-                        contract=contract, mask=mask, op=op.detach(), col=col.detach(), left_out=left_out, zeroed=zeroed,
-                        counts=dict(near_tie=int(near_tie.sum()), on_face=int(on_face.sum()), on_kink=int(on_kink.sum()),
-                                    left_out=int(left_out.sum())),
-                        u_op=u_op, u_col=u_col, grads=grads)
-    return _CACHE[name]
+    _CACHE[key] = dict(name=name, grids=grids, cgrids=cgrids, dec=dec, pts=pts, gidx=gidx, enc=enc, scaffold=scaffold, form=form,
+                       contract=contract, mask=mask, op=op.detach(), col=col.detach(), left_out=left_out, zeroed=zeroed,
+                       counts=dict(near_tie=int(near_tie.sum()), on_face=int(on_face.sum()), on_kink=int(on_kink.sum()),
+                                   left_out=int(left_out.sum())),
+                       u_op=u_op, u_col=u_col, grads=grads, raw_o=seen.raw_o, raw_c=seen.raw_c[..., :3])
+    return _CACHE[key]
 
 
 def on_device(c, dev, requires_grad=()):

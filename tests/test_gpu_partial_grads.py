@@ -129,10 +129,10 @@ def _last_backward():
     return fn()
 
 
-def _baseline_meets_the_oracle(e, d, dev, base):
+def _baseline_meets_the_oracle(e, d, dev, base, tag=None):
     """The suite's own oracle machinery, unchanged, on the all-leaves call of the entry; ``base`` (the same call through this file's
     runner) is the very launch it proves: outputs bit-identical, gradients up to the order of the atomics."""
-    tag = f"partial-grad baseline {e.id}"
+    tag = tag or f"partial-grad baseline {e.id}"
     with config_set(**e.config):
         twin = has_dump_twin(d, kernel=e.kernel, march_order=e.march_order)
         if twin:
