@@ -644,6 +644,30 @@ def lightplane_splatter_naive(rays, output_grid_size, num_samples, num_samples_i
                           mask_out_of_bounds_samples, contract_coords, disparity_at_inf, return_list)
 
 
+def splatter_sums(rays, output_grid_size, num_samples, num_samples_inf=0, mask_out_of_bounds_samples=False,
+                  contract_coords=False, disparity_at_inf=1e-5, **_ignored):
+    """What the Splatter adds up BEFORE it normalises: per output grid ``(feature_sums [B*D*H*W, C], weight_sums [B*D*H*W])``, the two
+    scatter-adds of ``_splatter_impl`` (``_splat_one_grid`` of the encodings and of ones) without the division -- an error of the
+    feature walk and one of the weight walk show separately, and one common to both does not cancel."""
+    sizes = [[int(v) for v in gs] for gs in (output_grid_size.tolist() if torch.is_tensor(output_grid_size) else output_grid_size)]
+    dtype, device = rays.directions.dtype, rays.directions.device
+    with torch.no_grad():
+        points = _splatter_points(rays, num_samples, num_samples_inf, contract_coords, disparity_at_inf)
+        feat = rays.encoding[:, None, :].expand(-1, points.shape[1], -1)
+        if mask_out_of_bounds_samples:
+            ray_mask = in_bounds(points).to(dtype)
+        else:
+            ray_mask = torch.ones(points.shape[:-1], dtype=dtype, device=device)
+        ones = torch.ones(points.shape[:-1] + (1,), dtype=dtype, device=device)
+        out = []
+        for gs in sizes:
+            B, D, H, W, C = gs
+            fgrid = _splat_one_grid(torch.zeros(B * D * H * W, C, dtype=dtype, device=device), gs, points, rays.grid_idx, feat, ray_mask)
+            wgrid = _splat_one_grid(torch.zeros(B * D * H * W, 1, dtype=dtype, device=device), gs, points, rays.grid_idx, ones, ray_mask)
+            out.append((fgrid, wgrid[:, 0]))
+    return out
+
+
 def _ray_chunk(rays, lo, hi):
     import copy
     r = copy.copy(rays)
