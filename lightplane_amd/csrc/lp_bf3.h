@@ -272,6 +272,32 @@ LP_DEV void limb_tile_store(char* trow, const float (&v)[8 * NCH]) {
     *reinterpret_cast<u32x4_t*>(trow + 32 * c + rm_bytes(32)) = l2;
   }
 }
+// The same store where the asm IS the first conversion (the rays-per-wavefront tuned backward, round 8).  Passing the eight inputs
+// through "+v" while they stay live afterwards costs one v_mov_b32 per value -- 40 register copies per sample of that kernel; an
+// opaque v_cvt_pk_bf16_f32 hides the first limb, and with it the second, from the same value numbering at no instruction of its own.
+// Same instructions on the same values: the tiles are bit-identical.  (The looped and the transposed-march kernels keep the form
+// above: their register allocations were tuned around it and have not been re-measured.)
+LP_DEV unsigned pk_bf16_opaque(float a, float b) {
+  unsigned p;
+  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(a), "v"(b));
+  return p;
+}
+template <int NCH>
+LP_DEV void limb_tile_store_cvt(char* trow, const float (&v)[8 * NCH]) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    u32x4_t l1, l2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float a = v[8 * c + 2 * i], b = v[8 * c + 2 * i + 1];
+      const unsigned p1 = pk_bf16_opaque(a, b);
+      l1[i] = p1;
+      l2[i] = pk_bf16(a - bf16_lo(p1), b - bf16_hi(p1));
+    }
+    *reinterpret_cast<u32x4_t*>(trow + 32 * c) = l1;
+    *reinterpret_cast<u32x4_t*>(trow + 32 * c + rm_bytes(32)) = l2;
+  }
+}
 
 // the dX chains' operand split / chunk product with DXL = 2 or 3 limbs of the gradient operand (l3 unused with two)
 template <int DXL>

@@ -457,6 +457,17 @@ LP_DEV float relu_f(float x) {
 LP_DEV unsigned mask_bit(unsigned m, float relu_value, int q) {
   return m | ((relu_value > 0.0f) ? (1u << q) : 0u);
 }
+// mask_push: the mask shifted left by one with "relu_value > 0" appended (compare, select of 0 / 1, one shift-or per two pushes: no
+// bit literal in a register); after n pushes the decision of push i sits at bit n - 1 - i.
+LP_DEV unsigned mask_push(unsigned m, float relu_value) { return m + m + ((relu_value > 0.0f) ? 1u : 0u); }
+// mask_gate: mask_apply with the bit-field extract kept as ONE instruction (v_bfe_i32 + v_and_b32; left to itself the optimiser
+// turns "v & sign-extended bit" back into and + compare + select, three instructions and a literal in a register)
+template <int Q>
+LP_DEV float mask_gate(unsigned m, float v) {
+  int all;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(all) : "v"(m), "n"(Q));
+  return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & all);
+}
 LP_DEV float mask_apply(unsigned m, int q, float v) {
   const int all = ((int)(m << (31 - q))) >> 31;
   return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & all);

@@ -189,6 +189,51 @@ LP_DEV void gather_taps4(const float* data, const int* row, const float* w, floa
   }
 }
 
+// Border-clamped taps of a canonical triplane (round 8).  plane_taps_from_axes() marks an out-of-range tap with row -1 and weight 0
+// per TAP, and the gather then clamps the row: two selects and a compare + 64-bit select per tap, 60 VALU instructions per sample for
+// the twelve taps.  Here validity is folded in per AXIS: an invalid axis tap gets weight 0 (so every tap product with it is +0, as
+// before: the weights are never negative) and its index is clamped into the axis (one v_med3_i32), so every row is a row of the plane
+// and no tap needs a select.  An invalid tap used to read row 0 of the tensor and now reads a border row of its plane; either is
+// multiplied by +0, so finite grids give bit-identical features (non-finite grid values are outside the contract either way).
+struct AxisClamp {
+  int i[2];
+  float w[2];
+};
+LP_DEV AxisClamp axis_clamp(const AxisTap& t, int size) {  // t.i0 is in [-2, size] (axis_taps)
+  AxisClamp c;
+  c.i[0] = min(max(t.i0, 0), size - 1);
+  c.i[1] = min(max(t.i0 + 1, 0), size - 1);
+  c.w[0] = t.ok[0] ? t.w[0] : 0.0f;
+  c.w[1] = t.ok[1] ? t.w[1] : 0.0f;
+  return c;
+}
+// the four taps (slot k = u-bit + 2 v-bit, the order of plane_taps_from_axes) of one plane: loads first, then the accumulation in the
+// order of four gather_tap() calls
+template <int C>
+LP_DEV void gather_plane_clamped(const float* data, int base, int U, const AxisClamp& u, const AxisClamp& v, float keep, int h,
+                                 float (&x0)[C / 2]) {
+  float4 val[4][C / 8];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned row = (unsigned)(base + v.i[k >> 1] * U + u.i[k & 1]);  // (never negative: zero-extended, not sign-extended)
+    const float4* src = reinterpret_cast<const float4*>(data + (uint64_t)row * C + 4 * h);
+#pragma unroll
+    for (int j = 0; j < C / 8; ++j) val[k][j] = src[2 * j];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float wk = (u.w[k & 1] * v.w[k >> 1]) * keep;
+#pragma unroll
+    for (int j = 0; j < C / 8; ++j) {
+      x0[4 * j + 0] = fmaf(wk, val[k][j].x, x0[4 * j + 0]);
+      x0[4 * j + 1] = fmaf(wk, val[k][j].y, x0[4 * j + 1]);
+      x0[4 * j + 2] = fmaf(wk, val[k][j].z, x0[4 * j + 2]);
+      x0[4 * j + 3] = fmaf(wk, val[k][j].w, x0[4 * j + 3]);
+    }
+  }
+}
+
 // gather from an explicit grid-list (run-time loop over its grids): the colour grid-list of the two-grid decoder
 template <int C, bool FENCED>
 LP_DEV void gather_list(const LpGridList& gl, bool mask_oob, const Ray& ray, float x, float y, float z, int h,
@@ -224,15 +269,13 @@ LP_DEV void gather_features(const LpRendererArgs& a, const Ray& ray, float x, fl
       AxisTap ax, ay, az;
       triplane_axes<false>(a.grid.grids, x, y, z, ax, ay, az);
       const int W = a.grid.grids[0].W, H = a.grid.grids[0].H, D = a.grid.grids[1].D;
+      const AxisClamp cx = axis_clamp(ax, W), cy = axis_clamp(ay, H), cz = axis_clamp(az, D);
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         __builtin_amdgcn_sched_barrier(0);
-        if (pm & WaveRanges::bit(g)) {
-          Taps t;
-          plane_taps_from_axes((int)a.grid.grids[g].row_offset + ray.b * ((g == 0 ? H : D) * (g == 2 ? H : W)), g == 2 ? H : W,
-                               g == 2 ? ay : ax, g == 0 ? ay : az, t);
-          gather_taps4<C>(a.grid.grids[g].data, t.row, t.w, keep, h, x0);
-        }
+        if (pm & WaveRanges::bit(g))
+          gather_plane_clamped<C>(a.grid.grids[g].data, (int)a.grid.grids[g].row_offset + ray.b * ((g == 0 ? H : D) * (g == 2 ? H : W)),
+                                  g == 2 ? H : W, g == 2 ? cy : cx, g == 0 ? cy : cz, keep, h, x0);
       }
       __builtin_amdgcn_sched_barrier(0);
     } else {
@@ -519,18 +562,23 @@ LP_DEV void scatter_plane(float* gg, const LpGrid& g, int b, float x, float y, f
 // DPP wave shift (one VALU instruction, no LDS round trip).  The ray walk itself (scalar-branched run merge, one atomic per
 // run and row) is the one of scatter_plane_ax.
 struct AxisNorm {
-  int i;        // first cell of the pair, both cells in range unless dead
-  float w0, w1;
+  int i;        // first cell of the pair, both cells in range (also where dead)
+  float w0, w1; // both 0 where dead
   bool dead;
 };
+// (Round 8: the same values from fewer selects.  With the weights gated per tap first -- g_k = ok_k ? w_k : 0 -- a border cell, one tap
+// in range, is the pair with its weights SWAPPED: the in-range weight moves to the other slot and the slot it leaves gets the 0 of the
+// out-of-range tap; a dead axis has both gated weights 0 whether swapped or not.  The cell index is the tap index clamped to
+// [0, size - 2], one v_med3_i32: -1 -> 0 and size - 1 -> size - 2 are exactly the border moves; axes have at least two cells.)
 LP_DEV AxisNorm axis_norm(float c, int size) {
   AxisTap t;
   axis_taps<false>(c, size, t.i0, t.w, t.ok);
-  const bool only0 = t.ok[0] & !t.ok[1], only1 = !t.ok[0] & t.ok[1];  // a border cell: one tap in range (selects, no branches)
+  const bool swap = t.ok[0] != t.ok[1];
+  const float g0 = t.ok[0] ? t.w[0] : 0.0f, g1 = t.ok[1] ? t.w[1] : 0.0f;
   AxisNorm n;
-  n.i = t.i0 + (only1 ? 1 : 0) - (only0 ? 1 : 0);
-  n.w0 = only0 ? 0.0f : (only1 ? t.w[1] : t.w[0]);
-  n.w1 = only1 ? 0.0f : (only0 ? t.w[0] : t.w[1]);
+  n.i = min(max(t.i0, 0), size - 2);
+  n.w0 = swap ? g1 : g0;
+  n.w1 = swap ? g0 : g1;
   n.dead = !(t.ok[0] | t.ok[1]);
   return n;
 }
@@ -547,14 +595,16 @@ LP_DEV void scatter_triplane(float* const* gg_list, const LpGridList& gl, int b,
   const int row_xy = d0 ? -1 : (int)gl.grids[0].row_offset + (b * H + ay.i) * W + ax.i;
   const int row_xz = d1 ? -1 : (int)gl.grids[1].row_offset + (b * D + az.i) * W + ax.i;
   const int row_yz = d2 ? -1 : (int)gl.grids[2].row_offset + (b * D + az.i) * H + ay.i;
-  const float wy = h ? ay.w1 : ay.w0, wz = h ? az.w1 : az.w0;  // the v-weight of this lane's two slots
+  // the v-weight of this lane's two slots, 0 for a ray that is not live: every product below carries wy or wz, and a dead axis carries
+  // its own zeros (axis_norm), so the six weights need no select of their own -- +0 wherever the plane's row is the sentinel
+  const float wy = live ? (h ? ay.w1 : ay.w0) : 0.0f, wz = live ? (h ? az.w1 : az.w0) : 0.0f;
   float* const wl = wT + (2 * h) * 32 + r;
-  wl[0] = d0 ? 0.0f : ax.w0 * wy;
-  wl[32] = d0 ? 0.0f : ax.w1 * wy;
-  wl[128] = d1 ? 0.0f : ax.w0 * wz;
-  wl[160] = d1 ? 0.0f : ax.w1 * wz;
-  wl[256] = d2 ? 0.0f : ay.w0 * wz;
-  wl[288] = d2 ? 0.0f : ay.w1 * wz;
+  wl[0] = ax.w0 * wy;
+  wl[32] = ax.w1 * wy;
+  wl[128] = ax.w0 * wz;
+  wl[160] = ax.w1 * wz;
+  wl[256] = ay.w0 * wz;
+  wl[288] = ay.w1 * wz;
   const bool first = r == 0;
   const unsigned m_xy = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(first | (row_xy != lane_prev(row_xy))));
   const unsigned m_xz = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(first | (row_xz != lane_prev(row_xz))));

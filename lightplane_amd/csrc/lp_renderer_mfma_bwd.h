@@ -308,6 +308,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
   // samples at which this wave's rays can reach each plane (lp_mfma_common.h: scalar registers); the non-PLAIN and the segmented
   // instantiations keep every sample
   const WaveRanges rg = wave_plane_ranges<GM>(a, ray, valid, PLAIN && !SEG);
+  // transmittance in front of the sample the sweep is at: T behind sample s IS T in front of sample s + 1 -- the same exp(-nlt) of the
+  // same nlt -- so it is carried from sample to sample and recomputed only where a checkpoint reloads nlt (one v_exp_f32 per sample
+  // instead of two)
+  float t_carry = __expf(-nlt);
   Sample<C> nx;
   // (the first fetch gathers every plane: with scalar branches in it the allocator spills ~20 loop-invariant registers that the sample
   // loop then reloads -- scripts/isa_loop_scratch.py: 23 scratch instructions per sample instead of none)
@@ -378,9 +382,12 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       hd = heads_forward<NC>(sm, h, ho, hc, zo);
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        ho_mask = mask_bit(ho_mask, ho[q], q);
+        ho_mask = mask_push(ho_mask, ho[q]);  // (decision of q at bit 15 - q)
         hc_mask = mask_bit(hc_mask, hc[q], q);
       }
+      // (opaque: the optimiser otherwise sees through the adds of mask_push, gates d ho on ho itself and keeps ho in 16 registers
+      // across the compositing)
+      asm volatile("" : "+v"(ho_mask));
       if constexpr (DUMP) {
         unsigned m1 = 0, m2 = 0, mo = 0, mc = 0;
 #pragma unroll
@@ -388,7 +395,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
           const unsigned bit = 1u << featq(q, h);
           m1 |= (h1[q] > 0.0f) ? bit : 0u;
           m2 |= (e[q] > 0.0f) ? bit : 0u;
-          mo |= ((ho_mask >> q) & 1u) ? bit : 0u;
+          mo |= ((ho_mask >> (15 - q)) & 1u) ? bit : 0u;
           mc |= ((hc_mask >> q) & 1u) ? bit : 0u;
         }
         m1 |= __shfl_xor(m1, 32); m2 |= __shfl_xor(m2, 32); mo |= __shfl_xor(mo, 32); mc |= __shfl_xor(mc, 32);
@@ -399,6 +406,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       }
       LP_SCHED_FENCE();
       // ho / hc go to the (wave-private) tiles: the output layers' dW reads them from there
+      // (Round 8 also read hc back from its tile as the ReLU gate of d hc -- 16 lane-private ds_read_b32, compare + select, no hc mask:
+      // 36 VALU instructions fewer per sample, but 1.1 % SLOWER on cfg 2 and 1.7 % on cfg 4 than the mask: profiles/r08_loop_diet_ab.txt.)
       if (want_params) {
         tile_store_fm(xt, r, h, ho);
         tile_store_fm(yt, r, h, hc);
@@ -423,12 +432,14 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
         const float2 c2 = *reinterpret_cast<const float2*>(a.neg_log_t_ckpt + (rid * n_ckpt + ck) * 2);
         nlt = c2.x;
         nlt_lo = c2.y;
+        t_carry = __expf(-nlt);
       }
     }
-    const float t_i = __expf(-nlt);
+    const float t_i = t_carry;
     nlt_add(nlt, nlt_lo, on ? -(opacity * delta) : 0.0f);
     if (!(nlt > 0.0f)) { nlt = 0.0f; nlt_lo = 0.0f; }
     const float t_im1 = __expf(-nlt);
+    t_carry = t_im1;
     const float w = t_im1 - t_i;
     float sg[4];
     float p_i = g_len * depth;
@@ -506,7 +517,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     f32x16 acc = (f32x16){0};
     {
       if constexpr (DWB) {
-        if (want_params) limb_tile_store<2>(xrow, e);
+        if (want_params) limb_tile_store_cvt<2>(xrow, e);
         acc = layer_dxv<2, DXL>(Ab(I3{}), lane, dhc, acc, want_params ? yrow : nullptr);
       } else {
         if (want_params) {
@@ -529,14 +540,15 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     LP_MARK("o1");
     {
       float dho[16];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      auto gate4 = [&](auto jc) {  // (the decision of value q sits at bit 15 - q: mask_push)
+        constexpr int j = decltype(jc)::value;
         const float4 wo = *reinterpret_cast<const float4*>(ldz + M::WO2 + 8 * j + 4 * h);
-        dho[4 * j + 0] = mask_apply(ho_mask, 4 * j + 0, dro * wo.x);
-        dho[4 * j + 1] = mask_apply(ho_mask, 4 * j + 1, dro * wo.y);
-        dho[4 * j + 2] = mask_apply(ho_mask, 4 * j + 2, dro * wo.z);
-        dho[4 * j + 3] = mask_apply(ho_mask, 4 * j + 3, dro * wo.w);
-      }
+        dho[4 * j + 0] = mask_gate<15 - (4 * j + 0)>(ho_mask, dro * wo.x);
+        dho[4 * j + 1] = mask_gate<15 - (4 * j + 1)>(ho_mask, dro * wo.y);
+        dho[4 * j + 2] = mask_gate<15 - (4 * j + 2)>(ho_mask, dro * wo.z);
+        dho[4 * j + 3] = mask_gate<15 - (4 * j + 3)>(ho_mask, dro * wo.w);
+      };
+      gate4(I0{}); gate4(I1{}); gate4(I2{}); gate4(I3{});
       if constexpr (DWB) {
         acc = layer_dxv<2, DXL>(Ab(I2{}), lane, dho, acc, want_params ? yrow : nullptr);  // the X tile still holds e
       } else {
@@ -559,7 +571,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     float dh1[16];
     {
       if constexpr (DWB) {
-        if (want_params) limb_tile_store<2>(xrow, h1);
+        if (want_params) limb_tile_store_cvt<2>(xrow, h1);
         acc = layer_dxv<2, DXL>(Ab(I1{}), lane, de, (f32x16){0}, want_params ? yrow : nullptr);
       } else {
         if (want_params) {
@@ -582,11 +594,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
     LP_MARK("t1");
     {
       if constexpr (DWB) {
-        if (want_params) limb_tile_store<C / 16>(xrow, x0);
+        if (want_params) limb_tile_store_cvt<C / 16>(xrow, x0);
         if (ggs) {
           acc = layer_dxv<2, DXL>(Ab(I0{}), lane, dh1, (f32x16){0}, want_params ? yrow : nullptr);  // rows >= C of the result are unused
         } else if (want_params) {
-          limb_tile_store<2>(yrow, dh1);
+          limb_tile_store_cvt<2>(yrow, dh1);
         }
       } else {
         if (want_params) {
