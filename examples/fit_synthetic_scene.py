@@ -9,6 +9,7 @@ GPU boxes have no datasets.
 
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
+                                            [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -34,6 +35,10 @@ batch) and ``hit_fraction``.  Without the flag the run is bit for bit what it is
 ``--scaffold-size``^3 lattice at ``--scaffold-threshold`` (no dilation) picks the occupied lattice points, ``renderer.eval_decoder_at_points``
 -- one fused kernel, ``lp.lightplane_eval_mlp`` -- gives their opacity and their colour seen along ``-z``, and the file holds one
 float32 row ``x y z | r g b | opacity`` per point.
+
+``--export-mesh FILE.ply`` writes the fitted scene as a triangle mesh after the fit: ``renderer.extract_mesh`` -- the fused opacity
+lattice of ``--mesh-size``^3 points, marching cubes on the GPU at the opacity ``--mesh-level`` (``lp.marching_cubes``) and the fused
+point decoder for the vertex colours seen along ``-z`` -- and the file is an ASCII PLY with positions, normals and 8-bit colours.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -94,7 +99,9 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None,
 
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
-        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False):
+        upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False,
+        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None):
+    """``on_fitted(renderer, grids)``: called after the last step, before the exports, with the fitted module and its planes"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -158,11 +165,35 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_tv=float(tvs[0]), last_tv=float(tvs[-1]),
                    grads_finite=all(bool(torch.isfinite(g.grad).all()) for g in grids))
+    if on_fitted is not None:
+        on_fitted(renderer, list(grids))
     if export_pointcloud:
         cloud = pointcloud(renderer, list(grids), scaffold_size, scaffold_threshold, dev)
         np.save(export_pointcloud, cloud.cpu().numpy())
         out.update(pointcloud_file=export_pointcloud, pointcloud_points=int(cloud.shape[0]))
+    if export_mesh:
+        mesh = renderer.extract_mesh(list(grids), [1, mesh_size, mesh_size, mesh_size], level=mesh_level,
+                                     view_directions=torch.tensor([[0.0, 0.0, -1.0]], device=dev))
+        write_ply(export_mesh, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), mesh.normals.cpu().numpy(),
+                  mesh.colors.cpu().numpy())
+        out.update(mesh_file=export_mesh, mesh_vertices=int(mesh.vertices.shape[0]), mesh_faces=int(mesh.faces.shape[0]),
+                   mesh_level=mesh_level)
     return out
+
+
+def write_ply(path, vertices, faces, normals, colors):
+    """ASCII PLY: ``x y z nx ny nz red green blue`` per vertex (colours as 8-bit), ``3 i j k`` per face"""
+    rgb = np.clip(np.rint(colors[:, :3] * 255.0), 0, 255).astype(np.int64)
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\ncomment lightplane_amd marching cubes\n")
+        f.write(f"element vertex {vertices.shape[0]}\n")
+        f.write("property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n")
+        f.write("property uchar red\nproperty uchar green\nproperty uchar blue\n")
+        f.write(f"element face {faces.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+        for v, n, c in zip(vertices, normals, rgb):
+            f.write(f"{v[0]:.9g} {v[1]:.9g} {v[2]:.9g} {n[0]:.6g} {n[1]:.6g} {n[2]:.6g} {c[0]} {c[1]} {c[2]}\n")
+        for t in faces:
+            f.write(f"3 {t[0]} {t[1]} {t[2]}\n")
 
 
 @torch.no_grad()
@@ -196,11 +227,16 @@ def main(argv=None):
                     help="after the fit, write xyz | rgb | opacity of the occupied lattice points of a scaffold")
     ap.add_argument("--clip-rays", action="store_true",
                     help="clip every ray batch to the scaffold's occupied span (to the scene box before a scaffold exists)")
+    ap.add_argument("--export-mesh", default=None, metavar="FILE.ply",
+                    help="after the fit, write the level set of the opacity as a coloured triangle mesh (ASCII PLY)")
+    ap.add_argument("--mesh-size", type=int, default=64, help="points per axis of the lattice the mesh is extracted from")
+    ap.add_argument("--mesh-level", type=float, default=1.0, help="opacity of the extracted level set")
     ap.add_argument("--res", type=int, default=64, help="resolution of the planes")
     a = ap.parse_args(argv)
     out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
               upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
-              scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays)
+              scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays,
+              export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level)
     print(json.dumps(out))
     return out
 

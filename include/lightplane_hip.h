@@ -107,7 +107,10 @@ extern "C" {
                                   and again (additive: a new struct and four new entry points): gather and splat of a grid-list at
                                   arbitrary points, LpPointGridArgs with lp_point_gather() / lp_point_splat() / lp_point_normalize() /
                                   lp_point_grad_points() (lp_build_info() then has a "point_grid" entry; lp_abi_sizeof(14) answers
-                                  for the new struct) */
+                                  for the new struct)
+                                  and again (additive: a new struct and three new entry points): the triangle mesh of a lattice's
+                                  level set, LpMeshArgs with lp_mesh_workspace_bytes() / lp_mesh_count() / lp_mesh_emit()
+                                  (lp_build_info() then has a "mesh" entry; lp_abi_sizeof(16) answers for the new struct) */
 
 #define LP_MAX_GRIDS 8   /* grids per grid-list                         */
 #define LP_MAX_LAYERS 8  /* layers per MLP                              */
@@ -342,9 +345,9 @@ const char* lp_build_info(void);
 const char* lp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * which = 0 LpGrid, 1 LpGridList, 2 LpRays, 3 LpMarch, 4 LpMlp, 5 LpRendererArgs,
- * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs, 12 LpRayClipArgs, 14 LpPointGridArgs; anything else returns
- * -1 -- 9, 11 and 13 among them: the scaffold's, the point evaluation's and the ray clip's tests pin those answers as "the first
- * selector that does not exist", so the next addition took the one after. */
+ * 6 LpSplatterArgs, 7 LpRayEmbedArgs, 8 LpScaffoldArgs, 10 LpPointsArgs, 12 LpRayClipArgs, 14 LpPointGridArgs, 16 LpMeshArgs; anything
+ * else returns -1 -- 9, 11, 13 and 15 among them: the scaffold's, the point evaluation's, the ray clip's and the point gather's tests
+ * pin those answers as "the first selector that does not exist", so the next addition took the one after. */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the
@@ -652,6 +655,47 @@ int lp_point_gather(const LpPointGridArgs* args, void* stream);
 int lp_point_splat(const LpPointGridArgs* args, void* stream);
 int lp_point_normalize(const LpPointGridArgs* args, void* stream);
 int lp_point_grad_points(const LpPointGridArgs* args, void* stream);
+
+/* Triangle mesh of the level set {volume = level} of a [B, D, H, W] lattice: marching cubes (lp_mesh.hip; an extension -- the
+ * reference has no mesh extraction).  Lattice point n = ((b D + z) H + y) W + x sits at the scaffold's coordinates
+ * (lin(W)[x], lin(H)[y], lin(D)[z]), lin(n) = linspace(-1, 1, n); a point is inside when volume >= level (a NaN is outside).  A
+ * lattice edge belongs to its endpoint with the lower coordinate and carries a vertex when exactly one endpoint is inside:
+ *   vertex = p_lo + t (p_hi - p_lo),  t = clamp((level - v_lo) / (v_hi - v_lo), 0, 1) in fp32 (a NaN quotient -- an infinite or NaN
+ *   endpoint -- counts as 0; finite values whose difference overflows fp32 are halved first, so +-3e38 around level 0 still gives 0.5).
+ * Each cell (min corner n) contributes the triangles of the table lp_mc_table.h (generated by scripts/gen_mc_table.py; watertight by
+ * construction, normals towards the lower values).  The output order is part of the contract:
+ *   vertices: by owner point n, then axis x, y, z;   faces: by cell n, then table order;   scenes concatenated.
+ * A face holds three vertex ids local to its scene (global id - vertex_offsets[b]).  An axis of size 1 has no cells: the mesh is empty.
+ *   lp_mesh_workspace_bytes: shapes only (no device): 4 bytes per lattice point + 16 bytes per 256 points (+ the small upper levels
+ *                            of the scan), or a negative LP_E* code.
+ *   lp_mesh_count:  count pass + scan.  WRITES every element of vertex_offsets / face_offsets ([B + 1] int64: entry b = vertices /
+ *                   faces of the scenes before b, entry B = the totals) and the workspace.  Reads volume.
+ *   lp_mesh_emit:   after lp_mesh_count with the same arguments and workspace (which it reads, with vertex_offsets).  WRITES
+ *                   vertices[i], normals[i] for every i < min(total vertices, max_vertices) and faces[i] for every
+ *                   i < min(total faces, max_faces); touches nothing at or beyond a capacity -- the offsets keep the true counts, so
+ *                   the caller detects the overflow.  normals == NULL: none; else the unit vector along -(gradient), the gradient by
+ *                   central differences (one-sided at the border) in scene coordinates at the two endpoints, interpolated with t;
+ *                   (0, 0, 0) where it vanishes or is not finite.
+ * No atomics, nothing waits on another workgroup (the scan is a hierarchy of separate launches), no host synchronisation, no
+ * allocation: graph-capturable and bit-reproducible.  Every device pointer is 16-byte aligned (Conventions).  Before anything touches
+ * the device: LP_ENULL for NULL args / volume / offsets / workspace, or a NULL vertices / faces with a capacity > 0; LP_EINVAL for an
+ * extent < 1, a negative capacity, an under-aligned pointer, a workspace smaller than lp_mesh_workspace_bytes(); LP_EUNSUPPORTED
+ * for B D H W >= 2^31.  The vertices of one scene have to stay below 2^31 (int32 ids). */
+typedef struct LpMeshArgs {
+  const float* volume;      /* [B, D, H, W] (read) */
+  LpGrid shape;             /* B, D, H, W (row_offset and data ignored) */
+  float level;
+  int32_t reserved;         /* 0 */
+  int64_t* vertex_offsets;  /* [B + 1] (count: written; emit: read) */
+  int64_t* face_offsets;    /* [B + 1] (count: written) */
+  float* vertices;          /* emit: [max_vertices, 3] (written below the count) */
+  int32_t* faces;           /* emit: [max_faces, 3] (written below the count) */
+  float* normals;           /* emit: NULL or [max_vertices, 3] (written below the count) */
+  int64_t max_vertices, max_faces;
+} LpMeshArgs;
+int64_t lp_mesh_workspace_bytes(const LpMeshArgs* args);
+int lp_mesh_count(const LpMeshArgs* args, void* workspace, int64_t workspace_bytes, void* stream);
+int lp_mesh_emit(const LpMeshArgs* args, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* out[i] = hash_randn(x1[i], x2[i], seed), i < n (test hook for the opacity-noise RNG). */
 int lp_hash_randn(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,

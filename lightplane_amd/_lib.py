@@ -137,6 +137,14 @@ class LpPointGridArgs(C.Structure):
     ]
 
 
+class LpMeshArgs(C.Structure):
+    _fields_ = [
+        ("volume", C.c_void_p), ("shape", LpGrid), ("level", C.c_float), ("reserved", C.c_int32),
+        ("vertex_offsets", C.c_void_p), ("face_offsets", C.c_void_p), ("vertices", C.c_void_p), ("faces", C.c_void_p),
+        ("normals", C.c_void_p), ("max_vertices", C.c_int64), ("max_faces", C.c_int64),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -155,6 +163,7 @@ EXPORTS = (
     "lp_points_forward", "lp_points_backward",
     "lp_rays_clip",
     "lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points",
+    "lp_mesh_count", "lp_mesh_emit",  # (+ lp_mesh_workspace_bytes, which returns int64_t)
 )
 
 
@@ -252,11 +261,18 @@ def lib() -> C.CDLL:
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(LpPointGridArgs), C.c_void_p]
+    # triangle mesh of a lattice's level set: args, workspace, workspace bytes, stream
+    L.lp_mesh_workspace_bytes.restype = C.c_int64
+    L.lp_mesh_workspace_bytes.argtypes = [C.POINTER(LpMeshArgs)]
+    for name in ("lp_mesh_count", "lp_mesh_emit"):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(LpMeshArgs), C.c_void_p, C.c_int64, C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
                       (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
-                      (14, LpPointGridArgs)):  # (selectors 9, 11 and 13 do not exist: lightplane_hip.h)
+                      (14, LpPointGridArgs), (16, LpMeshArgs)):  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

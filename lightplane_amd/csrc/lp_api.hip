@@ -619,6 +619,49 @@ static int check_ray_clip(const LpRayClipArgs* args, const float* near_out, cons
   return LP_OK;
 }
 
+// the shape of a lattice to mesh: all lp_mesh_workspace_bytes() looks at
+static int check_mesh_shape(const char* what, const LpMeshArgs* args) {
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const LpGrid& s = args->shape;
+  if (s.B < 1 || s.D < 1 || s.H < 1 || s.W < 1)
+    return set_error(LP_EINVAL, "%s: volume shape [%d,%d,%d,%d] has an extent < 1", what, s.B, s.D, s.H, s.W);
+  // (the product of four positive int32 can pass 2^63: compare step by step)
+  int64_t n = 1;
+  for (const int64_t e : {(int64_t)s.B, (int64_t)s.D, (int64_t)s.H, (int64_t)s.W}) {
+    n *= e;
+    if (n >= ((int64_t)1 << 31))
+      return set_error(LP_EUNSUPPORTED, "%s: volume shape [%d,%d,%d,%d]: B * D * H * W has to stay below 2^31", what, s.B, s.D, s.H, s.W);
+  }
+  return LP_OK;
+}
+
+// everything lp_mesh_count / lp_mesh_emit check
+static int check_mesh(const char* what, const LpMeshArgs* args, const void* workspace, int64_t workspace_bytes, bool emit) {
+  int rc;
+  if ((rc = check_mesh_shape(what, args))) return rc;
+  const struct { const char* field; const void* p; } ptrs[] = {
+      {"volume", args->volume},     {"vertex_offsets", args->vertex_offsets}, {"face_offsets", args->face_offsets},
+      {"vertices", args->vertices}, {"faces", args->faces},                   {"normals", args->normals},
+      {"workspace", workspace}};
+  for (const auto& f : ptrs)
+    if ((rc = check_aligned(f.field, f.p))) return rc;
+  if (!args->volume) return set_error(LP_ENULL, "%s: volume is NULL", what);
+  if (!args->vertex_offsets || !args->face_offsets) return set_error(LP_ENULL, "%s: vertex_offsets / face_offsets is NULL", what);
+  const int64_t need = mesh_workspace_bytes(args->shape);
+  if (!workspace) return set_error(LP_ENULL, "%s: workspace is NULL, lp_mesh_workspace_bytes() asks for %lld bytes", what, (long long)need);
+  if (workspace_bytes < need)
+    return set_error(LP_EINVAL, "%s: workspace of %lld bytes, lp_mesh_workspace_bytes() asks for %lld", what, (long long)workspace_bytes,
+                     (long long)need);
+  if (emit) {
+    if (args->max_vertices < 0 || args->max_faces < 0)
+      return set_error(LP_EINVAL, "%s: max_vertices = %lld, max_faces = %lld, have to be >= 0", what, (long long)args->max_vertices,
+                       (long long)args->max_faces);
+    if (args->max_vertices > 0 && !args->vertices) return set_error(LP_ENULL, "%s: vertices is NULL with max_vertices = %lld", what, (long long)args->max_vertices);
+    if (args->max_faces > 0 && !args->faces) return set_error(LP_ENULL, "%s: faces is NULL with max_faces = %lld", what, (long long)args->max_faces);
+  }
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -634,10 +677,10 @@ const char* lp_build_info(void) {
   static const bool once = [] {
     snprintf(info, sizeof(info),
              "{\"version\": %d, \"src_hash\": \"%s\", \"test_hooks\": %s, \"tuned_bwd\": %s, \"loop_bwd_deep\": %s, "
-             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"ray_clip\": %s, \"point_grid\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
+             "\"loop_bwd_shallow\": %s, \"mlp_splatter_bwd\": %s, \"loop_fwd_stream\": %s, \"grid_tv\": %s, \"grid_resample\": %s, \"scaffold\": %s, \"points\": %s, \"ray_clip\": %s, \"point_grid\": %s, \"mesh\": %s, \"forward\": \"bf16x3 (three exact bf16 limbs per fp32 operand, six limb "
              "products, fp32 accumulation) on v_mfma_f32_32x32x16_bf16; generic kernels: fp32 FMA\", \"flags\": %s}",
              lp_version(), LP_BUILD_SRC_HASH, build_info_tuned_bwd_aux(), build_info_tuned_bwd(), build_info_loop_deep(),
-             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), build_info_ray_clip(), build_info_point_grid(), LP_BUILD_FLAGS_JSON);
+             build_info_loop_shallow(), build_info_splatter_mlp(), build_info_loop_stream(), build_info_grid_tv(), build_info_grid_resample(), build_info_scaffold(), build_info_points(), build_info_ray_clip(), build_info_point_grid(), build_info_mesh(), LP_BUILD_FLAGS_JSON);
     return true;
   }();
   (void)once;
@@ -658,6 +701,7 @@ int lp_abi_sizeof(int which) {
     case 10: return (int)sizeof(LpPointsArgs);  // (9 stays unanswered: lightplane_hip.h)
     case 12: return (int)sizeof(LpRayClipArgs);  // (and so does 11)
     case 14: return (int)sizeof(LpPointGridArgs);  // (and 13)
+    case 16: return (int)sizeof(LpMeshArgs);  // (and 15)
     default: return -1;
   }
 }
@@ -1095,6 +1139,24 @@ int lp_scaffold_build(const LpScaffoldArgs* args, float* scaffold, void* workspa
       return set_error(LP_EINVAL, "lp_scaffold_build: the workspace overlaps the result");
   }
   return scaffold_launch(a, scaffold, workspace, true, (hipStream_t)stream);
+}
+
+int64_t lp_mesh_workspace_bytes(const LpMeshArgs* args) {
+  const int rc = check_mesh_shape("lp_mesh_workspace_bytes", args);
+  if (rc) return rc;
+  return mesh_workspace_bytes(args->shape);
+}
+
+int lp_mesh_count(const LpMeshArgs* args, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = check_mesh("lp_mesh_count", args, workspace, workspace_bytes, false);
+  if (rc) return rc;
+  return mesh_count_launch(*args, workspace, (hipStream_t)stream);
+}
+
+int lp_mesh_emit(const LpMeshArgs* args, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = check_mesh("lp_mesh_emit", args, workspace, workspace_bytes, true);
+  if (rc) return rc;
+  return mesh_emit_launch(*args, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

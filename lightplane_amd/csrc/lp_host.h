@@ -139,6 +139,11 @@ int point_splat_launch(const LpPointGridArgs& a, hipStream_t stream);
 int point_normalize_launch(const LpPointGridArgs& a, hipStream_t stream);
 int point_grad_points_launch(const LpPointGridArgs& a, hipStream_t stream);
 const char* build_info_point_grid();
+// triangle mesh of a lattice's level set: lp_mesh.hip (`a` checked by lp_api.hip; `workspace` of mesh_workspace_bytes() bytes)
+int64_t mesh_workspace_bytes(const LpGrid& shape);
+int mesh_count_launch(const LpMeshArgs& a, void* workspace, hipStream_t stream);
+int mesh_emit_launch(const LpMeshArgs& a, void* workspace, hipStream_t stream);
+const char* build_info_mesh();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

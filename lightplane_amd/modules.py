@@ -33,6 +33,7 @@ from .points import lightplane_eval_mlp as _fused_eval_mlp, lightplane_eval_mlp_
 from .renderer import _render, lightplane_renderer
 from .ray_clip import clip_rays_to_scaffold as _clip_rays_to_scaffold
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
+from .mesh import extract_mesh as _fused_extract_mesh
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
 
 logger = logging.getLogger(__name__)
@@ -335,6 +336,23 @@ class LightplaneRenderer(torch.nn.Module):
             ks = dilate_scaffold * 2 + 1
             scaffold = torch.nn.functional.max_pool3d(scaffold, kernel_size=ks, padding=dilate_scaffold, stride=1)
         return (scaffold > threshold) * 1.0
+
+    @torch.no_grad()
+    def extract_mesh(self, feature_grid, lattice_size, *, level: float, view_directions=None, ray_encoding=None,
+                     color_feature_grid=None, with_normals: bool = True, grid_sizes=None, color_grid_sizes=None):
+        """Triangle mesh of the level set ``{opacity = level}`` of this module's decoder on a ``[B, D, H, W]`` lattice:
+        :func:`lightplane_amd.extract_mesh` (``scaffold_opacity`` -> ``marching_cubes``) with the module's decoder,
+        gain and out-of-bounds mask; returns its ``ColoredMesh``.  Per-vertex colours come with one viewing direction
+        (``view_directions [B, 3]``, through the module's ray embedding) or one ``ray_encoding [B, E]`` per scene; without either,
+        ``colors`` is ``None``.  Vertices are in the lattice's own frame (no contraction).  Fused kernels only: the grids have to be
+        fp32, dense and 16-byte aligned on the GPU (there is no fallback through the Renderer)."""
+        enc = None
+        if view_directions is not None or ray_encoding is not None:
+            enc = self._get_ray_encoding(ray_encoding, view_directions)
+        return _fused_extract_mesh(
+            feature_grid, self.get_decoder_params(), [int(v) for v in lattice_size], level=level, gain=self.gain,
+            mask_out_of_bounds_samples=self.mask_out_of_bounds_samples, grid_sizes=grid_sizes, with_normals=with_normals,
+            rays_encoding=enc, color_grid=color_feature_grid, color_grid_sizes=color_grid_sizes)
 
     @torch.no_grad()
     def clip_rays(self, rays: Rays, scaffold=None, pad: float = 0.5):
