@@ -123,6 +123,45 @@ LP_DEV f32x4 dw_quadrant_bf(const char* wave0b, int x_off, int y_off, int v0, in
   }
   return acc;
 }
+// The same products over the NV source waves [v0, v0 + NV), unrolled and software-pipelined (round 9): the loop above reads b2, a1 ->
+// two products -> reads b1 -> two products -> reads a2 -> one product, three LDS round trips per source wave that a 16-cycle product
+// hides nothing of, and the four waves of a workgroup run the stretch together between two barriers.  Here the eight
+// ds_read_b64_tr_b16 of source wave v + 1 are issued before the products of wave v, and all four operands of a wave before its first
+// product: one exposed round trip per round instead of 3 NV, for at most 16 more transient registers.  Every product keeps its
+// operands and its place in its accumulator's chain: the sums are bit-identical to the loop's.
+// (The transposed-march kernel keeps the loop: its register allocation was tuned around it.  So do the 32-channel instantiations on a
+// generic grid-list, PIPE = false: pipelined they spill 9 to 24 registers more than with the loop; the spilled registers of all
+// instantiations together fall -- profiles/r09_lds_waits_static.txt.)
+template <int STRIDE_BYTES, int NV, bool PIPE = true>
+LP_DEV f32x4 dw_quadrant_bf_pipe(const char* wave0b, int x_off, int y_off, int v0, f32x4 acc, f32x4& acc_db, unsigned onehot, bool do_db = true) {
+  if constexpr (!PIPE) return dw_quadrant_bf<STRIDE_BYTES>(wave0b, x_off, y_off, v0, v0 + NV, acc, acc_db, onehot, do_db);
+  const u32x4_t oh = {onehot, onehot, onehot, onehot};
+  const char* base = wave0b + v0 * STRIDE_BYTES;
+  u32x4_t b2 = limb_tile_operand(base + y_off + LT_LIMB);
+  u32x4_t a1 = limb_tile_operand(base + x_off);
+  u32x4_t b1 = limb_tile_operand(base + y_off);
+  u32x4_t a2 = limb_tile_operand(base + x_off + LT_LIMB);
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    u32x4_t nb2 = b2, na1 = a1, nb1 = b1, na2 = a2;
+    if (v + 1 < NV) {
+      const char* nxt = base + (v + 1) * STRIDE_BYTES;
+      nb2 = limb_tile_operand(nxt + y_off + LT_LIMB);
+      na1 = limb_tile_operand(nxt + x_off);
+      nb1 = limb_tile_operand(nxt + y_off);
+      na2 = limb_tile_operand(nxt + x_off + LT_LIMB);
+    }
+    LP_SCHED_FENCE();  // (the reads of wave v + 1 stay above the products of wave v)
+    if (do_db) acc_db = LP_MFMA16B(oh, b2, acc_db);  // (wave-uniform)
+    acc = LP_MFMA16B(a1, b2, acc);
+    if (do_db) acc_db = LP_MFMA16B(oh, b1, acc_db);
+    acc = LP_MFMA16B(a1, b1, acc);
+    acc = LP_MFMA16B(a2, b1, acc);
+    LP_SCHED_FENCE();
+    b2 = nb2; a1 = na1; b1 = nb1; a2 = na2;
+  }
+  return acc;
+}
 
 // =======================================================================================
 // Backward of the default shape with the recompute and the dX chains as bf16x3 on the bf16 matrix cores (lp_bf3.h).
@@ -170,6 +209,7 @@ template <int C, int GM, bool PLAIN, int NC, int NW, bool SEG = false, bool DUMP
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(const LpRendererArgs a, const MfmaParams mp) {
   constexpr int DXL = F32 ? 3 : 2;  // limbs of the gradient operand of the dX chains
   constexpr bool DWB = !F32;        // weight gradients on the bf16 pipe (two-limb tiles)
+  constexpr bool QPIPE = !(C == 32 && GM == GM_GENERIC);  // software-pipelined quadrant rounds (see dw_quadrant_bf_pipe)
   using M = Lds;
   using L = LdsBf3<C>;
   using R = LdsBf3Rm<C>;
@@ -530,7 +570,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       for (int q = 0; q < 16; ++q) dsum[q] += dhc[q];
       if (want_params) {
         lds_barrier();
-        if constexpr (DWB) dq_c1 = dw_quadrant_bf<B::PER_WAVE * 4>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, v0 + 4, dq_c1, dq_b, onehot(0));
+        if constexpr (DWB) dq_c1 = dw_quadrant_bf_pipe<B::PER_WAVE * 4, 4, QPIPE>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, dq_c1, dq_b, onehot(0));
         else dq_c1 = dw_quadrant<B::PER_WAVE>(wave0, a_off, b_off, v0, v0 + 4, dq_c1, db_c1);
         lds_barrier();
       }
@@ -557,7 +597,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       }
       if (want_params) {
         lds_barrier();
-        if constexpr (DWB) dq_o1 = dw_quadrant_bf<B::PER_WAVE * 4>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, v0 + 4, dq_o1, dq_b, onehot(1));
+        if constexpr (DWB) dq_o1 = dw_quadrant_bf_pipe<B::PER_WAVE * 4, 4, QPIPE>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, dq_o1, dq_b, onehot(1));
         else dq_o1 = dw_quadrant<B::PER_WAVE>(wave0, a_off, b_off, v0, v0 + 4, dq_o1, db_o1);
         lds_barrier();
       }
@@ -582,7 +622,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       }
       if (want_params) {
         lds_barrier();
-        if constexpr (DWB) dq_t2 = dw_quadrant_bf<B::PER_WAVE * 4>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, v0 + 4, dq_t2, dq_b, onehot(2));
+        if constexpr (DWB) dq_t2 = dw_quadrant_bf_pipe<B::PER_WAVE * 4, 4, QPIPE>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, dq_t2, dq_b, onehot(2));
         else dq_t2 = dw_quadrant<B::PER_WAVE>(wave0, a_off, b_off, v0, v0 + 4, dq_t2, db_t2);
       }
 #pragma unroll
@@ -612,7 +652,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
       }
       if (want_params) {
         lds_barrier();
-        if constexpr (DWB) dq_t1 = dw_quadrant_bf<B::PER_WAVE * 4>(reinterpret_cast<const char*>(wave0), (C == 16) ? xq_off - 32 * mi : xq_off, yq_off, t1_v0, t1_v1, dq_t1, dq_b, onehot(3));
+        if constexpr (DWB) dq_t1 = dw_quadrant_bf_pipe<B::PER_WAVE * 4, (C == 16 ? 2 : 4), QPIPE>(reinterpret_cast<const char*>(wave0), (C == 16) ? xq_off - 32 * mi : xq_off, yq_off, t1_v0, dq_t1, dq_b, onehot(3));
         else dq_t1 = dw_quadrant<B::PER_WAVE>(wave0, a_off_t1, b_off, t1_v0, t1_v1, dq_t1, db_t1);
         lds_barrier();
       }
@@ -673,7 +713,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) renderer_bwd_bf3(con
         limb_tile_store<2>(xrow, enc);
         limb_tile_store<2>(yrow, dsum);
         lds_barrier();
-        dq_c1 = dw_quadrant_bf<B::PER_WAVE * 4>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, v0 + 4, dq_c1, dq_b, 0u, false);
+        dq_c1 = dw_quadrant_bf_pipe<B::PER_WAVE * 4, 4, QPIPE>(reinterpret_cast<const char*>(wave0), xq_off, yq_off, v0, dq_c1, dq_b, 0u, false);
       } else {
         tile_store_fm(xt, r, h, enc);
         tile_store_fm(yt, r, h, dsum);
