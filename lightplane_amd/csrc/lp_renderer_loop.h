@@ -380,6 +380,9 @@ __global__ void __launch_bounds__(256, (NB == 1 && MT <= 2 && MH <= 1 && !WC) ? 
     const float2 e2 = *reinterpret_cast<const float2*>(a.neg_log_t_ckpt + (rid * n_ckpt + n_ckpt - 1) * 2);
     s_last_w = __builtin_amdgcn_readfirstlane((int)e2.x);
     s_last_w = s_last_w < 0 ? 0 : (s_last_w > s_tot - 1 ? s_tot - 1 : s_last_w);
+    // a wave without a ray (part-filled last workgroup) read ray 0's pair: the forward left such a wave at sample 0, and it must not
+    // make its siblings start behind their own last samples
+    if (!__builtin_amdgcn_readfirstlane((int)valid)) s_last_w = 0;
     nlt_lo = e2.y;
   }
   if (lane == 0) ts[0] = (float)s_last_w;

@@ -534,11 +534,17 @@ def lightplane_renderer_naive(
     color_grid=None,
     grid_sizes=None,
     color_grid_sizes=None,
+    last_sample: Optional[torch.Tensor] = None,
     **_ignored,
 ):
     """Oracle Renderer; same call signature and returns as the reference's
     ``lightplane_renderer_naive`` (naive_renderer.py:39-60):
-    ``(ray_length_render [N], negative_log_transmittance [N], feature_render [N, color_chn])``."""
+    ``(ray_length_render [N], negative_log_transmittance [N], feature_render [N, color_chn])``.
+
+    ``last_sample`` (int64 ``[N]``; not in the reference): the TRUNCATED march of early ray termination -- sample ``s`` of ray ``r``
+    contributes only if ``s <= last_sample[r]``.  One mask on ``opacity * delta`` does it: a masked sample adds nothing to -log T, so
+    its weight ``T_{s-1} - T_s`` is exactly 0 and no gradient passes through it; the returned -log T is the value at the last
+    contributing sample.  ``None`` (or ``S_tot - 1`` everywhere) is the full march, bit for bit."""
     grids = _as_grid_list(grid, grid_sizes)
     color_grids = None if color_grid is None else _as_grid_list(color_grid, color_grid_sizes)
     n_rays = rays.directions.shape[0]
@@ -560,7 +566,11 @@ def lightplane_renderer_naive(
         mask_out_of_bounds_samples=mask_out_of_bounds_samples, noise=noise, scaffold=scaffold,
         color_grids=color_grids, contract_coords=contract_coords,
     )
-    nlt = torch.cumsum(torch.nn.functional.pad(opacity * delta, (1, 0)), dim=-1)
+    od = opacity * delta
+    if last_sample is not None:
+        contributes = torch.arange(tot, device=od.device)[None, :] <= last_sample.to(od.device).long()[:, None]
+        od = torch.where(contributes, od, torch.zeros_like(od))
+    nlt = torch.cumsum(torch.nn.functional.pad(od, (1, 0)), dim=-1)
     if _VALUE_RECORDER is not None:
         _VALUE_RECORDER.nlt = nlt.detach()
     transmittance = torch.exp(-nlt)
@@ -569,6 +579,39 @@ def lightplane_renderer_naive(
     feature = (color * w[..., None]).sum(dim=-2)
     feature = feature[..., : decoder_params.color_chn]
     return ray_length, nlt[:, -1], feature
+
+
+class EarlyStop(NamedTuple):
+    """``early_stop_index``'s result, one entry per group of consecutive rays."""
+    index: torch.Tensor          # [G] int64: the last sample the group marches
+    margin_reached: torch.Tensor  # [G]: the group's smallest -log T at ``index`` minus the threshold (inf where the group never stops)
+    margin_before: torch.Tensor   # [G]: the threshold minus the group's smallest -log T one sample earlier (inf for ``index`` 0)
+
+
+def early_stop_index(neg_log_t_cum: torch.Tensor, stop_neg_log_t: float, group: int) -> EarlyStop:
+    """The march rule of early ray termination (``stop_transmittance``; not in the reference), on the -log T after every sample
+    ``neg_log_t_cum [R, S_tot]`` of the FULL march: consecutive rays form groups of ``group`` (the last one may be part-filled; the rays
+    it lacks do not vote); a group's index is the first ``s`` at which EVERY ray of the group has ``-log T >= stop_neg_log_t``, else
+    ``S_tot - 1``.  Two margins decide that index: how far the group's smallest -log T is above the threshold AT the index, and how far
+    below one sample EARLIER (-log T never falls along a ray, so every earlier sample is at least as far below).  An implementation whose
+    -log T is off by less than both margins takes the same index.  A group that never reaches the threshold, or only at the last sample (where the
+    march ends whatever the vote says), has no first margin (inf), a group that stops at sample 0 no second one."""
+    nlt = neg_log_t_cum.detach()
+    n_rays, s_tot = nlt.shape
+    n_groups = (n_rays + group - 1) // group
+    index = torch.empty(n_groups, dtype=torch.int64)
+    reached = torch.empty(n_groups, dtype=nlt.dtype)
+    before = torch.empty(n_groups, dtype=nlt.dtype)
+    for g in range(n_groups):
+        low = nlt[g * group:(g + 1) * group].amin(dim=0)          # [S_tot]: the ray that holds the group back, per sample
+        done = (low >= stop_neg_log_t).nonzero()
+        stops = done.numel() > 0
+        s = int(done[0]) if stops else s_tot - 1
+        index[g] = s
+        # (at the last sample the march ends whatever the vote says: nothing is decided there)
+        reached[g] = low[s] - stop_neg_log_t if stops and s < s_tot - 1 else math.inf
+        before[g] = stop_neg_log_t - low[s - 1] if s > 0 else math.inf
+    return EarlyStop(index, reached, before)
 
 
 # ======================================================================================

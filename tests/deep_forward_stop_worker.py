@@ -9,6 +9,11 @@ runs in this process of its own and the test waits for it under a time limit.
                -- two wavefronts that stop, at different samples, next to one that marches to the end and a mixed one;
   workgroup 1: 256 saturating rays, ordered by density -- every wave stops, the workgroup leaves the sample loop early and together;
   workgroup 2: 44 saturating rays -- the same exit, taken with waves that never held a ray.
+
+The same launch is then PROVEN against the truncated fp64 oracle (tests/test_gpu_parity.py ``forced_oracle_check``, with a non-zero
+upstream gradient on -log T as well): the backward's own ReLU decisions and last marched samples forced onto the oracle, every output and
+gradient at 1e-4; and every 64-ray group's last sample is the one ``oracle.early_stop_index`` expects wherever the oracle's two decisive
+margins clear the tie bar of tests/early_stop_cases.py (the rays are picked by the kernels here, not solved for margins).
 """
 import os
 import sys
@@ -22,8 +27,10 @@ import torch
 
 import lightplane_amd as lp
 from lightplane_amd import _lib
+from oracle import lightplane_oracle as O
+from tests import early_stop_cases as E
 from tests.synth import RendererCase
-from tests.test_gpu_parity import _rays_to
+from tests.test_gpu_parity import FORCED_EVENTS, _rays_to, forced_oracle_check, has_dump_twin
 
 EPS = 1e-5
 N_RAYS = 556
@@ -94,6 +101,7 @@ def main(layers, seed, family):
     assert len(idx) == N_RAYS and len(torch.unique(idx)) == N_RAYS
     d["rays"] = d["rays"][idx]
     g_len, g_nlt, g_feat = d["upstream"]
+    up_all = (g_len[idx], g_nlt[idx], g_feat[idx])
     d["upstream"] = (g_len[idx], torch.zeros_like(g_nlt[idx]), g_feat[idx])  # no loss on -log T
 
     out0, _, gr0 = _run(d, dev, _lib.LP_KERNEL_AUTO)
@@ -124,6 +132,24 @@ def main(layers, seed, family):
     for (nm, a), (_, b) in zip(gr1, gr0):
         scale = float(b.abs().max()) + 1e-30
         assert float((a - b).abs().max()) / scale <= 1e-3, nm
+
+    # the proof: this forward, the shape-generic backward (64-ray groups), against the truncated fp64 oracle
+    d["upstream"] = up_all
+    assert has_dump_twin(d, stop_transmittance=EPS)
+    forced_oracle_check(f"early-stop deep forward {layers}", d, dev, stop_transmittance=EPS)
+    s_last = s_last.long()
+    assert FORCED_EVENTS[-1]["stopped_rays"] == int((s_last < S - 1).sum()), "the backward contributed other samples than the forward marched"
+    nlt = E.neg_log_t_cum(d)
+    want = O.early_stop_index(nlt, -np.log(EPS), 64)
+    returned = nlt.gather(1, s_last[:, None])[:, 0]
+    bar = E.TIE_FACTOR * E.OUTPUT_BAR * float(returned.max())
+    decided = (want.margin_reached >= bar) & (want.margin_before >= bar)
+    got = s_last[::64]
+    print(f"{layers}: oracle's last samples {want.index.tolist()}, margins reached {[round(float(v), 3) for v in want.margin_reached]} / before "
+          f"{[round(float(v), 3) for v in want.margin_before]}, tie bar {bar:.4f}: {int(decided.sum())} of {len(got)} groups decided", flush=True)
+    # (the two groups of workgroup 0 that never stop are decided by construction: the comparison has to reach groups that do stop)
+    assert int((decided & (want.index < S - 1)).sum()) >= 3, "the oracle's margins decide too few stopping groups for the comparison to mean anything"
+    assert torch.equal(got[decided], want.index[decided]), (got.tolist(), want.index.tolist())
     print("DEEP_STOP_OK", flush=True)
 
 

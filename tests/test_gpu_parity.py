@@ -217,9 +217,8 @@ def assert_grad_close(name, got, want, entries_per_sample, tol=1e-4, want64=None
 
 def has_dump_twin(d, kernel=_lib.LP_KERNEL_AUTO, **extra):
     """The kernel that runs this case has a DUMP twin (every family since round 6: tuned, layer-looped, shape-generic; not the tuned
-    family's eight-wave workgroups, not LP_ARITH_FP32, not early termination -- the oracle marches every sample)."""
-    if extra.get("stop_transmittance"):
-        return False
+    family's eight-wave workgroups, not LP_ARITH_FP32).  Early termination keeps its twin: the flag word of the dump says which samples
+    contributed, and ``oracle_forced`` truncates the oracle's march there."""
     from lightplane_amd.renderer import relu_dump_words
     return relu_dump_words(d["rays"], d["grids"], d["decoder"], color_grid=d.get("color_grids"),
                            num_samples_inf=d["cfg"].get("num_samples_inf", 0), kernel=kernel) > 0
@@ -250,13 +249,14 @@ def unpack_relu_dump(dump, widths, words_per_site=1):
     return masks, d[..., -1] != 0
 
 
-def run_hip_renderer_with_dump(d, dev, kernel=_lib.LP_KERNEL_AUTO, **extra):
+def run_hip_renderer_with_dump(d, dev, kernel=_lib.LP_KERNEL_AUTO, runner=None, **extra):
     """The production backward AND the same backward through the DUMP twin of its kernel (ReLU decisions recorded).
-    Returns (production results, dump, words per site)."""
+    Returns (production results, dump, words per site).  ``runner``: the launch, if not ``run_hip_renderer`` (same arguments and returns)."""
     from lightplane_amd.renderer import relu_dump_recorder
-    prod = run_hip_renderer(d, dev, kernel, **extra)
+    runner = runner or run_hip_renderer
+    prod = runner(d, dev, kernel, **extra)
     with relu_dump_recorder() as rec:
-        twin = run_hip_renderer(d, dev, kernel, **extra)
+        twin = runner(d, dev, kernel, **extra)
     assert rec.dump is not None, "the backward did not go through the dump hook"
     # the twin is the same template with stores added: same arithmetic, so its gradients equal the production launch's up to
     # the order of the fp32 atomics
@@ -277,25 +277,38 @@ FORCED_TIE_K = 1  # a unit the kernel decided against the fp64 oracle's sign has
                   # product of 16-64 terms whose inputs carry the round-off of up to seven earlier layers (profiles/r06_forced_oracle.json)
 
 
-def oracle_forced(d, dump, idx=None, chunk=2048, dtype=torch.float64, words_per_site=1):
+def oracle_forced(d, dump, idx=None, chunk=2048, dtype=torch.float64, words_per_site=1, epilogue=None):
     """fp64 oracle forward + backward over the rays ``idx`` (default all), in chunks, with the kernel's own ReLU decisions
     (``dump`` [n_rays_total, S, W] from the DUMP twin) forced onto every unit of every sample the kernel visited.
     Returns (outs, grad_params, grad_encoding, grad_grids, grad_color_grids, stats) -- stats: n_forced = units whose forced branch
     differs from the oracle's own, max_forced_margin = the largest relative |pre-activation| among them, n_near_units = units of the
-    visited samples within FORCED_TIE_K * TIE_EPS of zero (the pool a forced unit has to come from), n_units."""
+    visited samples within FORCED_TIE_K * TIE_EPS of zero (the pool a forced unit has to come from), n_units, last_sample = per ray the
+    last sample the kernel let contribute.
+
+    Early termination: the oracle marches what the kernel marched.  Per ray the last sample whose flag word is 1 (contributed) becomes the
+    oracle's ``last_sample``; the flags have to say "contributed" for every sample up to it and for none behind it.
+
+    ``epilogue``: maps the oracle's three outputs to the three the launch returns (the module front end's background and alpha) before
+    they meet the upstream gradients."""
     import copy
     rays = d["rays"] if idx is None else d["rays"][idx]
     up = d["upstream"] if idx is None else tuple(u[idx] for u in d["upstream"])
     dump = dump if idx is None else dump[idx.to(dump.device)]
     widths = relu_site_widths(d)
     masks, visited = unpack_relu_dump(dump, widths, words_per_site)
+    contributed = (dump[..., -1] == 1).cpu()
+    s_tot = contributed.shape[1]
+    last = (contributed * torch.arange(1, s_tot + 1)).amax(dim=1) - 1                      # largest s with flag 1 (-1: none)
+    assert bool((last >= 0).all()), f"{int((last < 0).sum())} rays without a contributing sample in the dump"
+    assert bool((contributed == (torch.arange(s_tot)[None, :] <= last[:, None])).all()), "the contributing samples of a ray are not its first ones"
+    truncated = bool((last < s_tot - 1).any())
     dec = d["decoder"]
     params = dec.mlp_params.to(dtype).clone().requires_grad_(True)
     grids = [g.to(dtype).clone().requires_grad_(True) for g in d["grids"]]
     cgrids = None if d.get("color_grids") is None else [g.to(dtype).clone().requires_grad_(True) for g in d["color_grids"]]
     scaffold = None if d.get("scaffold") is None else d["scaffold"].to(dtype)
     outs, g_enc = [[], [], []], []
-    stats = dict(n_forced=0, max_forced_margin=0.0, n_near_units=0, n_units=0)
+    stats = dict(n_forced=0, max_forced_margin=0.0, n_near_units=0, n_units=0, last_sample=last)
     old_threads = torch.get_num_threads()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     try:
@@ -312,12 +325,15 @@ def oracle_forced(d, dump, idx=None, chunk=2048, dtype=torch.float64, words_per_
             # moves a pre-activation by up to 1e-5 of its site's largest on a 128-cell axis: the forced margins of the cfg-4 block
             # measured 7e-6 .. 9.5e-6 that way, 3 .. 8 x what the decoder's own arithmetic explains.)
             with O.geometry_dtype(torch.float32), O.relu_mask_forcer([m[lo:lo + chunk] for m in masks], keep, near_eps=FORCED_TIE_K * TIE_EPS) as forcer:
-                out = O.lightplane_renderer_naive(r, grids, dd, scaffold=scaffold, color_grid=cgrids, **d["cfg"])
+                out = O.lightplane_renderer_naive(r, grids, dd, scaffold=scaffold, color_grid=cgrids,
+                                                  last_sample=last[lo:lo + chunk] if truncated else None, **d["cfg"])
             assert forcer.k == len(widths), f"the oracle evaluated {forcer.k} ReLU sites, the dump holds {len(widths)}"
             stats["n_forced"] += forcer.n_forced
             stats["n_near_units"] += forcer.n_near_units
             stats["n_units"] += forcer.n_units
             stats["max_forced_margin"] = max(stats["max_forced_margin"], forcer.max_forced_margin)
+            if epilogue is not None:
+                out = epilogue(out)
             u = [x[lo:lo + chunk].to(dtype) for x in up]
             ((out[0] * u[0]).sum() + (out[1] * u[1]).sum() + (out[2] * u[2]).sum()).backward()
             for k in range(3):
@@ -332,7 +348,8 @@ def oracle_forced(d, dump, idx=None, chunk=2048, dtype=torch.float64, words_per_
 FORCED_EVENTS = []  # one record per forced-oracle check; printed by conftest.pytest_terminal_summary
 
 
-def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_lib.LP_KERNEL_AUTO, return_results=False, **extra):
+def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_lib.LP_KERNEL_AUTO, return_results=False, runner=None,
+                        epilogue=None, **extra):
     """THE PROOF behind the ReLU-flip allowance (round-4 review, next 2): the production backward's own ReLU decisions, read
     back from the DUMP twin of its kernel, are forced onto the fp64 oracle; then EVERY entry of every gradient family and every
     output has to meet the north_star bar outright -- no allowance, no second oracle, no mask.  Whatever separated the kernel
@@ -344,21 +361,27 @@ def forced_oracle_check(name, d, dev, idx=None, tol=1e-4, chunk=2048, kernel=_li
     that close to zero.
 
     ``return_results``: return (n_forced, the production launch's results as run_hip_renderer returns them, the forced fp64 oracle's
-    (outs, grad_params, grad_encoding, grad_grids, grad_color_grids)) instead of n_forced alone, once everything above has passed."""
-    prod, dump, wps = run_hip_renderer_with_dump(d, dev, kernel, **extra)
+    (outs, grad_params, grad_encoding, grad_grids, grad_color_grids)) instead of n_forced alone, once everything above has passed.
+
+    Early termination (``stop_transmittance=`` among ``extra``) needs nothing more: ``oracle_forced`` reads from the dump which samples
+    contributed and truncates the oracle's march there.  ``runner`` / ``epilogue``: another launch of the same kernels (the module front
+    end) and the map from the oracle's outputs to that launch's (``run_hip_renderer_with_dump``, ``oracle_forced``); the second output is
+    then reported as "alpha"."""
+    prod, dump, wps = run_hip_renderer_with_dump(d, dev, kernel, runner=runner, **extra)
     out, gp, ge, gg, gc = prod
-    f_out, f_gp, f_ge, f_gg, f_gc, st = oracle_forced(d, dump, idx, chunk=chunk, words_per_site=wps)
+    f_out, f_gp, f_ge, f_gg, f_gc, st = oracle_forced(d, dump, idx, chunk=chunk, words_per_site=wps, epilogue=epilogue)
     sel = (lambda t: t) if idx is None else (lambda t: t[idx.to(t.device)])
     worst = {}
-    for nm, a, b in [("ray_length", sel(out[0]), f_out[0]), ("neg_log_t", sel(out[1]), f_out[1]), ("feature", sel(out[2]), f_out[2]),
-                     ("grad_mlp_params", gp, f_gp), ("grad_encoding", sel(ge), f_ge)] + \
+    for nm, a, b in [("ray_length", sel(out[0]), f_out[0]), ("neg_log_t" if epilogue is None else "alpha", sel(out[1]), f_out[1]),
+                     ("feature", sel(out[2]), f_out[2]), ("grad_mlp_params", gp, f_gp), ("grad_encoding", sel(ge), f_ge)] + \
             [(f"grad_grid{i}", a, b) for i, (a, b) in enumerate(zip(gg, f_gg))] + \
             ([] if gc is None else [(f"grad_color_grid{i}", a, b) for i, (a, b) in enumerate(zip(gc, f_gc))]):
         worst[nm] = _rel_err(a, b.numpy())
     visited = int((dump[..., -1] != 0).sum()) if idx is None else int((dump[idx.to(dump.device)][..., -1] != 0).sum())
     n_forced = st["n_forced"]
     FORCED_EVENTS.append(dict(name=name, forced_units=n_forced, visited_samples=visited, max_forced_margin=float(f"{st['max_forced_margin']:.3e}"),
-                              near_tie_units=st["n_near_units"], units=st["n_units"], worst={k: float(f"{v:.3e}") for k, v in worst.items()}))
+                              near_tie_units=st["n_near_units"], units=st["n_units"], worst={k: float(f"{v:.3e}") for k, v in worst.items()},
+                              stopped_rays=int((st["last_sample"] < dump.shape[1] - 1).sum())))
     print(f"forced-oracle {name}: {n_forced} ReLU units forced against the fp64 oracle's own sign over {visited} visited samples "
           f"(largest forced |pre-activation| / site max {st['max_forced_margin']:.2e}; the oracle has {st['n_near_units']} of {st['n_units']} units "
           f"within {FORCED_TIE_K * TIE_EPS:g}); max err / scale: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
