@@ -9,7 +9,7 @@ GPU boxes have no datasets.
 
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
-                                            [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0]
+                                            [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0] [--modular]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -39,6 +39,11 @@ float32 row ``x y z | r g b | opacity`` per point.
 ``--export-mesh FILE.ply`` writes the fitted scene as a triangle mesh after the fit: ``renderer.extract_mesh`` -- the fused opacity
 lattice of ``--mesh-size``^3 points, marching cubes on the GPU at the opacity ``--mesh-level`` (``lp.marching_cubes``) and the fused
 point decoder for the vertex colours seen along ``-z`` -- and the file is an ASCII PLY with positions, normals and 8-bit colours.
+
+``--modular`` renders the training batches through the modular march instead of the fused Renderer: ``renderer.ray_samples`` places
+the samples, ``renderer.eval_decoder_at_points`` (``lp.lightplane_eval_mlp``) decodes them and ``lp.composite_samples`` integrates
+them -- the same fit, with the per-sample tensors in the caller's hands (the JSON line gains ``modular``).  The held-out evaluation
+stays on the fused Renderer, so the PSNR also says that the two paths agree.  Without the flag the run is untouched.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -98,9 +103,18 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None,
     return -10.0 * math.log10(mse)
 
 
+def render_modular(renderer, rays, grids, scaffold=None):
+    """``(alpha, rgb)`` of ``renderer(rays, grids)`` through ray_samples -> the decoder at points -> composite_samples (background 0)"""
+    samples = renderer.ray_samples(rays)
+    opacity, color = renderer.eval_decoder_at_points(samples.points, rays.grid_idx, None, grids, scaffold=scaffold,
+                                                     directions=rays.directions)
+    _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
+    return 1.0 - torch.exp(-nlt), rgb
+
+
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
         upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False,
-        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None):
+        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None, modular=False):
     """``on_fitted(renderer, grids)``: called after the last step, before the exports, with the fitted module and its planes"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
@@ -141,7 +155,10 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
             rays, hit = renderer.clip_rays(rays, scaffold)
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
-        _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
+        if modular:
+            alpha, rgb = render_modular(renderer, rays, list(grids), scaffold)
+        else:
+            _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -154,6 +171,8 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5,
            "heldout_psnr_db": heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold, clip_rays),
            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
+    if modular:
+        out.update(modular=True)
     if upsample_steps:
         out.update(upsample_steps=upsample_steps, start_res=start_res, psnr_at_upsample_db=psnr_at_upsample,
                    grid_shapes=[list(g.shape) for g in grids])
@@ -232,11 +251,13 @@ def main(argv=None):
     ap.add_argument("--mesh-size", type=int, default=64, help="points per axis of the lattice the mesh is extracted from")
     ap.add_argument("--mesh-level", type=float, default=1.0, help="opacity of the extracted level set")
     ap.add_argument("--res", type=int, default=64, help="resolution of the planes")
+    ap.add_argument("--modular", action="store_true",
+                    help="render the training batches through ray_samples -> eval_decoder_at_points -> composite_samples")
     a = ap.parse_args(argv)
     out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
               upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
               scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays,
-              export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level)
+              export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level, modular=a.modular)
     print(json.dumps(out))
     return out
 

@@ -145,6 +145,24 @@ class LpMeshArgs(C.Structure):
     ]
 
 
+class LpRaySamplesArgs(C.Structure):  # include/lightplane_hip_samples.h
+    _fields_ = [
+        ("rays", LpRays), ("march", LpMarch), ("points", C.c_void_p), ("depths", C.c_void_p), ("deltas", C.c_void_p),
+        ("grad_points", C.c_void_p), ("grad_depths", C.c_void_p), ("grad_deltas", C.c_void_p),
+        ("grad_origins", C.c_void_p), ("grad_directions", C.c_void_p), ("grad_near", C.c_void_p), ("grad_far", C.c_void_p),
+    ]
+
+
+class LpCompositeArgs(C.Structure):  # include/lightplane_hip_samples.h
+    _fields_ = [
+        ("opacity", C.c_void_p), ("features", C.c_void_p), ("depths", C.c_void_p), ("deltas", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("channels", C.c_int32),
+        ("ray_length", C.c_void_p), ("neg_log_t", C.c_void_p), ("feature", C.c_void_p), ("weights", C.c_void_p),
+        ("grad_ray_length", C.c_void_p), ("grad_neg_log_t", C.c_void_p), ("grad_feature", C.c_void_p), ("grad_weights", C.c_void_p),
+        ("grad_opacity", C.c_void_p), ("grad_features", C.c_void_p), ("grad_depths", C.c_void_p), ("grad_deltas", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -165,6 +183,9 @@ EXPORTS = (
     "lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points",
     "lp_mesh_count", "lp_mesh_emit",  # (+ lp_mesh_workspace_bytes, which returns int64_t)
 )
+
+#: every symbol include/lightplane_hip_samples.h declares (a header and a table of their own: the ones above stay as they are)
+SAMPLES_EXPORTS = ("lp_ray_samples_forward", "lp_ray_samples_backward", "lp_composite_forward", "lp_composite_backward")
 
 
 class LightplaneHipError(RuntimeError):
@@ -268,11 +289,17 @@ def lib() -> C.CDLL:
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(LpMeshArgs), C.c_void_p, C.c_int64, C.c_void_p]
+    # sample placement and compositing of the march (include/lightplane_hip_samples.h): args, stream
+    for name, st in zip(SAMPLES_EXPORTS, (LpRaySamplesArgs, LpRaySamplesArgs, LpCompositeArgs, LpCompositeArgs)):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(st), C.c_void_p]
     L.lp_abi_sizeof.restype = C.c_int
     L.lp_abi_sizeof.argtypes = [C.c_int]
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
                       (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
-                      (14, LpPointGridArgs), (16, LpMeshArgs)):  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
+                      (14, LpPointGridArgs), (16, LpMeshArgs),  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
+                      (18, LpRaySamplesArgs), (20, LpCompositeArgs)):  # (nor 17, 19 and 21: lightplane_hip_samples.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

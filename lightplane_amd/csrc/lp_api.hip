@@ -274,9 +274,12 @@ static int check_scaffold_for_grid(const char* what, const LpGrid& s, const LpGr
   return LP_OK;
 }
 
-// a batch of n_rays x n_pts points: one wavefront per 64 of them, and a launch has at most 2^31 workgroups
-static int check_point_batch(const char* what, int64_t n_rays, int64_t n_pts) {
+// a batch of n_rays x n_pts points: one wavefront per 64 of them, and a launch has at most 2^31 workgroups.  `below_2_31`: the kernels
+// index the points themselves with 32 bits (the march in pieces, one wavefront per ray), so their number has to stay below 2^31.
+static int check_point_batch(const char* what, int64_t n_rays, int64_t n_pts, bool below_2_31 = false) {
   if (n_rays < 0 || n_pts < 0) return fail(what, LP_EINVAL, "n_rays %lld / n_pts %lld < 0", (long long)n_rays, (long long)n_pts);
+  if (below_2_31 && n_pts > 0 && n_rays > (((int64_t)1 << 31) - 1) / n_pts)
+    return fail(what, LP_EUNSUPPORTED, "n_rays %lld x %lld samples per ray: has to stay below 2^31", (long long)n_rays, (long long)n_pts);
   if (n_pts > 0 && n_rays > (((int64_t)1 << 37) - 64) / n_pts)
     return fail(what, LP_EUNSUPPORTED, "%lld x %lld points are more than 2^31 wavefronts", (long long)n_rays, (long long)n_pts);
   return LP_OK;
@@ -664,6 +667,73 @@ static int check_mesh(const char* what, const LpMeshArgs* args, const void* work
   return LP_OK;
 }
 
+// everything lp_ray_samples_forward / _backward check.  Messages begin with the field (no entry-point prefix).
+static int check_ray_samples(const LpRaySamplesArgs* args, bool backward) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  const LpRays& r = args->rays;
+  if ((rc = check_ray_pointers(nullptr, r, false))) return rc;
+  if ((rc = check_aligned("rays.encoding", r.encoding))) return rc;
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, grad_points);
+  LP_ALIGNED(*args, grad_depths);
+  LP_ALIGNED(*args, grad_deltas);
+  LP_ALIGNED(*args, grad_origins);
+  LP_ALIGNED(*args, grad_directions);
+  LP_ALIGNED(*args, grad_near);
+  LP_ALIGNED(*args, grad_far);
+  if ((rc = check_march(args->march))) return rc;
+  const int64_t S_tot = (int64_t)args->march.num_samples + args->march.num_samples_inf;
+  if ((rc = check_point_batch(nullptr, r.n_rays, S_tot, true))) return rc;
+  if (r.n_rays == 0) return LP_OK;
+  // (grid_idx and encoding are not read: check_ray_pointers' rule for the marchers does not apply)
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"rays.directions", r.directions, true}, {"rays.origins", r.origins, true}, {"rays.near_t", r.near_t, true},
+      {"rays.far_t", r.far_t, true},           {"points", args->points, !backward}, {"depths", args->depths, !backward},
+      {"deltas", args->deltas, !backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
+// everything lp_composite_forward / _backward check.  Messages begin with the field.
+static int check_composite(const LpCompositeArgs* args, bool backward) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  LP_ALIGNED(*args, opacity);
+  LP_ALIGNED(*args, features);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, ray_length);
+  LP_ALIGNED(*args, neg_log_t);
+  LP_ALIGNED(*args, feature);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, grad_ray_length);
+  LP_ALIGNED(*args, grad_neg_log_t);
+  LP_ALIGNED(*args, grad_feature);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_opacity);
+  LP_ALIGNED(*args, grad_features);
+  LP_ALIGNED(*args, grad_depths);
+  LP_ALIGNED(*args, grad_deltas);
+  if (args->n_samples < 1) return set_error(LP_EINVAL, "n_samples %d < 1", args->n_samples);
+  if ((rc = check_point_batch(nullptr, args->n_rays, args->n_samples, true))) return rc;
+  if (args->channels < 0 || args->channels > LP_MAX_WIDTH)
+    return set_error(LP_EUNSUPPORTED, "channels %d outside [0, %d]", args->channels, LP_MAX_WIDTH);
+  if (args->n_rays == 0) return LP_OK;
+  const bool feat = args->channels > 0;
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"opacity", args->opacity, true},          {"depths", args->depths, true},          {"deltas", args->deltas, true},
+      {"ray_length", args->ray_length, !backward}, {"neg_log_t", args->neg_log_t, !backward},
+      {"feature", args->feature, feat && !backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  if (feat && !args->features) return set_error(LP_ENULL, "features is NULL with channels = %d", args->channels);
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -713,6 +783,8 @@ int lp_abi_sizeof(int which) {
     case 12: return (int)sizeof(LpRayClipArgs);  // (and so does 11)
     case 14: return (int)sizeof(LpPointGridArgs);  // (and 13)
     case 16: return (int)sizeof(LpMeshArgs);  // (and 15)
+    case 18: return (int)sizeof(LpRaySamplesArgs);  // (and 17; this one and the next: lightplane_hip_samples.h)
+    case 20: return (int)sizeof(LpCompositeArgs);  // (and 19)
     default: return -1;
   }
 }
@@ -1088,6 +1160,30 @@ int lp_point_grad_points(const LpPointGridArgs* args, void* stream) {
   const int rc = check_point_grid("lp_point_grad_points", args, 3, a);
   if (rc != LP_OK) return rc;
   return point_grad_points_launch(a, (hipStream_t)stream);
+}
+
+int lp_ray_samples_forward(const LpRaySamplesArgs* args, void* stream) {
+  const int rc = check_ray_samples(args, false);
+  if (rc || args->rays.n_rays == 0) return rc;
+  return ray_samples_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_ray_samples_backward(const LpRaySamplesArgs* args, void* stream) {
+  const int rc = check_ray_samples(args, true);
+  if (rc || args->rays.n_rays == 0) return rc;
+  return ray_samples_launch(*args, true, (hipStream_t)stream);
+}
+
+int lp_composite_forward(const LpCompositeArgs* args, void* stream) {
+  const int rc = check_composite(args, false);
+  if (rc || args->n_rays == 0) return rc;
+  return composite_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_composite_backward(const LpCompositeArgs* args, void* stream) {
+  const int rc = check_composite(args, true);
+  if (rc || args->n_rays == 0) return rc;
+  return composite_launch(*args, true, (hipStream_t)stream);
 }
 
 int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream) {

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "../../include/lightplane_hip.h"
+#include "../../include/lightplane_hip_samples.h"
 
 namespace lp {
 
@@ -144,6 +145,9 @@ int64_t mesh_workspace_bytes(const LpGrid& shape);
 int mesh_count_launch(const LpMeshArgs& a, void* workspace, hipStream_t stream);
 int mesh_emit_launch(const LpMeshArgs& a, void* workspace, hipStream_t stream);
 const char* build_info_mesh();
+// sample placement and compositing of the ray march as ops of their own: lp_composite.hip (`a` checked by lp_api.hip; n_rays > 0)
+int ray_samples_launch(const LpRaySamplesArgs& a, bool backward, hipStream_t stream);
+int composite_launch(const LpCompositeArgs& a, bool backward, hipStream_t stream);
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -32,6 +32,7 @@ from . import _lib, config
 from .points import lightplane_eval_mlp as _fused_eval_mlp, lightplane_eval_mlp_opacity_only as _fused_eval_mlp_opacity_only
 from .renderer import _render, lightplane_renderer
 from .ray_clip import clip_rays_to_scaffold as _clip_rays_to_scaffold
+from .compositing import ray_samples as _ray_samples
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .mesh import extract_mesh as _fused_extract_mesh
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
@@ -366,6 +367,12 @@ class LightplaneRenderer(torch.nn.Module):
             raise NotImplementedError("clip_rays walks straight rays through the scaffold's cells; with contract_coords=True the "
                                       "Renderer bends them (MeRF contraction), so the clipped span would be wrong")
         return _clip_rays_to_scaffold(rays, scaffold, pad=pad)
+
+    def ray_samples(self, rays: Rays):
+        """``RaySamples(points, depths, deltas)`` of :func:`lightplane_amd.ray_samples` with the module's ``num_samples``,
+        ``num_samples_inf`` and ``disparity_at_inf``: the samples ``forward`` marches for ``rays`` (without jitter), for a decoder of
+        the caller's own and :func:`lightplane_amd.composite_samples`.  The points are not contracted."""
+        return _ray_samples(rays, self.num_samples, self.num_samples_inf, disparity_at_inf=self.disparity_at_inf)
 
     # -- ray encoding ---------------------------------------------------------------------
     def _get_ray_embedding(self, ray_directions: torch.Tensor) -> torch.Tensor:
