@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .grids import GridDesc
+from .params import mlp_numel
 
 LP_MAX_GRIDS = 8
 LP_MAX_LAYERS = 8
@@ -188,6 +188,58 @@ EXPORTS = (
 SAMPLES_EXPORTS = ("lp_ray_samples_forward", "lp_ray_samples_backward", "lp_composite_forward", "lp_composite_backward")
 
 
+def _signatures():
+    P, vp, i32, i64, f32 = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    ren, spl, tv_list = P(LpRendererArgs), P(LpSplatterArgs), P(LpGridList)
+    tv = (tv_list, vp, i32, i32)          # grid-list, HOST weight array, count, p
+    tv_grad = (vp, f32, vp, vp, i32)      # grad_loss, scale, grad, grad_list (HOST array), n_grad_list
+    return (
+        (("lp_version",), C.c_int, ()),
+        (("lp_last_error", "lp_build_info"), C.c_char_p, ()),
+        (("lp_abi_sizeof",), C.c_int, (C.c_int,)),
+        (("lp_renderer_forward", "lp_renderer_backward"), C.c_int, (ren, vp)),
+        (("lp_renderer_kernel_family", "lp_renderer_forward_family", "lp_renderer_backward_segments", "lp_renderer_relu_dump_words"),
+         C.c_int, (ren,)),
+        (("lp_renderer_forward_workspace_bytes",), i64, (ren,)),
+        (("lp_renderer_forward_ws", "lp_renderer_backward_relu_dump"), C.c_int, (ren, vp, i64, vp)),
+        (("lp_renderer_corner_rows",), C.c_int, (ren, vp, vp)),
+        (("lp_splatter_forward", "lp_splatter_backward", "lp_mlp_splatter_launch_shape"), C.c_int, (spl, vp)),
+        (("lp_splatter_kernel_family", "lp_mlp_splatter_relu_dump_words"), C.c_int, (spl,)),
+        (("lp_mlp_splatter_backward_relu_dump",), C.c_int, (spl, vp, i64, vp)),
+        (("lp_splatter_normalize",), C.c_int, (vp, vp, i64, i32, vp)),
+        (("lp_hash_randn",), C.c_int, (vp, vp, vp, i64, i32, vp)),
+        (("lp_ray_embedding_forward", "lp_ray_embedding_backward"), C.c_int, (P(LpRayEmbedArgs), vp)),
+        # total-variation regulariser
+        (("lp_grid_tv_workspace_bytes",), i64, (tv_list,)),
+        (("lp_grid_tv_forward",), C.c_int, tv + (vp, vp, i64, vp)),
+        (("lp_grid_tv_backward",), C.c_int, tv + tv_grad + (i32, vp)),
+        (("lp_grid_tv_fused",), C.c_int, tv + (vp, vp, i64) + tv_grad + (vp,)),
+        # resampling of a grid-list: source list, destination list, align_corners, HOST coefficient array (or NULL), ...
+        (("lp_grid_resample_forward",), C.c_int, (tv_list, tv_list, i32, vp, vp)),
+        (("lp_grid_resample_backward",), C.c_int, (tv_list, tv_list, i32, vp, i32, vp)),
+        # occupancy scaffold of a grid-list: args, result (, workspace, workspace bytes), stream
+        (("lp_scaffold_workspace_bytes",), i64, (P(LpScaffoldArgs),)),
+        (("lp_scaffold_opacity",), C.c_int, (P(LpScaffoldArgs), vp, vp)),
+        (("lp_scaffold_build",), C.c_int, (P(LpScaffoldArgs), vp, vp, i64, vp)),
+        # the decoder at arbitrary points: args, stream
+        (("lp_points_forward", "lp_points_backward"), C.c_int, (P(LpPointsArgs), vp)),
+        # rays clipped to the occupied span of a scaffold: args, near_out, far_out, hit_out, stream
+        (("lp_rays_clip",), C.c_int, (P(LpRayClipArgs), vp, vp, vp, vp)),
+        # gather / splat of a grid-list at arbitrary points: args, stream
+        (("lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points"), C.c_int, (P(LpPointGridArgs), vp)),
+        # triangle mesh of a lattice's level set: args, workspace, workspace bytes, stream
+        (("lp_mesh_workspace_bytes",), i64, (P(LpMeshArgs),)),
+        (("lp_mesh_count", "lp_mesh_emit"), C.c_int, (P(LpMeshArgs), vp, i64, vp)),
+        # sample placement and compositing of the march (include/lightplane_hip_samples.h): args, stream
+        (SAMPLES_EXPORTS[:2], C.c_int, (P(LpRaySamplesArgs), vp)),
+        (SAMPLES_EXPORTS[2:], C.c_int, (P(LpCompositeArgs), vp)),
+    )
+
+
+#: ``(names, restype, argtypes)`` of every export: what ``lib()`` sets on the loaded library
+SIGNATURES = _signatures()
+
+
 class LightplaneHipError(RuntimeError):
     """A C-ABI call returned a non-zero code."""
 
@@ -203,99 +255,10 @@ def lib() -> C.CDLL:
             "`python lightplane_amd/csrc/build.py` (there is no CPU / PyTorch fallback)."
         )
     L = C.CDLL(LIB_PATH)
-    L.lp_version.restype = C.c_int
-    L.lp_last_error.restype = C.c_char_p
-    for name in ("lp_renderer_forward", "lp_renderer_backward"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p]
-    for name in ("lp_splatter_forward", "lp_splatter_backward"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpSplatterArgs), C.c_void_p]
-    L.lp_splatter_normalize.restype = C.c_int
-    L.lp_splatter_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    L.lp_hash_randn.restype = C.c_int
-    L.lp_hash_randn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    L.lp_renderer_corner_rows.restype = C.c_int
-    L.lp_renderer_corner_rows.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p, C.c_void_p]
-    L.lp_renderer_backward_relu_dump.restype = C.c_int
-    L.lp_renderer_backward_relu_dump.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p, C.c_int64, C.c_void_p]
-    L.lp_renderer_relu_dump_words.restype = C.c_int
-    L.lp_renderer_relu_dump_words.argtypes = [C.POINTER(LpRendererArgs)]
-    L.lp_mlp_splatter_backward_relu_dump.restype = C.c_int
-    L.lp_mlp_splatter_backward_relu_dump.argtypes = [C.POINTER(LpSplatterArgs), C.c_void_p, C.c_int64, C.c_void_p]
-    L.lp_mlp_splatter_relu_dump_words.restype = C.c_int
-    L.lp_mlp_splatter_relu_dump_words.argtypes = [C.POINTER(LpSplatterArgs)]
-    L.lp_mlp_splatter_launch_shape.restype = C.c_int
-    L.lp_mlp_splatter_launch_shape.argtypes = [C.POINTER(LpSplatterArgs), C.c_void_p]
-    L.lp_build_info.restype = C.c_char_p
-    L.lp_renderer_kernel_family.restype = C.c_int
-    L.lp_renderer_kernel_family.argtypes = [C.POINTER(LpRendererArgs)]
-    L.lp_renderer_forward_family.restype = C.c_int
-    L.lp_renderer_forward_family.argtypes = [C.POINTER(LpRendererArgs)]
-    L.lp_renderer_forward_workspace_bytes.restype = C.c_int64
-    L.lp_renderer_forward_workspace_bytes.argtypes = [C.POINTER(LpRendererArgs)]
-    L.lp_renderer_forward_ws.restype = C.c_int
-    L.lp_renderer_forward_ws.argtypes = [C.POINTER(LpRendererArgs), C.c_void_p, C.c_int64, C.c_void_p]
-    L.lp_renderer_backward_segments.restype = C.c_int
-    L.lp_renderer_backward_segments.argtypes = [C.POINTER(LpRendererArgs)]
-    L.lp_splatter_kernel_family.restype = C.c_int
-    L.lp_splatter_kernel_family.argtypes = [C.POINTER(LpSplatterArgs)]
-    for name in ("lp_ray_embedding_forward", "lp_ray_embedding_backward"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpRayEmbedArgs), C.c_void_p]
-    # total-variation regulariser (grid-list, HOST weight array, count, p, ...)
-    _tv = [C.POINTER(LpGridList), C.c_void_p, C.c_int32, C.c_int32]
-    _tv_grad = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]  # grad_loss, scale, grad, grad_list (HOST array), n_grad_list
-    L.lp_grid_tv_workspace_bytes.restype = C.c_int64
-    L.lp_grid_tv_workspace_bytes.argtypes = [C.POINTER(LpGridList)]
-    L.lp_grid_tv_forward.restype = C.c_int
-    L.lp_grid_tv_forward.argtypes = _tv + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.lp_grid_tv_backward.restype = C.c_int
-    L.lp_grid_tv_backward.argtypes = _tv + _tv_grad + [C.c_int32, C.c_void_p]
-    L.lp_grid_tv_fused.restype = C.c_int
-    L.lp_grid_tv_fused.argtypes = _tv + [C.c_void_p, C.c_void_p, C.c_int64] + _tv_grad + [C.c_void_p]
-    # resampling of a grid-list: source list, destination list, align_corners, HOST coefficient array (or NULL), ...
-    L.lp_grid_resample_forward.restype = C.c_int
-    L.lp_grid_resample_forward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_void_p]
-    L.lp_grid_resample_backward.restype = C.c_int
-    L.lp_grid_resample_backward.argtypes = [C.POINTER(LpGridList), C.POINTER(LpGridList), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    # occupancy scaffold of a grid-list: args, result (, workspace, workspace bytes), stream
-    L.lp_scaffold_workspace_bytes.restype = C.c_int64
-    L.lp_scaffold_workspace_bytes.argtypes = [C.POINTER(LpScaffoldArgs)]
-    L.lp_scaffold_opacity.restype = C.c_int
-    L.lp_scaffold_opacity.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p]
-    L.lp_scaffold_build.restype = C.c_int
-    L.lp_scaffold_build.argtypes = [C.POINTER(LpScaffoldArgs), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    # the decoder at arbitrary points: args, stream
-    for name in ("lp_points_forward", "lp_points_backward"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpPointsArgs), C.c_void_p]
-    # rays clipped to the occupied span of a scaffold: args, near_out, far_out, hit_out, stream
-    L.lp_rays_clip.restype = C.c_int
-    L.lp_rays_clip.argtypes = [C.POINTER(LpRayClipArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    # gather / splat of a grid-list at arbitrary points: args, stream
-    for name in ("lp_point_gather", "lp_point_splat", "lp_point_normalize", "lp_point_grad_points"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpPointGridArgs), C.c_void_p]
-    # triangle mesh of a lattice's level set: args, workspace, workspace bytes, stream
-    L.lp_mesh_workspace_bytes.restype = C.c_int64
-    L.lp_mesh_workspace_bytes.argtypes = [C.POINTER(LpMeshArgs)]
-    for name in ("lp_mesh_count", "lp_mesh_emit"):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LpMeshArgs), C.c_void_p, C.c_int64, C.c_void_p]
-    # sample placement and compositing of the march (include/lightplane_hip_samples.h): args, stream
-    for name, st in zip(SAMPLES_EXPORTS, (LpRaySamplesArgs, LpRaySamplesArgs, LpCompositeArgs, LpCompositeArgs)):
-        fn = getattr(L, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(st), C.c_void_p]
-    L.lp_abi_sizeof.restype = C.c_int
-    L.lp_abi_sizeof.argtypes = [C.c_int]
+    for names, restype, argtypes in SIGNATURES:
+        for name in names:
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
                       (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
                       (14, LpPointGridArgs), (16, LpMeshArgs),  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
@@ -392,6 +355,33 @@ def check_tensors(device: torch.device, float32: dict, any_dtype: Optional[dict]
                 assert t.dtype == torch.float32, f"{name} has to be float32 (got {t.dtype})"
 
 
+def check_grids(tensors, name: str, extra_f32: Optional[dict] = None, any_dtype: Optional[dict] = None,
+                device: Optional[torch.device] = None) -> torch.device:
+    """The checks of a front-end that hands grid tensors to the library as they are: ``extra_f32`` and the grids (``name[i]``) fp32,
+    ``any_dtype`` of whatever type, all on ``device`` (default: the first grid's), the grids contiguous, and the device a GPU."""
+    dev = tensors[0].device if device is None else device
+    f32 = dict(extra_f32 or ())
+    f32.update({f"{name}[{i}]": g for i, g in enumerate(tensors)})
+    check_tensors(dev, f32, any_dtype)
+    for g in tensors:
+        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
+    current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    return dev
+
+
+def int32_index(t: torch.Tensor) -> torch.Tensor:
+    """A ``grid_idx`` tensor as the kernels read it: int32, contiguous, 16-byte aligned."""
+    return aligned(t.to(torch.int32).contiguous())
+
+
+def query(fn, *args, what: str) -> int:
+    """The count a ``*_workspace_bytes`` / ``*_dump_words`` style entry point answers; a negative answer is its error code."""
+    n = int(fn(*args))
+    if n < 0:
+        check(n, what)
+    return n
+
+
 def current_stream(device: torch.device) -> Optional[int]:
     if device.type != "cuda":
         raise LightplaneHipError(
@@ -424,7 +414,7 @@ def make_march(num_samples, num_samples_inf, mask_out_of_bounds_samples, contrac
     return m
 
 
-def make_grid_list(data, descs: Sequence[GridDesc], channels: int, n_rows: int) -> LpGridList:
+def make_grid_list(data, descs: Sequence, channels: int, n_rows: int) -> LpGridList:
     """``data``: the flat ``[rows, C]`` tensor (grids at their ``row_offset``), or a LIST of per-grid tensors (zero-copy
     grid-lists: every grid in its own allocation, addressed from row 0 of its own tensor), or ``None`` (shapes only)."""
     gl = LpGridList()
@@ -458,3 +448,27 @@ def make_mlp(dims: Sequence[int], offset: int) -> LpMlp:
         m.dims[i] = v
     m.offset = int(offset)
     return m
+
+
+def make_decoder(a, dims_t, dims_o, dims_c=None) -> None:
+    """``a.trunk``, ``a.opacity`` and (with ``dims_c``) ``a.color``: the decoder's MLPs, one after the other in the flat parameter vector."""
+    n_t = mlp_numel(dims_t)
+    a.trunk, a.opacity = make_mlp(dims_t, 0), make_mlp(dims_o, n_t)
+    if dims_c is not None:
+        a.color = make_mlp(dims_c, n_t + mlp_numel(dims_o))
+
+
+def route_grads(a, field: str, form, grads, needs, clear: bool = False) -> tuple:
+    """Hand the gradient buffers of a grid-list (``grads``: one per tensor of ``form``, or ``None`` -- the kernels scatter into every
+    grid of a list or into none, so the caller allocates all of them when any grid asks) to the argument block: a flat form's to
+    ``a.<field>``, a list's to ``a.<field>_list``.  Returns what autograd gets: the buffers somebody asked for.  ``clear``: ``a`` is a
+    used block, reset both fields."""
+    flat = grads is not None and not form.is_list
+    many = grads is not None and form.is_list
+    if flat or clear:
+        setattr(a, field, ptr(grads[0]) if flat else None)
+    if many or clear:
+        fill_ptr_list(getattr(a, field + "_list"), grads if many else None)
+    if grads is None:
+        return (None,) * len(needs)
+    return tuple(g if need else None for g, need in zip(grads, needs))

@@ -15,9 +15,11 @@ integers (``GridDesc``), never as a device tensor, so no device sync is needed.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, List, NamedTuple, Sequence, Tuple
 
 import torch
+
+from . import _lib  # (which imports nothing of this module: the one place that writes an LpGridList is its make_grid_list)
 
 
 def assert_shape(x: torch.Tensor, shape: Sequence[int]) -> None:
@@ -192,19 +194,79 @@ class GridDesc:
         )
 
 
+class GridForm(NamedTuple):
+    """How one grid-list argument reaches the C ABI: as one ``[B, D, H, W, C]`` tensor per grid that is never concatenated
+    (``is_list``), or as ONE flat ``[rows, channels]`` tensor with the grids at their ``row_offset``.  Shapes only -- the tensors
+    travel next to it -- so it is built once per call, kept on the autograd context and applied to any tensors of that form (the
+    grids, their gradients, a fresh result).
+
+    ``sampler=True`` holds the sizes to what the ray marchers sample (``make_grid_descs``): one batch size, voxel grids and planes.
+    ``sampler=False`` takes any positive extents (a line, a single cell) and differing batch sizes, 1 to ``LP_MAX_GRIDS`` grids: fine
+    for a regulariser, and the library checks the samplers' limits of the ops that have them."""
+
+    is_list: bool
+    descs: Tuple[GridDesc, ...]
+    channels: int
+    rows: int
+
+    @property
+    def n_tensors(self) -> int:
+        return len(self.descs) if self.is_list else 1
+
+    @classmethod
+    def of_sizes(cls, grid_sizes, *, sampler: bool, is_list: bool = False) -> "GridForm":
+        """The form of grids of these ``[B, D, H, W, C]`` sizes."""
+        sizes = sizes_to_list(grid_sizes)
+        if sampler:
+            assert len(sizes) > 0
+        else:
+            assert 0 < len(sizes) <= _lib.LP_MAX_GRIDS, f"a grid-list holds 1 to {_lib.LP_MAX_GRIDS} grids"
+        channels, batch = sizes[0][4], sizes[0][0]
+        descs, row = [], 0
+        for gs in sizes:
+            assert gs[4] == channels, "All grids should have the same feature dimensions."
+            if sampler:
+                assert gs[0] == batch, "All grids should have the same batch size."
+            else:
+                assert all(v >= 1 for v in gs), f"grid size {gs} has an empty dimension"
+            d = GridDesc(gs[0], gs[1], gs[2], gs[3], row)
+            if sampler:
+                d.kind  # validates
+            descs.append(d)
+            row += d.n_rows
+        return cls(is_list, tuple(descs), channels, row)
+
+    @classmethod
+    def of(cls, grid, grid_sizes=None, *, name: str = "grid", sampler: bool, sizes_name: str = "grid_sizes"):
+        """``(tensors, form)`` of a grid argument, accepted as ``lightplane_renderer`` accepts it: a *list* of ``[B, D, H, W, C]``
+        tensors, or a flat 2-D tensor with ``grid_sizes``; anything else is a ``NotImplementedError``."""
+        check_grid(grid, grid_sizes)
+        if isinstance(grid, list):
+            tensors = tuple(grid)
+            for g in tensors:
+                assert isinstance(g, torch.Tensor) and g.ndim == 5, (
+                    "every grid of a grid-list has to be [B, D, H, W, C]" if sampler
+                    else f"every entry of a {name} list has to be a [B, D, H, W, C] tensor")
+            return tensors, cls.of_sizes([g.shape for g in tensors], sampler=sampler, is_list=True)
+        form = cls.of_sizes(grid_sizes, sampler=sampler)
+        assert grid.ndim == 2 and tuple(grid.shape) == (form.rows, form.channels), f"flat {name} tensor does not match {sizes_name}"
+        return (grid,), form
+
+    def abi(self, tensors=None):
+        """The ``LpGridList`` of ``tensors`` in this form (``None``: shapes only)."""
+        data = None if tensors is None else list(tensors) if self.is_list else tensors[0]
+        return _lib.make_grid_list(data, self.descs, self.channels, self.rows)
+
+    def sizes(self) -> List[List[int]]:
+        """``[B, D, H, W, C]`` of every grid."""
+        return [[d.B, d.D, d.H, d.W, self.channels] for d in self.descs]
+
+    def out_shapes(self) -> List[Tuple[int, ...]]:
+        """Shape of every tensor of a fresh result or gradient in this form."""
+        return [tuple(s) for s in self.sizes()] if self.is_list else [(self.rows, self.channels)]
+
+
 def make_grid_descs(grid_sizes) -> Tuple[List[GridDesc], int, int]:
     """``(descs, n_channels, total_rows)`` for a list of ``[B, D, H, W, C]`` sizes."""
-    sizes = sizes_to_list(grid_sizes)
-    assert len(sizes) > 0
-    C = sizes[0][4]
-    B = sizes[0][0]
-    descs: List[GridDesc] = []
-    row = 0
-    for gs in sizes:
-        assert gs[4] == C, "All grids should have the same feature dimensions."
-        assert gs[0] == B, "All grids should have the same batch size."
-        d = GridDesc(gs[0], gs[1], gs[2], gs[3], row)
-        d.kind  # validates
-        descs.append(d)
-        row += d.n_rows
-    return descs, C, row
+    form = GridForm.of_sizes(grid_sizes, sampler=True)
+    return list(form.descs), form.channels, form.rows

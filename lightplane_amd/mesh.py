@@ -63,10 +63,7 @@ def mesh_workspace_bytes(volume_size) -> int:
     shapes only, no GPU): 4 bytes per lattice point, 16 bytes per 256 points and the small upper levels of the scan."""
     a = _lib.LpMeshArgs()
     a.shape = _lib.LpGrid(*_shape(volume_size), 0, None)
-    n = int(_lib.lib().lp_mesh_workspace_bytes(ctypes.byref(a)))
-    if n < 0:
-        _lib.check(n, "lp_mesh_workspace_bytes")
-    return n
+    return _lib.query(_lib.lib().lp_mesh_workspace_bytes, ctypes.byref(a), what="lp_mesh_workspace_bytes")
 
 
 @torch.no_grad()
@@ -106,9 +103,7 @@ def _marching_cubes(volume, level, with_normals, max_vertices, max_faces, worksp
     a.volume = volume.data_ptr()
     a.shape = _lib.LpGrid(*size, 0, None)
     a.level = float(level)
-    need = int(L.lp_mesh_workspace_bytes(ctypes.byref(a)))
-    if need < 0:
-        _lib.check(need, "lp_mesh_workspace_bytes")
+    need = _lib.query(L.lp_mesh_workspace_bytes, ctypes.byref(a), what="lp_mesh_workspace_bytes")
     with torch.cuda.device(dev):
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=dev)

@@ -24,16 +24,13 @@ from typing import List, NamedTuple, Union
 import torch
 
 from . import _lib
-from .regularizers import _grid_list, _normalize, _tv_descs
+from .grids import GridForm
 
 __all__ = ["sample_grid_at_points", "splat_points"]
 
 
 class _Cfg(NamedTuple):
-    is_list: bool
-    descs: tuple
-    channels: int
-    rows: int
+    grid: GridForm
     mask: bool
     contract: bool
     normalize: bool = False
@@ -42,13 +39,14 @@ class _Cfg(NamedTuple):
 def _args(cfg: _Cfg, tensors, points, grid_idx, row_weight=None) -> _lib.LpPointGridArgs:
     """``tensors``: the grid-list's tensors in the form ``cfg`` describes; ``row_weight``: ``None`` or their ``[rows]`` twins."""
     a = _lib.LpPointGridArgs()
-    a.grid = _grid_list(tensors, cfg.is_list, list(cfg.descs), cfg.channels, cfg.rows)
+    form = cfg.grid
+    a.grid = form.abi(tensors)
     if row_weight is not None:
-        for g in range(len(cfg.descs)):  # (the flat form has one buffer: row i of the flat tensor has weight i)
-            a.row_weight[g] = _lib.ptr(row_weight[g if cfg.is_list else 0])
+        for g in range(len(form.descs)):  # (the flat form has one buffer: row i of the flat tensor has weight i)
+            a.row_weight[g] = _lib.ptr(row_weight[g if form.is_list else 0])
     a.points, a.grid_idx = _lib.ptr(points), _lib.ptr(grid_idx)
     a.n_rays, a.n_pts = points.shape[0], points.shape[1]
-    a.channels = cfg.channels
+    a.channels = form.channels
     a.mask_out_of_bounds, a.contract_coords = int(cfg.mask), int(cfg.contract)
     return a
 
@@ -72,7 +70,7 @@ class _SampleAtPoints(torch.autograd.Function):
         points = _lib.aligned(points.contiguous())
         tensors = tuple(_lib.aligned(t, grid=True) for t in tensors)
         with torch.cuda.device(dev):
-            out = torch.empty(points.shape[0], points.shape[1], cfg.channels, device=dev, dtype=torch.float32)
+            out = torch.empty(points.shape[0], points.shape[1], cfg.grid.channels, device=dev, dtype=torch.float32)
             a = _args(cfg, tensors, points, grid_idx)
             a.out_features = _lib.ptr(out)
             _call("lp_point_gather", a, stream)
@@ -118,14 +116,9 @@ class _SplatPoints(torch.autograd.Function):
         dev = points.device
         stream = _lib.current_stream(dev)
         points, features = _lib.aligned(points.contiguous()), _lib.aligned(features.contiguous())
-        C = cfg.channels
         with torch.cuda.device(dev):
-            if cfg.is_list:
-                outs = [torch.zeros(d.B, d.D, d.H, d.W, C, device=dev, dtype=torch.float32) for d in cfg.descs]
-                weights = [torch.zeros(d.n_rows, device=dev, dtype=torch.float32) for d in cfg.descs] if cfg.normalize else None
-            else:
-                outs = [torch.zeros(cfg.rows, C, device=dev, dtype=torch.float32)]
-                weights = [torch.zeros(cfg.rows, device=dev, dtype=torch.float32)] if cfg.normalize else None
+            outs = [torch.zeros(s, device=dev, dtype=torch.float32) for s in cfg.grid.out_shapes()]
+            weights = [torch.zeros(o.numel() // o.shape[-1], device=dev, dtype=torch.float32) for o in outs] if cfg.normalize else None
             a = _args(cfg, outs, points, grid_idx, weights)
             a.vectors = _lib.ptr(features)
             _call("lp_point_splat", a, stream)
@@ -149,8 +142,7 @@ class _SplatPoints(torch.autograd.Function):
         d_points, d_features = None, None
         with torch.cuda.device(dev):
             # (a grid nobody differentiated has a zero upstream gradient: the kernels read every grid of the list)
-            shapes = [(d.B, d.D, d.H, d.W, cfg.channels) for d in cfg.descs] if cfg.is_list else [(cfg.rows, cfg.channels)]
-            ups = [torch.zeros(s, device=dev, dtype=torch.float32) if g is None else _dense(g) for g, s in zip(g_outs, shapes)]
+            ups = [torch.zeros(s, device=dev, dtype=torch.float32) if g is None else _dense(g) for g, s in zip(g_outs, cfg.grid.out_shapes())]
             if need[2]:
                 d_features = torch.empty_like(features)
                 a = _args(cfg, ups, points, grid_idx, weights if cfg.normalize else None)
@@ -182,16 +174,10 @@ def sample_grid_at_points(points, grid, ray_grid_idx, mask_out_of_bounds_samples
     ``lightplane_eval_mlp`` takes them; ``ray_grid_idx [n_rays]`` (any integer dtype): the batch element of each row's points.
     Differentiable with respect to every grid and to ``points``."""
     _check_points(points, ray_grid_idx)
-    tensors, is_list, descs, channels, rows = _normalize(grid, grid_sizes, name="grid")
-    dev = points.device
-    f32 = {"points": points}
-    f32.update({f"grid[{i}]": g for i, g in enumerate(tensors)})
-    _lib.check_tensors(dev, f32, {"ray_grid_idx": ray_grid_idx})
-    for g in tensors:
-        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
-    grid_idx = _lib.aligned(ray_grid_idx.to(torch.int32).contiguous())
-    cfg = _Cfg(is_list, tuple(descs), channels, rows, bool(mask_out_of_bounds_samples), bool(contract_coords))
+    tensors, form = GridForm.of(grid, grid_sizes, name="grid", sampler=False)
+    _lib.check_grids(tensors, "grid", {"points": points}, {"ray_grid_idx": ray_grid_idx}, device=points.device)
+    grid_idx = _lib.int32_index(ray_grid_idx)
+    cfg = _Cfg(form, bool(mask_out_of_bounds_samples), bool(contract_coords))
     return _SampleAtPoints.apply(cfg, points, grid_idx, *tensors)
 
 
@@ -207,16 +193,15 @@ def splat_points(points, features, output_grid_size, ray_grid_idx, mask_out_of_b
     and ``points``.  Returns the list of ``[B, D, H, W, C]`` tensors, or with ``return_list=False`` the flat ``[sum BDHW, C]`` tensor
     (splatted into directly).  A per-ray ``[n_rays, C]`` feature is not broadcast: use the Splatter, or ``expand(...).contiguous()``."""
     _check_points(points, ray_grid_idx)
-    descs, channels, rows = _tv_descs(output_grid_size)
+    form = GridForm.of_sizes(output_grid_size, sampler=False, is_list=bool(return_list))
+    channels = form.channels
     assert torch.is_tensor(features) and tuple(features.shape) == tuple(points.shape[:2]) + (channels,), (
         f"features has to be a [{points.shape[0]}, {points.shape[1]}, {channels}] tensor (one vector per point, the grids' channels)")
     if normalize and points.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError("splat_points(normalize=True) has no gradient with respect to points (the derivative through the "
                                   "division by the splatted weights is not provided): use normalize=False, or detach the points")
-    dev = points.device
-    _lib.check_tensors(dev, {"points": points, "features": features}, {"ray_grid_idx": ray_grid_idx})
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
-    grid_idx = _lib.aligned(ray_grid_idx.to(torch.int32).contiguous())
-    cfg = _Cfg(bool(return_list), tuple(descs), channels, rows, bool(mask_out_of_bounds_samples), bool(contract_coords), bool(normalize))
+    _lib.check_grids((), "grid", {"points": points, "features": features}, {"ray_grid_idx": ray_grid_idx}, device=points.device)
+    grid_idx = _lib.int32_index(ray_grid_idx)
+    cfg = _Cfg(form, bool(mask_out_of_bounds_samples), bool(contract_coords), bool(normalize))
     outs = _SplatPoints.apply(cfg, points, features, grid_idx)
     return list(outs) if return_list else outs[0]

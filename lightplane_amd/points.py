@@ -28,24 +28,15 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-from .grids import check_grid_and_color_grid
-from .params import DecoderParams, int_list_of, mlp_numel
-from .regularizers import _grid_list, _normalize
+from .grids import GridForm, check_grid_and_color_grid
+from .params import DecoderParams, int_list_of
 
 __all__ = ["lightplane_eval_mlp", "lightplane_eval_mlp_opacity_only"]
 
 
-class _GridForm(NamedTuple):
-    is_list: bool
-    descs: tuple
-    channels: int
-    rows: int
-    n_tensors: int
-
-
 class _Cfg(NamedTuple):
-    grid: _GridForm
-    color_grid: Optional[_GridForm]
+    grid: GridForm
+    color_grid: Optional[GridForm]
     dims_t: tuple
     dims_o: tuple
     dims_c: tuple
@@ -56,21 +47,13 @@ class _Cfg(NamedTuple):
     opacity_only: bool
 
 
-def _form(grid, sizes, name):
-    tensors, is_list, descs, channels, rows = _normalize(grid, sizes, name=name)
-    return tensors, _GridForm(is_list, tuple(descs), channels, rows, len(tensors))
-
-
 def _fill(cfg: _Cfg, points, mlp_params, encoding, grid_idx, scaffold, grids, color_grids, with_color: bool) -> _lib.LpPointsArgs:
     a = _lib.LpPointsArgs()
-    g = cfg.grid
-    a.grid = _grid_list(grids, g.is_list, list(g.descs), g.channels, g.rows)
+    a.grid = cfg.grid.abi(grids)
     if with_color and cfg.color_grid is not None:
-        c = cfg.color_grid
-        a.color_grid = _grid_list(color_grids, c.is_list, list(c.descs), c.channels, c.rows)
+        a.color_grid = cfg.color_grid.abi(color_grids)
     a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
-    n_t, n_o = mlp_numel(cfg.dims_t), mlp_numel(cfg.dims_o)
-    a.trunk, a.opacity, a.color = _lib.make_mlp(cfg.dims_t, 0), _lib.make_mlp(cfg.dims_o, n_t), _lib.make_mlp(cfg.dims_c, n_t + n_o)
+    _lib.make_decoder(a, cfg.dims_t, cfg.dims_o, cfg.dims_c)
     a.color_chn, a.gain = cfg.color_chn, cfg.gain
     a.mask_out_of_bounds, a.contract_coords = int(cfg.mask), int(cfg.contract)
     a.points, a.grid_idx = _lib.ptr(points), _lib.ptr(grid_idx)
@@ -135,22 +118,12 @@ class _EvalPoints(torch.autograd.Function):
             a.grad_opacity, a.grad_color = _lib.ptr(g_opacity), _lib.ptr(g_color)
             a.grad_points, a.grad_mlp_params = _lib.ptr(d_points), _lib.ptr(d_params)
             a.grad_encoding = _lib.ptr(d_enc) if with_color else None
-            for form, grads, flat, lst in ((cfg.grid, d_grids, "grad_grid", a.grad_grid_list),
-                                           (cfg.color_grid, d_cgrids, "grad_color_grid", a.grad_color_grid_list)):
-                if grads is None:
-                    continue
-                if form.is_list:
-                    _lib.fill_ptr_list(lst, grads)
-                else:
-                    setattr(a, flat, _lib.ptr(grads[0]))
+            g_grids = _lib.route_grads(a, "grad_grid", cfg.grid, d_grids, need[6:6 + n_g])
+            g_cgrids = _lib.route_grads(a, "grad_color_grid", cfg.color_grid, d_cgrids, need[6 + n_g:])
             _lib.check(_lib.lib().lp_points_backward(ctypes.byref(a), stream), "lp_points_backward")
-        out = [None, d_points, d_params, d_enc, None, None]
-        out += [g if n else None for g, n in zip(d_grids or [None] * n_g, need[6:6 + n_g])]
-        n_c = len(color_grids)
-        if d_cgrids is None and any(need[6 + n_g:]):  # (the colour grids took no part: their gradient is zero, not absent)
-            d_cgrids = [torch.zeros_like(t) for t in color_grids]
-        out += [g if n else None for g, n in zip(d_cgrids or [None] * n_c, need[6 + n_g:])]
-        return tuple(out)
+        if d_cgrids is None:  # (the colour grids took no part: their gradient is zero, not absent)
+            g_cgrids = tuple(torch.zeros_like(t) if n else None for t, n in zip(color_grids, need[6 + n_g:]))
+        return (None, d_points, d_params, d_enc, None, None) + g_grids + g_cgrids
 
 
 def _eval(points, grid, ray_grid_idx, decoder_params: DecoderParams, rays_encoding, gain, mask, noise, scaffold, color_grid, contract,
@@ -168,8 +141,8 @@ def _eval(points, grid, ray_grid_idx, decoder_params: DecoderParams, rays_encodi
         assert torch.is_tensor(rays_encoding) and tuple(rays_encoding.shape) == (n_rays, dims_c[0]), (
             f"rays_encoding has to be a [{n_rays}, {dims_c[0]}] tensor (the colour head's input width)")
     check_grid_and_color_grid(grid, color_grid, grid_sizes, color_grid_sizes)
-    grids, gform = _form(grid, grid_sizes, "grid")
-    cgrids, cform = ((), None) if color_grid is None else _form(color_grid, color_grid_sizes, "color_grid")
+    grids, gform = GridForm.of(grid, grid_sizes, name="grid", sampler=False)
+    cgrids, cform = ((), None) if color_grid is None else GridForm.of(color_grid, color_grid_sizes, name="color_grid", sampler=False)
     if cform is not None:
         assert len(dims_t) <= 1, "a decoder with a separate colour grid has no trunk layers"
     mlp_params = decoder_params.mlp_params
@@ -178,13 +151,10 @@ def _eval(points, grid, ray_grid_idx, decoder_params: DecoderParams, rays_encodi
         assert torch.is_tensor(scaffold) and scaffold.ndim == 4, "scaffold has to be a [B, D, H, W] tensor"
     dev = points.device
     f32 = {"points": points, "decoder_params.mlp_params": mlp_params, "rays_encoding": rays_encoding, "scaffold": scaffold}
-    f32.update({f"grid[{i}]": g for i, g in enumerate(grids)})
-    f32.update({f"color_grid[{i}]": g for i, g in enumerate(cgrids)})
-    _lib.check_tensors(dev, f32, {"ray_grid_idx": ray_grid_idx})
-    for g in grids + cgrids:
-        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
-    grid_idx = _lib.aligned(ray_grid_idx.to(torch.int32).contiguous())
+    _lib.check_grids(grids, "grid", f32, {"ray_grid_idx": ray_grid_idx}, device=dev)
+    if cgrids:
+        _lib.check_grids(cgrids, "color_grid", device=dev)
+    grid_idx = _lib.int32_index(ray_grid_idx)
     scaffold = None if scaffold is None else _lib.aligned(scaffold.detach().contiguous())
     cfg = _Cfg(gform, cform, dims_t, dims_o, dims_c, int(decoder_params.color_chn), float(gain), bool(mask), bool(contract), opacity_only)
     return _EvalPoints.apply(cfg, points, mlp_params, rays_encoding, grid_idx, scaffold, *grids, *cgrids)

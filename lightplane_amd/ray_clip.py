@@ -61,7 +61,7 @@ def clip_rays_to_scaffold(rays: Rays, scaffold: Optional[torch.Tensor] = None, *
                 assert t.is_contiguous() and tuple(t.shape) == (n,), f"out[{i}] has to be a contiguous [{n}] tensor"
         a = _lib.LpRayClipArgs()
         directions, origins = _lib.aligned(rays.directions), _lib.aligned(rays.origins)
-        grid_idx = _lib.aligned(rays.grid_idx.to(torch.int32))
+        grid_idx = _lib.int32_index(rays.grid_idx)
         near_in, far_in = rays.near, rays.far
         if near_in.data_ptr() % 16 and near_in is not near:
             near_in = _lib.aligned(near_in)

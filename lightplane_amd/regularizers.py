@@ -14,48 +14,14 @@ at 0 is 0, as ``torch.abs`` has it.  No atomics (bit-reproducible), no host sync
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import torch
 
 from . import _lib
-from .grids import GridDesc, check_grid, sizes_to_list
+from .grids import GridForm
 
 __all__ = ["grid_tv_loss", "add_grid_tv_grad_", "grid_tv_workspace_bytes"]
-
-
-def _tv_descs(grid_sizes) -> Tuple[List[GridDesc], int, int]:
-    """``(descs, channels, rows)``: like ``grids.make_grid_descs`` without the samplers' limits -- any positive extents (a line, a
-    single cell) and differing batch sizes are fine for a regulariser."""
-    sizes = sizes_to_list(grid_sizes)
-    assert 0 < len(sizes) <= _lib.LP_MAX_GRIDS, f"a grid-list holds 1 to {_lib.LP_MAX_GRIDS} grids"
-    channels = sizes[0][4]
-    descs, row = [], 0
-    for gs in sizes:
-        assert gs[4] == channels, "All grids should have the same feature dimensions."
-        assert all(v >= 1 for v in gs), f"grid size {gs} has an empty dimension"
-        descs.append(GridDesc(gs[0], gs[1], gs[2], gs[3], row))
-        row += descs[-1].n_rows
-    return descs, channels, row
-
-
-def _normalize(grid, grid_sizes, name="grid"):
-    """``(tensors, is_list, descs, channels, rows)`` of a grid argument, accepted exactly as ``lightplane_renderer`` accepts it: a
-    *list* of ``[B, D, H, W, C]`` tensors, or a flat 2-D tensor with ``grid_sizes``; anything else is a ``NotImplementedError``."""
-    check_grid(grid, grid_sizes)
-    if isinstance(grid, list):
-        tensors = tuple(grid)
-        for g in tensors:
-            assert torch.is_tensor(g) and g.ndim == 5, f"every entry of a {name} list has to be a [B, D, H, W, C] tensor"
-        descs, channels, rows = _tv_descs([list(g.shape) for g in tensors])
-        return tensors, True, descs, channels, rows
-    descs, channels, rows = _tv_descs(grid_sizes)
-    assert grid.ndim == 2 and tuple(grid.shape) == (rows, channels), f"flat {name} tensor does not match grid_sizes"
-    return (grid,), False, descs, channels, rows
-
-
-def _grid_list(tensors, is_list, descs, channels, rows) -> _lib.LpGridList:
-    return _lib.make_grid_list(list(tensors) if is_list else tensors[0], descs, channels, rows)
 
 
 def _weights(grid_weights, n: int):
@@ -69,29 +35,18 @@ def _weights(grid_weights, n: int):
     return (ctypes.c_float * n)(*w), n
 
 
-def _check(tensors, p: int) -> torch.device:
-    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
-    dev = tensors[0].device
-    _lib.check_tensors(dev, {f"grid[{i}]": g for i, g in enumerate(tensors)})
-    for g in tensors:
-        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
-    return dev
-
-
 def grid_tv_workspace_bytes(grid_sizes) -> int:
     """Bytes of device workspace one loss evaluation of grids of these ``[B, D, H, W, C]`` sizes takes (``lp_grid_tv_workspace_bytes``;
     shapes only, no GPU)."""
-    descs, channels, rows = _tv_descs(grid_sizes)
-    gl = _lib.make_grid_list(None, descs, channels, rows)
-    n = int(_lib.lib().lp_grid_tv_workspace_bytes(ctypes.byref(gl)))
-    if n < 0:
-        _lib.check(n, "lp_grid_tv_workspace_bytes")
-    return n
+    gl = GridForm.of_sizes(grid_sizes, sampler=False).abi()
+    return _lib.query(_lib.lib().lp_grid_tv_workspace_bytes, ctypes.byref(gl), what="lp_grid_tv_workspace_bytes")
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+def _grad_args(form: GridForm, grads):
+    """``(grad, grad_list, n_grad_list)`` of the C ABI for gradient tensors in ``form``."""
+    if form.is_list:
+        return None, (ctypes.c_void_p * len(grads))(*[t.data_ptr() for t in grads]), len(grads)
+    return grads[0].data_ptr(), None, 0
 
 
 class _GridTV(torch.autograd.Function):
@@ -100,10 +55,10 @@ class _GridTV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, *tensors):
-        is_list, descs, channels, rows, p, weights = cfg
+        form, p, weights = cfg
         dev = tensors[0].device
-        gl = _grid_list(tensors, is_list, descs, channels, rows)
-        w, nw = _weights(weights, len(descs))
+        gl = form.abi(tensors)
+        w, nw = _weights(weights, len(form.descs))
         L = _lib.lib()
         ws_bytes = int(L.lp_grid_tv_workspace_bytes(ctypes.byref(gl)))
         with torch.cuda.device(dev):
@@ -118,23 +73,20 @@ class _GridTV(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss):
-        is_list, descs, channels, rows, p, weights = ctx.cfg
+        form, p, weights = ctx.cfg
         tensors = ctx.saved_tensors
-        if not any(ctx.needs_input_grad[1:]):
+        needs = ctx.needs_input_grad[1:]
+        if not any(needs):
             return (None,) * (1 + len(tensors))
         dev = tensors[0].device
-        gl = _grid_list(tensors, is_list, descs, channels, rows)
-        w, nw = _weights(weights, len(descs))
+        gl = form.abi(tensors)
+        w, nw = _weights(weights, len(form.descs))
         g_loss = g_loss.to(device=dev, dtype=torch.float32).contiguous()
         with torch.cuda.device(dev):
             grads = [torch.empty_like(t) for t in tensors]
-            if is_list:
-                flat, lst, n = None, _ptr_array(grads), len(grads)
-            else:
-                flat, lst, n = grads[0].data_ptr(), None, 0
-            _lib.check(_lib.lib().lp_grid_tv_backward(ctypes.byref(gl), w, nw, p, g_loss.data_ptr(), 1.0, flat, lst, n, 0,
+            _lib.check(_lib.lib().lp_grid_tv_backward(ctypes.byref(gl), w, nw, p, g_loss.data_ptr(), 1.0, *_grad_args(form, grads), 0,
                                                       _lib.current_stream(dev)), "lp_grid_tv_backward")
-        return (None,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
+        return (None,) + tuple(g if need else None for g, need in zip(grads, needs))
 
 
 def grid_tv_loss(grid, grid_sizes=None, p: int = 1, grid_weights: Optional[Sequence[float]] = None) -> torch.Tensor:
@@ -144,11 +96,13 @@ def grid_tv_loss(grid, grid_sizes=None, p: int = 1, grid_weights: Optional[Seque
     takes them (anything else: ``NotImplementedError``).  ``p``: 1 or 2.  ``grid_weights``: one float per grid (default 1).
     The backward returns one gradient per list tensor.  Memory beyond the result: ``grid_tv_workspace_bytes`` in the forward, the
     gradient buffers in the backward."""
-    tensors, is_list, descs, channels, rows = _normalize(grid, grid_sizes)
+    tensors, form = GridForm.of(grid, grid_sizes, sampler=False)
+    n = len(form.descs)
     weights = None if grid_weights is None else tuple(float(v) for v in (grid_weights.tolist() if torch.is_tensor(grid_weights) else grid_weights))
-    assert weights is None or len(weights) == len(descs), f"grid_weights has {len(weights)} entries for {len(descs)} grids"
-    _check(tensors, p)
-    return _GridTV.apply((is_list, descs, channels, rows, int(p), weights), *tensors)
+    assert weights is None or len(weights) == n, f"grid_weights has {len(weights)} entries for {n} grids"
+    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
+    _lib.check_grids(tensors, "grid")
+    return _GridTV.apply((form, int(p), weights), *tensors)
 
 
 def add_grid_tv_grad_(grid, grad, weight: float = 1.0, p: int = 1, grid_sizes=None,
@@ -162,8 +116,8 @@ def add_grid_tv_grad_(grid, grad, weight: float = 1.0, p: int = 1, grid_sizes=No
         tv = add_grid_tv_grad_(list(grids), [g.grad for g in grids], weight=1e-3)
 
     Allocates nothing but the workspace (``grid_tv_workspace_bytes``) and the returned 0-dim tensor."""
-    tensors, is_list, descs, channels, rows = _normalize(grid, grid_sizes)
-    if is_list:
+    tensors, form = GridForm.of(grid, grid_sizes, sampler=False)
+    if form.is_list:
         assert isinstance(grad, list) and len(grad) == len(tensors), "grad has to be a list with one tensor per grid"
         grads = tuple(grad)
     else:
@@ -173,19 +127,16 @@ def add_grid_tv_grad_(grid, grad, weight: float = 1.0, p: int = 1, grid_sizes=No
         assert torch.is_tensor(g) and g.shape == t.shape and g.is_contiguous(), (
             "every gradient buffer has to be contiguous and shaped like its grid")
         assert g.data_ptr() != t.data_ptr(), "grad must not alias grid"
-    w, nw = _weights(grid_weights, len(descs))
+    w, nw = _weights(grid_weights, len(form.descs))
     _lib.check_tensors(tensors[0].device, {f"grad[{i}]": g for i, g in enumerate(grads)})
-    dev = _check(tensors, p)
-    gl = _grid_list(tensors, is_list, descs, channels, rows)
+    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
+    dev = _lib.check_grids(tensors, "grid")
+    gl = form.abi(tensors)
     L = _lib.lib()
     ws_bytes = int(L.lp_grid_tv_workspace_bytes(ctypes.byref(gl)))
     with torch.no_grad(), torch.cuda.device(dev):
         workspace = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        if is_list:
-            flat, lst, n = None, _ptr_array(grads), len(grads)
-        else:
-            flat, lst, n = grads[0].data_ptr(), None, 0
         _lib.check(L.lp_grid_tv_fused(ctypes.byref(gl), w, nw, int(p), loss.data_ptr(), workspace.data_ptr(), ws_bytes, None,
-                                      float(weight), flat, lst, n, _lib.current_stream(dev)), "lp_grid_tv_fused")
+                                      float(weight), *_grad_args(form, grads), _lib.current_stream(dev)), "lp_grid_tv_fused")
     return loss

@@ -24,28 +24,20 @@ import math
 import random
 import warnings
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
 from . import _lib, config
-from .grids import (
-    GridDesc,
-    check_grid_and_color_grid,
-    make_grid_descs,
-    process_and_flatten_grid,
-)
+from .grids import GridForm, check_grid_and_color_grid
 from .params import DecoderParams, int_list_of, mlp_numel
 from .rays import Rays
 
 
 @dataclass
 class _RendererCfg:
-    descs: List[GridDesc]
-    channels: int
-    n_rows: int
-    color_descs: Optional[List[GridDesc]]
-    color_n_rows: int
+    grid: GridForm
+    color_grid: Optional[GridForm]
     dims_trunk: List[int]
     dims_opacity: List[int]
     dims_color: List[int]
@@ -61,9 +53,6 @@ class _RendererCfg:
     scaffold_shape: Optional[Tuple[int, int, int, int]]
     kernel: int
     stop_neg_log_t: float = 0.0
-    n_grid_tensors: int = 1        # tensors the grid-list arrives in: 1 flat tensor, or one per grid (zero-copy list)
-    n_color_tensors: int = 0
-    grid_is_list: bool = False
     alpha_mode: int = 0            # fused module epilogue: 0 none, 1 alpha = 1 - T, 2 log T
     arithmetic: int = 0            # LP_ARITH_* of the backward (include/lightplane_hip.h)
     march_order: int = 0           # LP_MARCH_* of the backward
@@ -76,12 +65,9 @@ def _fill_args(cfg: _RendererCfg, grids, color_grids, mlp_params, directions, or
     per grid (zero-copy grid-list: per-grid base pointers in the ABI)."""
     a = _lib.LpRendererArgs()
     a.rays = _lib.make_rays(directions, origins, grid_idx, near, far, encoding, cfg.row_length)
-    a.grid = _lib.make_grid_list(list(grids) if cfg.grid_is_list else grids[0], cfg.descs, cfg.channels, cfg.n_rows)
-    if cfg.color_descs is not None:
-        a.color_grid = _lib.make_grid_list(list(color_grids) if cfg.grid_is_list else color_grids[0], cfg.color_descs,
-                                           cfg.channels, cfg.color_n_rows)
-    else:
-        a.color_grid = _lib.make_grid_list(None, [], 0, 0)
+    a.grid = cfg.grid.abi(grids)
+    if cfg.color_grid is not None:
+        a.color_grid = cfg.color_grid.abi(color_grids)
     if scaffold is not None:
         a.scaffold = _lib.ptr(scaffold)
         B, D, H, W = cfg.scaffold_shape
@@ -90,10 +76,7 @@ def _fill_args(cfg: _RendererCfg, grids, color_grids, mlp_params, directions, or
                               cfg.contract_coords, cfg.disparity_at_inf)
     a.mlp_params = _lib.ptr(mlp_params)
     a.n_mlp_params = mlp_params.numel()
-    n_t, n_o = mlp_numel(cfg.dims_trunk), mlp_numel(cfg.dims_opacity)
-    a.trunk = _lib.make_mlp(cfg.dims_trunk, 0)
-    a.opacity = _lib.make_mlp(cfg.dims_opacity, n_t)
-    a.color = _lib.make_mlp(cfg.dims_color, n_t + n_o)
+    _lib.make_decoder(a, cfg.dims_trunk, cfg.dims_opacity, cfg.dims_color)
     a.color_chn = cfg.color_chn
     a.gain = float(cfg.gain)
     a.noise_sigma = float(cfg.noise_sigma)
@@ -112,8 +95,8 @@ _warned_shapes = set()
 def _warn_if_generic(a, cfg: _RendererCfg) -> None:
     if not config.warn_generic_kernel or cfg.kernel != _lib.LP_KERNEL_AUTO or cfg.arithmetic != _lib.LP_ARITH_DEFAULT:
         return  # (LP_ARITH_FP32 outside the tuned family asks for the generic fp32 kernels by definition)
-    key = (cfg.channels, tuple(cfg.dims_trunk), tuple(cfg.dims_opacity), tuple(cfg.dims_color), cfg.color_chn,
-           cfg.color_descs is not None)
+    key = (cfg.grid.channels, tuple(cfg.dims_trunk), tuple(cfg.dims_opacity), tuple(cfg.dims_color), cfg.color_chn,
+           cfg.color_grid is not None)
     if key in _warned_shapes:
         return
     if _lib.lib().lp_renderer_kernel_family(ctypes.byref(a)) == 0:
@@ -124,8 +107,8 @@ def _warn_if_generic(a, cfg: _RendererCfg) -> None:
                 "lightplane_amd: the BACKWARD of this decoder shape runs on the shape-generic Renderer kernels (10-100x slower); its "
                 f"forward runs kernel family {fwd} (layer-looped MFMA forward, "
                 f"{'streamed' if fwd == 4 else 'resident'} weight images). "
-                f"Got channels={cfg.channels}, trunk={cfg.dims_trunk}, opacity={cfg.dims_opacity}, "
-                f"color={cfg.dims_color}, color_chn={cfg.color_chn}, separate colour grid={cfg.color_descs is not None}.")
+                f"Got channels={cfg.grid.channels}, trunk={cfg.dims_trunk}, opacity={cfg.dims_opacity}, "
+                f"color={cfg.dims_color}, color_chn={cfg.color_chn}, separate colour grid={cfg.color_grid is not None}.")
             return
         warnings.warn(
             "lightplane_amd: this decoder shape runs on the shape-generic Renderer kernels (10-100x slower), forward (kernel family 0) "
@@ -135,26 +118,20 @@ def _warn_if_generic(a, cfg: _RendererCfg) -> None:
             "layers with hidden width 64 and / or 64 grid channels and <= 4 colour channels (a separate colour grid only with 16 / 32 "
             "grid channels); at most 256 "
             "beyond-far samples. "
-            f"Got channels={cfg.channels}, trunk={cfg.dims_trunk}, opacity={cfg.dims_opacity}, "
-            f"color={cfg.dims_color}, color_chn={cfg.color_chn}, separate colour grid={cfg.color_descs is not None}.")
+            f"Got channels={cfg.grid.channels}, trunk={cfg.dims_trunk}, opacity={cfg.dims_opacity}, "
+            f"color={cfg.dims_color}, color_chn={cfg.color_chn}, separate colour grid={cfg.color_grid is not None}.")
 
 
 def _shape_args(grid, decoder_params: DecoderParams, grid_sizes=None, color_grid=None, color_grid_sizes=None):
     """``LpRendererArgs`` carrying shapes only (no pointers) -- what the library's selection queries look at."""
-    if isinstance(grid, (list, tuple)):
-        grid_sizes = [list(g.shape) for g in grid]
-    descs, channels, n_rows = make_grid_descs(grid_sizes)
-    color_descs, color_n_rows = None, 0
-    if color_grid is not None:
-        if isinstance(color_grid, (list, tuple)):
-            color_grid_sizes = [list(g.shape) for g in color_grid]
-        color_descs, _, color_n_rows = make_grid_descs(color_grid_sizes)
-    dims_t, dims_o, dims_c = _decoder_dims(decoder_params)
+    def form(g, sizes):
+        return GridForm.of_sizes([t.shape for t in g] if isinstance(g, (list, tuple)) else sizes, sampler=True)
     a = _lib.LpRendererArgs()
-    a.grid = _lib.make_grid_list(None, descs, channels, n_rows)
-    a.color_grid = _lib.make_grid_list(None, color_descs or [], channels if color_descs else 0, color_n_rows)
-    n_t, n_o = mlp_numel(dims_t), mlp_numel(dims_o)
-    a.trunk, a.opacity, a.color = _lib.make_mlp(dims_t, 0), _lib.make_mlp(dims_o, n_t), _lib.make_mlp(dims_c, n_t + n_o)
+    a.grid = form(grid, grid_sizes).abi()
+    if color_grid is not None:
+        # (the colour grid-list has the grid's channels, whatever its sizes say)
+        a.color_grid = form(color_grid, color_grid_sizes)._replace(channels=a.grid.channels).abi()
+    _lib.make_decoder(a, *_decoder_dims(decoder_params))
     a.color_chn = int(decoder_params.color_chn)
     return a
 
@@ -230,7 +207,6 @@ def backward_segments(rays: Rays, grid, decoder_params: DecoderParams, num_sampl
     """Number of ray segments the backward of this call is split into (``lp_renderer_backward_segments``; needs no
     GPU): 1 = one sweep per ray, > 1 = small batch, the number of state records per ray (one per LP_SEG_LEN = 8 samples; a workgroup sweeps one or two such blocks).  ``march_order``
     "samples" (the transposed march, where it applies) never segments: it deals a small batch over the chip by rays per wave."""
-    _unused.pop("march_order", None)
     _check_render_kwargs("backward_segments", _unused)
     a = _shape_args(grid, decoder_params, grid_sizes, color_grid, color_grid_sizes)
     a.rays.n_rays = int(rays.directions.shape[0])
@@ -275,7 +251,7 @@ class relu_dump_recorder:
 class LightplaneFunction(torch.autograd.Function):
     """Autograd boundary of the Renderer (name kept from the reference, :296).
 
-    The grid-list arrives as ``cfg.n_grid_tensors`` tensors (+ ``cfg.n_color_tensors`` for the colour grid-list): ONE
+    The grid-list arrives as ``cfg.grid.n_tensors`` tensors (+ ``cfg.color_grid.n_tensors`` for the colour grid-list): ONE
     flat ``[rows, C]`` tensor, or one tensor PER GRID -- a list input is never concatenated (the reference's
     ``flatten_grid``, misc_utils.py:42-45, copies the whole list every call and splits its gradient every backward):
     the kernels take per-grid base pointers and write per-grid gradient buffers."""
@@ -285,8 +261,9 @@ class LightplaneFunction(torch.autograd.Function):
                 bg_color, *grid_tensors):
         # (_lib.aligned: a dense view at an element offset into a larger buffer is copied to a 16-byte aligned base -- here, so that
         # autograd routes the gradient through the caller's view)
-        grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[: cfg.n_grid_tensors])
-        color_grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[cfg.n_grid_tensors:])
+        n_g = cfg.grid.n_tensors
+        grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[:n_g])
+        color_grids = tuple(_lib.aligned(g.contiguous(), grid=True) for g in grid_tensors[n_g:])
         dev = grids[0].device
         stream = _lib.current_stream(dev)
         mlp_params, encoding = _lib.aligned(mlp_params.contiguous()), _lib.aligned(encoding.contiguous())
@@ -346,13 +323,14 @@ class LightplaneFunction(torch.autograd.Function):
         (nlt, ckpt, seg, mlp_params, encoding, directions, origins, grid_idx, near, far, scaffold,
          bg_color) = ctx.saved_tensors[:12]
         cfg: _RendererCfg = ctx.cfg
-        grids = ctx.saved_tensors[12: 12 + cfg.n_grid_tensors]
-        color_grids = ctx.saved_tensors[12 + cfg.n_grid_tensors:]
+        n_g = cfg.grid.n_tensors
+        grids = ctx.saved_tensors[12: 12 + n_g]
+        color_grids = ctx.saved_tensors[12 + n_g:]
         dev = grids[0].device
         stream = _lib.current_stream(dev)
         need_params, need_enc = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        need_g = ctx.needs_input_grad[10: 10 + cfg.n_grid_tensors]
-        need_c = ctx.needs_input_grad[10 + cfg.n_grid_tensors:]
+        need_g = ctx.needs_input_grad[10: 10 + n_g]
+        need_c = ctx.needs_input_grad[10 + n_g:]
         # The forward's argument block is re-used: shapes, decoder layout and march are already in it.  Only the pointers
         # are taken again from the saved tensors (they are the forward's tensors unless a saved-tensor hook -- CPU
         # offloading, checkpointing -- unpacked them into new storage).
@@ -364,7 +342,7 @@ class LightplaneFunction(torch.autograd.Function):
         r.near_t, r.far_t, r.encoding = _lib.ptr(near), _lib.ptr(far), _lib.ptr(encoding)
         a.mlp_params, a.scaffold, a.bg_color = _lib.ptr(mlp_params), _lib.ptr(scaffold), _lib.ptr(bg_color)
         a.neg_log_t, a.neg_log_t_ckpt, a.seg_prefix = _lib.ptr(nlt), _lib.ptr(ckpt), _lib.ptr(seg)
-        if cfg.grid_is_list:
+        if cfg.grid.is_list:
             for i, g in enumerate(grids):
                 a.grid.grids[i].data = _lib.ptr(g)
             for i, g in enumerate(color_grids):
@@ -381,28 +359,16 @@ class LightplaneFunction(torch.autograd.Function):
         a.grad_alpha = _lib.ptr(g_alpha)
         # the kernels scatter into every grid of a list or into none: allocate all buffers if any grid needs one
         grad_grids = [torch.zeros_like(g) for g in grids] if any(need_g) else None
-        grad_cgrids = [torch.zeros_like(g) for g in color_grids] if (color_grids and any(need_c)) else None
+        grad_cgrids = [torch.zeros_like(g) for g in color_grids] if any(need_c) else None
         grad_params = torch.zeros_like(mlp_params) if need_params else None
         grad_enc = torch.zeros_like(encoding) if need_enc else None
-        a.grad_grid = a.grad_color_grid = None
-        for i in range(_lib.LP_MAX_GRIDS):
-            a.grad_grid_list[i] = a.grad_color_grid_list[i] = None
-        if grad_grids is not None:
-            if cfg.grid_is_list:
-                _lib.fill_ptr_list(a.grad_grid_list, grad_grids)
-            else:
-                a.grad_grid = _lib.ptr(grad_grids[0])
-        if grad_cgrids is not None:
-            if cfg.grid_is_list:
-                _lib.fill_ptr_list(a.grad_color_grid_list, grad_cgrids)
-            else:
-                a.grad_color_grid = _lib.ptr(grad_cgrids[0])
+        # (the block is the forward's, used by every backward through it: both fields of either grid-list are set anew)
+        gg = _lib.route_grads(a, "grad_grid", cfg.grid, grad_grids, need_g, clear=True)
+        gc = _lib.route_grads(a, "grad_color_grid", cfg.color_grid, grad_cgrids, need_c, clear=True)
         a.grad_mlp_params, a.grad_encoding = _lib.ptr(grad_params), _lib.ptr(grad_enc)
         with torch.cuda.device(dev):
             if _RELU_DUMP is not None:  # test hook (relu_dump_recorder): the DUMP twin of the same kernel
-                words = _lib.lib().lp_renderer_relu_dump_words(ctypes.byref(a))
-                if words < 0:
-                    _lib.check(words, "lp_renderer_relu_dump_words")
+                words = _lib.query(_lib.lib().lp_renderer_relu_dump_words, ctypes.byref(a), what="lp_renderer_relu_dump_words")
                 d = _RELU_DUMP.reset(directions.shape[0], cfg.num_samples + cfg.num_samples_inf, words, dev)
                 # ReLU sites in the reference's evaluation order (include/lightplane_hip.h): every kernel family writes the same number
                 # of words for each of them, then the flag word
@@ -417,9 +383,7 @@ class LightplaneFunction(torch.autograd.Function):
             for name, g in [("mlp_params", grad_params), ("encoding", grad_enc)] + \
                     [("grid", g) for g in (grad_grids or [])] + [("color_grid", g) for g in (grad_cgrids or [])]:
                 assert g is None or torch.isfinite(g).all(), f"non-finite gradient w.r.t. {name}"
-        gg = [None] * cfg.n_grid_tensors if grad_grids is None else [g if nd else None for g, nd in zip(grad_grids, need_g)]
-        gc = [None] * cfg.n_color_tensors if grad_cgrids is None else [g if nd else None for g, nd in zip(grad_cgrids, need_c)]
-        return (None, grad_params, grad_enc) + (None,) * 7 + tuple(gg) + tuple(gc)
+        return (None, grad_params, grad_enc) + (None,) * 7 + gg + gc
 
 
 def _neighbours(a, b, da, db):
@@ -566,33 +530,15 @@ def _render(rays: Rays, grid, decoder_params: DecoderParams, num_samples, gain, 
     stop_transmittance = float(stop_transmittance or 0.0)
     assert 0.0 <= stop_transmittance < 1.0, "stop_transmittance has to be in [0, 1)"
     stop_neg_log_t = -math.log(stop_transmittance) if stop_transmittance > 0.0 else 0.0
-    grid, color_grid, grid_sizes, color_grid_sizes = check_grid_and_color_grid(
-        grid, color_grid, grid_sizes, color_grid_sizes)
-    grid_is_list = isinstance(grid, (list, tuple))
-    if grid_is_list:
-        # zero-copy grid-list: the tensors go to the kernels as they are (per-grid base pointers); the reference
-        # (and round 1) concatenated the list into one flat tensor on every call (misc_utils.py:42-45)
-        grid_tensors = tuple(grid)
-        grid_sizes = [list(g.shape) for g in grid_tensors]
-        color_tensors = tuple(color_grid) if color_grid is not None else ()
-        color_grid_sizes = [list(g.shape) for g in color_tensors] if color_grid is not None else None
-        for g in grid_tensors + color_tensors:
-            assert g.ndim == 5, "every grid of a grid-list has to be [B, D, H, W, C]"
-    else:
-        grid, color_grid, grid_sizes, color_grid_sizes = process_and_flatten_grid(
-            grid, color_grid, grid_sizes, color_grid_sizes)
-        grid_tensors = (grid,)
-        color_tensors = (color_grid,) if color_grid is not None else ()
-    descs, channels, n_rows = make_grid_descs(grid_sizes)
-    if not grid_is_list:
-        assert grid.ndim == 2 and grid.shape[1] == channels and grid.shape[0] == n_rows, (
-            "flat grid tensor does not match grid_sizes")
-    color_descs, color_n_rows = None, 0
+    if color_grid is not None:  # (GridForm.of checks a grid on its own)
+        check_grid_and_color_grid(grid, color_grid, grid_sizes, color_grid_sizes)
+    # (a list is zero-copy: the tensors go to the kernels as they are (per-grid base pointers); the reference (and round 1)
+    # concatenated the list into one flat tensor on every call, misc_utils.py:42-45)
+    grid_tensors, gform = GridForm.of(grid, grid_sizes, sampler=True)
+    color_tensors, cform = (), None
     if color_grid is not None:
-        color_descs, c_channels, color_n_rows = make_grid_descs(color_grid_sizes)
-        assert c_channels == channels and color_descs[0].B == descs[0].B
-        if not grid_is_list:
-            assert color_grid.ndim == 2 and color_grid.shape == (color_n_rows, channels)
+        color_tensors, cform = GridForm.of(color_grid, color_grid_sizes, name="color_grid", sampler=True, sizes_name="color_grid_sizes")
+        assert cform.channels == gform.channels and cform.descs[0].B == gform.descs[0].B
 
     if mask_out_of_bounds_samples and contract_coords:
         warnings.warn(
@@ -624,8 +570,8 @@ def _render(rays: Rays, grid, decoder_params: DecoderParams, num_samples, gain, 
     else:
         inject_noise_seed = 0
 
-    B = descs[0].B
-    grid_idx = _lib.aligned(rays.grid_idx.to(torch.int32).contiguous())
+    B = gform.descs[0].B
+    grid_idx = _lib.int32_index(rays.grid_idx)
     march, row_length = check_inputs_and_plan(rays, grid_idx, B, march_order, rays_per_row)
 
     scaffold_shape = None
@@ -638,14 +584,13 @@ def _render(rays: Rays, grid, decoder_params: DecoderParams, num_samples, gain, 
         bg_color = _lib.aligned(bg_color.contiguous())
 
     cfg = _RendererCfg(
-        descs=descs, channels=channels, n_rows=n_rows, color_descs=color_descs, color_n_rows=color_n_rows,
+        grid=gform, color_grid=cform,
         dims_trunk=dims_t, dims_opacity=dims_o, dims_color=dims_c, color_chn=int(decoder_params.color_chn),
         num_samples=int(num_samples), num_samples_inf=int(num_samples_inf), gain=float(gain),
         mask_out_of_bounds_samples=bool(mask_out_of_bounds_samples), contract_coords=bool(contract_coords),
         disparity_at_inf=float(disparity_at_inf), noise_sigma=float(inject_noise_sigma),
         noise_seed=int(inject_noise_seed), scaffold_shape=scaffold_shape, kernel=int(kernel),
-        stop_neg_log_t=stop_neg_log_t, n_grid_tensors=len(grid_tensors), n_color_tensors=len(color_tensors),
-        grid_is_list=grid_is_list, alpha_mode=int(alpha_mode),
+        stop_neg_log_t=stop_neg_log_t, alpha_mode=int(alpha_mode),
         arithmetic=int(config.arithmetic if arithmetic is None else arithmetic), march_order=int(march), row_length=int(row_length),
     )
     return LightplaneFunction.apply(
@@ -657,17 +602,17 @@ def renderer_corner_rows(rays: Rays, grid_sizes, num_samples: int, num_samples_i
                          contract_coords: bool = False, disparity_at_inf: float = 1e-5) -> torch.Tensor:
     """Integer corner rows of the march ``[N, S_tot, K_tot]`` (int64, -1 = out of range), rows
     relative to each grid's start.  Parity hook for the bit-exact index tests."""
-    descs, channels, n_rows = make_grid_descs(grid_sizes)
+    form = GridForm.of_sizes(grid_sizes, sampler=True)
     dev = rays.device
     stream = _lib.current_stream(dev)
-    k_tot = sum(8 if d.kind == "voxel" else 4 for d in descs)
+    k_tot = sum(8 if d.kind == "voxel" else 4 for d in form.descs)
     s_tot = num_samples + num_samples_inf
     out = torch.empty(rays.n_rays, s_tot, k_tot, dtype=torch.int64, device=dev)
     a = _lib.LpRendererArgs()
     a.rays = _lib.make_rays(_lib.aligned(rays.directions.contiguous()), _lib.aligned(rays.origins.contiguous()),
-                            _lib.aligned(rays.grid_idx.to(torch.int32).contiguous()), _lib.aligned(rays.near.contiguous()),
+                            _lib.int32_index(rays.grid_idx), _lib.aligned(rays.near.contiguous()),
                             _lib.aligned(rays.far.contiguous()), None)
-    a.grid = _lib.make_grid_list(None, descs, channels, n_rows)
+    a.grid = form.abi()
     a.march = _lib.make_march(num_samples, num_samples_inf, False, contract_coords, disparity_at_inf)
     keep = (a, out)  # noqa: F841  (keep tensors alive across the async launch)
     with torch.cuda.device(dev):

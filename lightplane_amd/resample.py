@@ -21,7 +21,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .regularizers import _grid_list, _normalize, _tv_descs
+from .grids import GridForm
 
 __all__ = ["grid_resample", "grid_up_sample", "resampled_sizes"]
 
@@ -69,13 +69,6 @@ def _coeffs(n_grids: int, scale_factor, align_corners: bool):
     return (ctypes.c_float * (3 * n_grids))(*([a] * (3 * n_grids)))
 
 
-def _check(tensors, name="grid") -> torch.device:
-    dev = tensors[0].device
-    _lib.check_tensors(dev, {f"{name}[{i}]": g for i, g in enumerate(tensors)})
-    for g in tensors:
-        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
-    return dev
 
 
 class _GridResample(torch.autograd.Function):
@@ -84,36 +77,31 @@ class _GridResample(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, *tensors):
-        is_list, descs, out_descs, channels, rows, out_rows, align, scale = cfg
+        form, out_form, align, scale = cfg
         dev = tensors[0].device
-        src = _grid_list(tensors, is_list, descs, channels, rows)
+        src = form.abi(tensors)
         with torch.cuda.device(dev):
-            if is_list:
-                outs = tuple(torch.empty((d.B, d.D, d.H, d.W, channels), dtype=torch.float32, device=dev) for d in out_descs)
-            else:
-                outs = (torch.empty((out_rows, channels), dtype=torch.float32, device=dev),)
-            dst = _grid_list(outs, is_list, out_descs, channels, out_rows)
+            outs = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in out_form.out_shapes())
+            dst = out_form.abi(outs)
             _lib.check(_lib.lib().lp_grid_resample_forward(ctypes.byref(src), ctypes.byref(dst), int(align),
-                                                           _coeffs(len(descs), scale, align), _lib.current_stream(dev)),
+                                                           _coeffs(len(form.descs), scale, align), _lib.current_stream(dev)),
                        "lp_grid_resample_forward")
         ctx.cfg = cfg
-        ctx.in_shapes = tuple(t.shape for t in tensors)
         return outs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *g_outs):
-        is_list, descs, out_descs, channels, rows, out_rows, align, scale = ctx.cfg
+        form, out_form, align, scale = ctx.cfg
         if not any(ctx.needs_input_grad[1:]):
-            return (None,) * (1 + len(ctx.in_shapes))
+            return (None,) * (1 + form.n_tensors)
         dev = g_outs[0].device
         g_outs = tuple(g.to(dtype=torch.float32).contiguous() for g in g_outs)
         with torch.cuda.device(dev):
-            grads = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.in_shapes)
-            g_src = _grid_list(grads, is_list, descs, channels, rows)
-            g_dst = _grid_list(g_outs, is_list, out_descs, channels, out_rows)
+            grads = tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in form.out_shapes())
+            g_src, g_dst = form.abi(grads), out_form.abi(g_outs)
             _lib.check(_lib.lib().lp_grid_resample_backward(ctypes.byref(g_src), ctypes.byref(g_dst), int(align),
-                                                            _coeffs(len(descs), scale, align), 0, _lib.current_stream(dev)),
+                                                            _coeffs(len(form.descs), scale, align), 0, _lib.current_stream(dev)),
                        "lp_grid_resample_backward")
         return (None,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
 
@@ -126,14 +114,13 @@ def grid_resample(grid, grid_sizes=None, *, sizes=None, scale_factor: Optional[f
     and ``scale_factor`` (outputs ``floor(n * factor)``, singular axes stay singular: ``resampled_sizes``).
     Returns the same container kind: a list of tensors, or ``(flat, new_grid_sizes)`` with the sizes as a list of ``[B, D', H', W', C]``.
     The backward returns one gradient per input tensor."""
-    tensors, is_list, descs, channels, rows = _normalize(grid, grid_sizes)
-    in_sizes = [[d.B, d.D, d.H, d.W, channels] for d in descs]
-    out_sizes = _target_sizes(in_sizes, sizes, scale_factor)
-    out_descs, _, out_rows = _tv_descs(out_sizes)
-    _check(tensors)
-    cfg = (is_list, descs, out_descs, channels, rows, out_rows, bool(align_corners), None if scale_factor is None else float(scale_factor))
+    tensors, form = GridForm.of(grid, grid_sizes, sampler=False)
+    out_sizes = _target_sizes(form.sizes(), sizes, scale_factor)
+    out_form = GridForm.of_sizes(out_sizes, sampler=False, is_list=form.is_list)
+    _lib.check_grids(tensors, "grid")
+    cfg = (form, out_form, bool(align_corners), None if scale_factor is None else float(scale_factor))
     outs = _GridResample.apply(cfg, *tensors)
-    if is_list:
+    if form.is_list:
         return list(outs)
     return outs[0], out_sizes
 

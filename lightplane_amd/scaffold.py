@@ -21,8 +21,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .params import DecoderParams, int_list_of, mlp_numel
-from .regularizers import _grid_list, _normalize
+from .grids import GridForm
+from .params import DecoderParams, int_list_of
 
 __all__ = ["calculate_scaffold", "scaffold_opacity", "scaffold_workspace_bytes"]
 
@@ -41,32 +41,24 @@ def scaffold_workspace_bytes(scaffold_size, dilate_scaffold: int) -> int:
     a = _lib.LpScaffoldArgs()
     a.shape = _lib.LpGrid(*_shape(scaffold_size), 0, None)
     a.dilate = int(dilate_scaffold)
-    n = int(_lib.lib().lp_scaffold_workspace_bytes(ctypes.byref(a)))
-    if n < 0:
-        _lib.check(n, "lp_scaffold_workspace_bytes")
-    return n
+    return _lib.query(_lib.lib().lp_scaffold_workspace_bytes, ctypes.byref(a), what="lp_scaffold_workspace_bytes")
 
 
 def _args(feature_grid, decoder_params: DecoderParams, scaffold_size, gain, threshold, dilate, mask, grid_sizes):
     """``(args, device, keep-alive tensors)``: the argument block of one call.  The grid tensors go in as they are (contiguous, on one
     GPU, fp32 -- checked, never copied); the library refuses a base that is not 16-byte aligned."""
-    tensors, is_list, descs, channels, rows = _normalize(feature_grid, grid_sizes, name="feature_grid")
+    tensors, form = GridForm.of(feature_grid, grid_sizes, name="feature_grid", sampler=False)
     size = _shape(scaffold_size)
     dims_t, dims_o = int_list_of(decoder_params.n_hidden_trunk), int_list_of(decoder_params.n_hidden_opacity)
     mlp_params = decoder_params.mlp_params
-    dev = tensors[0].device
-    f32 = {f"feature_grid[{i}]": g for i, g in enumerate(tensors)}
-    f32["decoder_params.mlp_params"] = mlp_params
-    _lib.check_tensors(dev, f32)
-    for g in tensors:
-        assert g.is_contiguous(), "grids handed to the HIP library must be contiguous"
+    assert torch.is_tensor(mlp_params), "decoder_params.mlp_params has to be a tensor"
     assert mlp_params.ndim == 1, "decoder_params.mlp_params has to be the flat parameter vector"
-    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    dev = _lib.check_grids(tensors, "feature_grid", {"decoder_params.mlp_params": mlp_params})
     mlp_params = _lib.aligned(mlp_params.detach().contiguous())
     a = _lib.LpScaffoldArgs()
-    a.grid = _grid_list(tensors, is_list, descs, channels, rows)
+    a.grid = form.abi(tensors)
     a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
-    a.trunk, a.opacity = _lib.make_mlp(dims_t, 0), _lib.make_mlp(dims_o, mlp_numel(dims_t))
+    _lib.make_decoder(a, dims_t, dims_o)
     a.gain, a.mask_out_of_bounds = float(gain), int(bool(mask))
     a.shape = _lib.LpGrid(*size, 0, None)
     a.threshold, a.dilate = float(threshold), int(dilate)
@@ -100,9 +92,7 @@ def calculate_scaffold(feature_grid, decoder_params: DecoderParams, scaffold_siz
     a, dev, size, keep = _args(feature_grid, decoder_params, scaffold_size, gain, threshold, dilate_scaffold,
                                mask_out_of_bounds_samples, grid_sizes)
     L = _lib.lib()
-    need = int(L.lp_scaffold_workspace_bytes(ctypes.byref(a)))
-    if need < 0:
-        _lib.check(need, "lp_scaffold_workspace_bytes")
+    need = _lib.query(L.lp_scaffold_workspace_bytes, ctypes.byref(a), what="lp_scaffold_workspace_bytes")
     with torch.cuda.device(dev):
         out = _result(out, size, dev)
         if need > 0:

@@ -21,19 +21,21 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Optional, Sequence
 
 import torch
 
 from . import _lib, config
-from .grids import GridDesc, check_grid, make_grid_descs, process_and_flatten_grid, sizes_to_list, unflatten_grid
-from .params import SplatterParams, int_list_of
+from .grids import GridDesc, GridForm, unflatten_grid
+from .params import SplatterParams, int_list_of, mlp_numel
 from .rays import Rays
 
 
 @dataclass
 class _SplatterCfg:
-    descs: List[GridDesc]
+    # the output grid-list (always one flat tensor): the three values of a GridForm, spelled out because
+    # tests/test_gpu_walk_transitions.py builds this block positionally
+    descs: Sequence[GridDesc]
     channels: int
     n_rows: int
     num_samples: int
@@ -43,13 +45,9 @@ class _SplatterCfg:
     disparity_at_inf: float
     process_group: object = None
     # MLP-Splatter only
-    in_descs: Optional[List[GridDesc]] = None
-    in_channels: int = 0
-    in_n_rows: int = 0
-    mlp_dims: Optional[List[int]] = None
+    input_grid: Optional[GridForm] = None
+    mlp_dims: Optional[list] = None
     kernel: int = 0
-    in_is_list: bool = False   # the input grid-list arrives as one tensor per grid (zero-copy) instead of a flat tensor
-    n_in_tensors: int = 1
     march_order: int = 0       # LP_MARCH_* of the plain Splatter's forward walk
     row_length: int = 0        # LpRays.row_length: rays per image row (0 = unknown)
 
@@ -60,10 +58,9 @@ def _fill_args(cfg: _SplatterCfg, directions, origins, grid_idx, near, far, feat
     a.rays = _lib.make_rays(directions, origins, grid_idx, near, far, feature, cfg.row_length)
     a.march = _lib.make_march(cfg.num_samples, cfg.num_samples_inf, cfg.mask_out_of_bounds_samples,
                               cfg.contract_coords, cfg.disparity_at_inf)
-    a.out = _lib.make_grid_list(None, cfg.descs, cfg.channels, cfg.n_rows)
+    a.out = GridForm(False, tuple(cfg.descs), cfg.channels, cfg.n_rows).abi()
     if cfg.mlp_dims is not None:
-        a.input_grid = _lib.make_grid_list(list(input_grid) if cfg.in_is_list else input_grid[0], cfg.in_descs,
-                                           cfg.in_channels, cfg.in_n_rows)
+        a.input_grid = cfg.input_grid.abi(input_grid)
         a.mlp_params = _lib.ptr(mlp_params)
         a.n_mlp_params = mlp_params.numel()
         a.mlp = _lib.make_mlp(cfg.mlp_dims, 0)
@@ -162,17 +159,11 @@ class LightplaneMLPSplatterFunction(torch.autograd.Function):
         a = _fill_args(cfg, directions, origins, grid_idx, near, far, feature, mlp_params, input_grids)
         a.grad_out, a.weight = _lib.ptr(grad_out), _lib.ptr(weight)
         a.grad_encoding, a.grad_mlp_params = _lib.ptr(grad_feature), _lib.ptr(grad_params)
-        if grad_in is not None:
-            if cfg.in_is_list:
-                _lib.fill_ptr_list(a.grad_input_grid_list, grad_in)
-            else:
-                a.grad_input_grid = _lib.ptr(grad_in[0])
+        gi = _lib.route_grads(a, "grad_input_grid", cfg.input_grid, grad_in, need_grids)
         with torch.cuda.device(dev):
             if _RELU_DUMP is not None:  # test hook (mlp_splatter_relu_dump_recorder): the DUMP twin of the same kernel
                 L = _lib.lib()
-                words = L.lp_mlp_splatter_relu_dump_words(ctypes.byref(a))
-                if words < 0:
-                    _lib.check(words, "lp_mlp_splatter_relu_dump_words")
+                words = _lib.query(L.lp_mlp_splatter_relu_dump_words, ctypes.byref(a), what="lp_mlp_splatter_relu_dump_words")
                 d = _RELU_DUMP.reset(directions.shape[0], cfg.num_samples + cfg.num_samples_inf, words, dev)
                 _lib.check(L.lp_mlp_splatter_backward_relu_dump(ctypes.byref(a), d.data_ptr(), d.numel(), stream),
                            "lp_mlp_splatter_backward_relu_dump")
@@ -186,8 +177,7 @@ class LightplaneMLPSplatterFunction(torch.autograd.Function):
         if config.check_finite_grads:
             for g in [grad_feature, grad_params] + (grad_in or []):
                 assert g is None or torch.isfinite(g).all()
-        gi = [None] * len(input_grids) if grad_in is None else [g if nd else None for g, nd in zip(grad_in, need_grids)]
-        return (grad_feature, grad_params) + (None,) * 6 + tuple(gi)
+        return (grad_feature, grad_params) + (None,) * 6 + gi
 
 
 def _prep_rays(rays: Rays, B: int, march_order: Optional[str] = "rays", rays_per_row: Optional[int] = 0):
@@ -199,7 +189,7 @@ def _prep_rays(rays: Rays, B: int, march_order: Optional[str] = "rays", rays_per
         {"rays.directions": rays.directions, "rays.origins": rays.origins, "rays.near": rays.near,
          "rays.far": rays.far, "rays.encoding": rays.encoding},
         {"rays.grid_idx": rays.grid_idx})
-    grid_idx = _lib.aligned(rays.grid_idx.to(torch.int32).contiguous())
+    grid_idx = _lib.int32_index(rays.grid_idx)
     march = check_inputs_and_plan(rays, grid_idx, B, march_order, rays_per_row)
     return march, (_lib.aligned(rays.directions.contiguous()), _lib.aligned(rays.origins.contiguous()), grid_idx,
                    _lib.aligned(rays.near.contiguous()), _lib.aligned(rays.far.contiguous()))
@@ -236,44 +226,35 @@ def lightplane_splatter(
     ``rays_per_row``: rays per image row of a scanline-ordered batch (detected with the input check unless given; a hint for the
     backward walk, which then gathers for 2 x 4 pixel patches per wavefront; see ``lightplane_renderer``).
     """
-    sizes = sizes_to_list(output_grid_size)
-    descs, channels, n_rows = make_grid_descs(sizes)
+    form = GridForm.of_sizes(output_grid_size, sampler=True)
     assert rays.encoding is not None, "rays.encoding (the splatted feature) is required"
-    assert rays.encoding.shape[1] == channels, (
-        f"splatting feature width {rays.encoding.shape[1]} != output grid channels {channels}")
+    assert rays.encoding.shape[1] == form.channels, (
+        f"splatting feature width {rays.encoding.shape[1]} != output grid channels {form.channels}")
     assert rays.encoding.dtype == torch.float32
-    cfg = _SplatterCfg(descs, channels, n_rows, int(num_samples), int(num_samples_inf),
+    cfg = _SplatterCfg(form.descs, form.channels, form.rows, int(num_samples), int(num_samples_inf),
                        bool(mask_out_of_bounds_samples), bool(contract_coords), float(disparity_at_inf),
                        process_group)
-    (cfg.march_order, cfg.row_length), ray_tensors = _prep_rays(rays, descs[0].B, march_order, rays_per_row)
+    (cfg.march_order, cfg.row_length), ray_tensors = _prep_rays(rays, form.descs[0].B, march_order, rays_per_row)
     out = LightplaneSplatterFunction.apply(rays.encoding, cfg, *ray_tensors)
     if return_list:
-        return list(unflatten_grid(out, sizes))
+        return list(unflatten_grid(out, form.sizes()))
     return out
 
 
 def mlp_splatter_kernel_family(output_grid_size, mlp_params: SplatterParams, input_grid_sizes, num_samples_inf: int = 0) -> int:
     """Kernel family that runs an MLP-Splatter of these shapes: 3 = layer-looped MFMA family (2-4 layers, widths 16 / 32 / 64),
     0 = shape-generic kernels (``lp_splatter_kernel_family``: shapes only, needs no GPU)."""
-    descs, channels, n_rows = make_grid_descs(sizes_to_list(output_grid_size))
-    in_descs, in_channels, in_n_rows = make_grid_descs(sizes_to_list(input_grid_sizes))
-    a = _lib.LpSplatterArgs()
-    a.march = _lib.make_march(1, int(num_samples_inf), False, False, 1e-5)
-    a.out = _lib.make_grid_list(None, descs, channels, n_rows)
-    a.input_grid = _lib.make_grid_list(None, in_descs, in_channels, in_n_rows)
-    a.mlp = _lib.make_mlp(int_list_of(mlp_params.n_hidden), 0)
+    a = _mlp_shape_args(output_grid_size, mlp_params, input_grid_sizes, num_samples_inf=num_samples_inf)
     return int(_lib.lib().lp_splatter_kernel_family(ctypes.byref(a)))
 
 
 def _mlp_shape_args(output_grid_size, mlp_params: SplatterParams, input_grid_sizes, n_rays: int = 0, num_samples: int = 1,
                     num_samples_inf: int = 0, kernel: int = _lib.LP_KERNEL_AUTO) -> _lib.LpSplatterArgs:
-    descs, channels, n_rows = make_grid_descs(sizes_to_list(output_grid_size))
-    in_descs, in_channels, in_n_rows = make_grid_descs(sizes_to_list(input_grid_sizes))
     a = _lib.LpSplatterArgs()
     a.rays.n_rays = int(n_rays)
     a.march = _lib.make_march(int(num_samples), int(num_samples_inf), False, False, 1e-5)
-    a.out = _lib.make_grid_list(None, descs, channels, n_rows)
-    a.input_grid = _lib.make_grid_list(None, in_descs, in_channels, in_n_rows)
+    a.out = GridForm.of_sizes(output_grid_size, sampler=True).abi()
+    a.input_grid = GridForm.of_sizes(input_grid_sizes, sampler=True).abi()
     a.mlp = _lib.make_mlp(int_list_of(mlp_params.n_hidden), 0)
     a.kernel = int(kernel)
     return a
@@ -284,10 +265,7 @@ def mlp_splatter_relu_dump_words(output_grid_size, mlp_params: SplatterParams, i
     """Words per (ray, sample) of the MLP-Splatter's ReLU dump for these shapes (``lp_mlp_splatter_relu_dump_words``; test hook, needs
     no GPU): ceil(width / 32) per hidden layer + the flag word."""
     a = _mlp_shape_args(output_grid_size, mlp_params, input_grid_sizes, num_samples_inf=num_samples_inf, kernel=kernel)
-    w = int(_lib.lib().lp_mlp_splatter_relu_dump_words(ctypes.byref(a)))
-    if w < 0:
-        _lib.check(w, "lp_mlp_splatter_relu_dump_words")
-    return w
+    return _lib.query(_lib.lib().lp_mlp_splatter_relu_dump_words, ctypes.byref(a), what="lp_mlp_splatter_relu_dump_words")
 
 
 def mlp_splatter_launch_shape(n_rays: int, output_grid_size, mlp_params: SplatterParams, input_grid_sizes, num_samples: int,
@@ -357,44 +335,32 @@ def lightplane_mlp_splatter(
     ``lightplane_mlp_splatter`` (lightplane/lightplane_splatter.py:167-338).  Gradients flow to
     ``rays.encoding``, ``mlp_params.mlp_params`` and ``input_grid``.
     """
-    sizes = sizes_to_list(output_grid_size)
-    descs, channels, n_rows = make_grid_descs(sizes)
+    form = GridForm.of_sizes(output_grid_size, sampler=True)
     assert mlp_params is not None and len(mlp_params.n_hidden) > 1, (
         "mlp depth has to be bigger than 1 when using input_grid")
     assert input_grid is not None, "input_grid cannot be None when mlp_params is not None"
-    check_grid(input_grid, input_grid_sizes)
-    in_is_list = isinstance(input_grid, (list, tuple))
-    if in_is_list:  # zero-copy: one tensor per grid goes to the kernels as it is
-        in_tensors = tuple(input_grid)
-        input_grid_sizes = [list(g.shape) for g in in_tensors]
-    else:
-        input_grid, _, input_grid_sizes, _ = process_and_flatten_grid(input_grid, None, input_grid_sizes, None)
-        in_tensors = (input_grid,)
-    in_descs, in_channels, in_n_rows = make_grid_descs(input_grid_sizes)
-    if not in_is_list:
-        assert input_grid.ndim == 2 and input_grid.shape == (in_n_rows, in_channels), (
-            "flat input grid tensor does not match input_grid_sizes")
+    # (a list is zero-copy: one tensor per grid goes to the kernels as it is)
+    in_tensors, in_form = GridForm.of(input_grid, input_grid_sizes, name="input grid", sampler=True, sizes_name="input_grid_sizes")
     dims = int_list_of(mlp_params.n_hidden)
     assert rays.encoding is not None, "rays.encoding is required"
     assert rays.encoding.dtype == torch.float32
-    assert dims[0] == in_channels == rays.encoding.shape[1], (
-        f"MLP input width {dims[0]} must equal the input grid channels {in_channels} and the ray encoding "
+    assert dims[0] == in_form.channels == rays.encoding.shape[1], (
+        f"MLP input width {dims[0]} must equal the input grid channels {in_form.channels} and the ray encoding "
         f"width {rays.encoding.shape[1]}")
-    assert dims[-1] == channels, f"MLP output width {dims[-1]} != output grid channels {channels}"
-    assert in_descs[0].B == descs[0].B, "input and output grid-lists must share the batch size"
+    assert dims[-1] == form.channels, f"MLP output width {dims[-1]} != output grid channels {form.channels}"
+    assert in_form.descs[0].B == form.descs[0].B, "input and output grid-lists must share the batch size"
     flat_params = mlp_params.mlp_params
     assert flat_params.ndim == 1 and flat_params.dtype == torch.float32
-    from .params import mlp_numel
     assert flat_params.numel() == mlp_numel(dims), (
         f"The number of elements in mlp param should be {mlp_numel(dims)}. Got {flat_params.numel()} instead.")
     f32 = {"mlp_params.mlp_params": flat_params}
     f32.update({f"input_grid[{i}]": g for i, g in enumerate(in_tensors)})
     _lib.check_tensors(rays.encoding.device, f32)
-    cfg = _SplatterCfg(descs, channels, n_rows, int(num_samples), int(num_samples_inf),
+    cfg = _SplatterCfg(form.descs, form.channels, form.rows, int(num_samples), int(num_samples_inf),
                        bool(mask_out_of_bounds_samples), bool(contract_coords), float(disparity_at_inf),
-                       process_group, in_descs, in_channels, in_n_rows, dims, int(kernel), in_is_list, len(in_tensors))
-    out = LightplaneMLPSplatterFunction.apply(rays.encoding, flat_params, cfg, *_prep_rays(rays, descs[0].B)[1],
+                       process_group, in_form, dims, int(kernel))
+    out = LightplaneMLPSplatterFunction.apply(rays.encoding, flat_params, cfg, *_prep_rays(rays, form.descs[0].B)[1],
                                               *in_tensors)
     if return_list:
-        return list(unflatten_grid(out, sizes))
+        return list(unflatten_grid(out, form.sizes()))
     return out
