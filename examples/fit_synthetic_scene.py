@@ -10,6 +10,7 @@ GPU boxes have no datasets.
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
                                             [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0] [--modular]
+                                            [--importance N]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -44,6 +45,11 @@ point decoder for the vertex colours seen along ``-z`` -- and the file is an ASC
 the samples, ``renderer.eval_decoder_at_points`` (``lp.lightplane_eval_mlp``) decodes them and ``lp.composite_samples`` integrates
 them -- the same fit, with the per-sample tensors in the caller's hands (the JSON line gains ``modular``).  The held-out evaluation
 stays on the fused Renderer, so the PSNR also says that the two paths agree.  Without the flag the run is untouched.
+
+``--importance N`` (with ``--modular``) makes that march NeRF's coarse -> fine pass: the march above runs under ``no_grad`` and only for
+its compositing weights (``composite_samples(..., return_weights=True)``), ``renderer.importance_samples`` draws ``N`` more samples per
+ray from them (stratified, jittered with ``torch.rand``) and merges them into the coarse ones, and the fine pass over the
+``num_samples + N`` samples is the one that is fitted (the JSON line gains ``importance``).  0 leaves the run as it is without it.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -103,9 +109,17 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None,
     return -10.0 * math.log10(mse)
 
 
-def render_modular(renderer, rays, grids, scaffold=None):
-    """``(alpha, rgb)`` of ``renderer(rays, grids)`` through ray_samples -> the decoder at points -> composite_samples (background 0)"""
+def render_modular(renderer, rays, grids, scaffold=None, importance=0):
+    """``(alpha, rgb)`` of ``renderer(rays, grids)`` through ray_samples -> the decoder at points -> composite_samples (background 0);
+    ``importance`` > 0: that march only for its weights, and the result from the samples ``importance_samples`` makes of them"""
     samples = renderer.ray_samples(rays)
+    if importance > 0:
+        with torch.no_grad():
+            opacity, _ = renderer.eval_decoder_at_points(samples.points, rays.grid_idx, None, grids, scaffold=scaffold,
+                                                         directions=rays.directions)
+            weights = lp.composite_samples(opacity, None, samples.depths, samples.deltas, return_weights=True)[3]
+            jitter = torch.rand(weights.shape[0], importance, device=weights.device)
+        samples = renderer.importance_samples(rays, samples, weights, importance, jitter=jitter)
     opacity, color = renderer.eval_decoder_at_points(samples.points, rays.grid_idx, None, grids, scaffold=scaffold,
                                                      directions=rays.directions)
     _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
@@ -114,7 +128,7 @@ def render_modular(renderer, rays, grids, scaffold=None):
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
         upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False,
-        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None, modular=False):
+        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None, modular=False, importance=0):
     """``on_fitted(renderer, grids)``: called after the last step, before the exports, with the fitted module and its planes"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
@@ -156,7 +170,7 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         if modular:
-            alpha, rgb = render_modular(renderer, rays, list(grids), scaffold)
+            alpha, rgb = render_modular(renderer, rays, list(grids), scaffold, importance)
         else:
             _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
@@ -173,6 +187,8 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
            "steps": steps, "rays_per_step": n_rays, "stop_transmittance": stop_transmittance}
     if modular:
         out.update(modular=True)
+    if importance > 0:
+        out.update(importance=importance)
     if upsample_steps:
         out.update(upsample_steps=upsample_steps, start_res=start_res, psnr_at_upsample_db=psnr_at_upsample,
                    grid_shapes=[list(g.shape) for g in grids])
@@ -253,11 +269,14 @@ def main(argv=None):
     ap.add_argument("--res", type=int, default=64, help="resolution of the planes")
     ap.add_argument("--modular", action="store_true",
                     help="render the training batches through ray_samples -> eval_decoder_at_points -> composite_samples")
+    ap.add_argument("--importance", type=int, default=0,
+                    help="with --modular: new samples per ray drawn from the weights of a coarse pass (importance_samples); 0 = none")
     a = ap.parse_args(argv)
+    assert a.importance == 0 or a.modular, "--importance resamples the modular march: pass --modular as well"
     out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
               upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
               scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays,
-              export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level, modular=a.modular)
+              export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level, modular=a.modular, importance=a.importance)
     print(json.dumps(out))
     return out
 

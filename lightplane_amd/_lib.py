@@ -163,6 +163,15 @@ class LpCompositeArgs(C.Structure):  # include/lightplane_hip_samples.h
     ]
 
 
+class LpImportanceArgs(C.Structure):  # include/lightplane_hip_importance.h
+    _fields_ = [
+        ("origins", C.c_void_p), ("directions", C.c_void_p), ("depths", C.c_void_p), ("weights", C.c_void_p), ("jitter", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("n_importance", C.c_int32), ("include_coarse", C.c_int32), ("pad", C.c_float),
+        ("out_points", C.c_void_p), ("out_depths", C.c_void_p), ("out_deltas", C.c_void_p),
+        ("grad_points", C.c_void_p), ("grad_origins", C.c_void_p), ("grad_directions", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -186,6 +195,11 @@ EXPORTS = (
 
 #: every symbol include/lightplane_hip_samples.h declares (a header and a table of their own: the ones above stay as they are)
 SAMPLES_EXPORTS = ("lp_ray_samples_forward", "lp_ray_samples_backward", "lp_composite_forward", "lp_composite_backward")
+
+#: every symbol include/lightplane_hip_importance.h declares (again a header and a table of their own)
+IMPORTANCE_EXPORTS = ("lp_importance_samples_forward", "lp_importance_samples_backward")
+#: the most coarse samples and the most new samples per ray (LP_IMPORTANCE_MAX of that header: a ray's working set stays in LDS)
+LP_IMPORTANCE_MAX = 2048
 
 
 def _signatures():
@@ -233,6 +247,8 @@ def _signatures():
         # sample placement and compositing of the march (include/lightplane_hip_samples.h): args, stream
         (SAMPLES_EXPORTS[:2], C.c_int, (P(LpRaySamplesArgs), vp)),
         (SAMPLES_EXPORTS[2:], C.c_int, (P(LpCompositeArgs), vp)),
+        # importance resampling of a ray's samples (include/lightplane_hip_importance.h): args, stream
+        (IMPORTANCE_EXPORTS, C.c_int, (P(LpImportanceArgs), vp)),
     )
 
 
@@ -262,7 +278,8 @@ def lib() -> C.CDLL:
     for which, st in ((0, LpGrid), (1, LpGridList), (2, LpRays), (3, LpMarch), (4, LpMlp), (5, LpRendererArgs), (6, LpSplatterArgs),
                       (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
                       (14, LpPointGridArgs), (16, LpMeshArgs),  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
-                      (18, LpRaySamplesArgs), (20, LpCompositeArgs)):  # (nor 17, 19 and 21: lightplane_hip_samples.h)
+                      (18, LpRaySamplesArgs), (20, LpCompositeArgs),  # (nor 17, 19 and 21: lightplane_hip_samples.h)
+                      (22, LpImportanceArgs)):  # (nor 23: lightplane_hip_importance.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -734,6 +734,40 @@ static int check_composite(const LpCompositeArgs* args, bool backward) {
   return LP_OK;
 }
 
+// everything lp_importance_samples_forward / _backward check.  Messages begin with the field.
+static int check_importance(const LpImportanceArgs* args, bool backward) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  LP_ALIGNED(*args, origins);
+  LP_ALIGNED(*args, directions);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, jitter);
+  LP_ALIGNED(*args, out_points);
+  LP_ALIGNED(*args, out_depths);
+  LP_ALIGNED(*args, out_deltas);
+  LP_ALIGNED(*args, grad_points);
+  LP_ALIGNED(*args, grad_origins);
+  LP_ALIGNED(*args, grad_directions);
+  if (args->n_samples < 2) return set_error(LP_EINVAL, "n_samples %d < 2", args->n_samples);
+  if (args->n_importance < 1) return set_error(LP_EINVAL, "n_importance %d < 1", args->n_importance);
+  if (!std::isfinite(args->pad) || !(args->pad > 0.0f)) return set_error(LP_EINVAL, "pad %g has to be finite and > 0", (double)args->pad);
+  if (args->n_samples > LP_IMPORTANCE_MAX) return set_error(LP_EUNSUPPORTED, "n_samples %d > %d", args->n_samples, LP_IMPORTANCE_MAX);
+  if (args->n_importance > LP_IMPORTANCE_MAX)
+    return set_error(LP_EUNSUPPORTED, "n_importance %d > %d", args->n_importance, LP_IMPORTANCE_MAX);
+  // (the bound holds whatever include_coarse says: one rule for the forward and the backward of either layout)
+  if ((rc = check_point_batch(nullptr, args->n_rays, (int64_t)args->n_samples + args->n_importance, true))) return rc;
+  if (args->n_rays == 0) return LP_OK;
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"origins", args->origins, !backward},       {"directions", args->directions, true},
+      {"depths", args->depths, !backward},         {"weights", args->weights, !backward},
+      {"out_points", args->out_points, !backward}, {"out_depths", args->out_depths, true},
+      {"out_deltas", args->out_deltas, !backward}, {"grad_points", args->grad_points, backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -785,6 +819,7 @@ int lp_abi_sizeof(int which) {
     case 16: return (int)sizeof(LpMeshArgs);  // (and 15)
     case 18: return (int)sizeof(LpRaySamplesArgs);  // (and 17; this one and the next: lightplane_hip_samples.h)
     case 20: return (int)sizeof(LpCompositeArgs);  // (and 19)
+    case 22: return (int)sizeof(LpImportanceArgs);  // (and 21: lightplane_hip_importance.h)
     default: return -1;
   }
 }
@@ -1184,6 +1219,18 @@ int lp_composite_backward(const LpCompositeArgs* args, void* stream) {
   const int rc = check_composite(args, true);
   if (rc || args->n_rays == 0) return rc;
   return composite_launch(*args, true, (hipStream_t)stream);
+}
+
+int lp_importance_samples_forward(const LpImportanceArgs* args, void* stream) {
+  const int rc = check_importance(args, false);
+  if (rc || args->n_rays == 0) return rc;
+  return importance_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {
+  const int rc = check_importance(args, true);
+  if (rc || args->n_rays == 0) return rc;
+  return importance_launch(*args, true, (hipStream_t)stream);
 }
 
 int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream) {

@@ -9,6 +9,7 @@
 // per lane, one sample per step.
 #include "lp_device.h"
 #include "lp_host.h"
+#include "lp_wave.h"
 
 namespace lp {
 
@@ -38,30 +39,6 @@ LP_DEV Ray load_ray_geometry(const LpRays& r, int64_t i) {
   q.far_t = r.far_t[i];
   q.b = 0;
   return q;
-}
-
-LP_DEV float wave_sum(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-// inclusive prefix sum over the wave, lane 0 first
-LP_DEV float wave_scan(float x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-// inclusive suffix sum over the wave, lane 63 first
-LP_DEV float wave_rscan(float x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float y = __shfl_down(x, d, 64);
-    if (lane + d < 64) x += y;
-  }
-  return x;
 }
 
 // One lane per sample, n_items = n_rays * S_tot < 2^31 of them; the points leave through LDS so that a workgroup's 3 * 256 floats are

@@ -5,6 +5,7 @@
 
 #include "../../include/lightplane_hip.h"
 #include "../../include/lightplane_hip_samples.h"
+#include "../../include/lightplane_hip_importance.h"
 
 namespace lp {
 
@@ -148,6 +149,8 @@ const char* build_info_mesh();
 // sample placement and compositing of the ray march as ops of their own: lp_composite.hip (`a` checked by lp_api.hip; n_rays > 0)
 int ray_samples_launch(const LpRaySamplesArgs& a, bool backward, hipStream_t stream);
 int composite_launch(const LpCompositeArgs& a, bool backward, hipStream_t stream);
+// importance resampling of a ray's samples from its compositing weights: lp_importance.hip (`a` checked by lp_api.hip; n_rays > 0)
+int importance_launch(const LpImportanceArgs& a, bool backward, hipStream_t stream);
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

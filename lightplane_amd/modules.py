@@ -33,6 +33,7 @@ from .points import lightplane_eval_mlp as _fused_eval_mlp, lightplane_eval_mlp_
 from .renderer import _render, lightplane_renderer
 from .ray_clip import clip_rays_to_scaffold as _clip_rays_to_scaffold
 from .compositing import ray_samples as _ray_samples
+from .importance import importance_samples as _importance_samples
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .mesh import extract_mesh as _fused_extract_mesh
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
@@ -373,6 +374,12 @@ class LightplaneRenderer(torch.nn.Module):
         ``num_samples_inf`` and ``disparity_at_inf``: the samples ``forward`` marches for ``rays`` (without jitter), for a decoder of
         the caller's own and :func:`lightplane_amd.composite_samples`.  The points are not contracted."""
         return _ray_samples(rays, self.num_samples, self.num_samples_inf, disparity_at_inf=self.disparity_at_inf)
+
+    def importance_samples(self, rays: Rays, samples, weights: torch.Tensor, num_importance: int, **kw):
+        """:func:`lightplane_amd.importance_samples` on the depths of ``samples`` (a ``RaySamples``, as ``ray_samples`` returns):
+        ``num_importance`` new samples per ray drawn from the compositing ``weights`` of the coarse pass, merged into the coarse
+        ones -- the samples of the fine pass.  Keywords (``include_coarse``, ``pad``, ``jitter``) are passed on."""
+        return _importance_samples(rays, samples.depths, weights, num_importance, **kw)
 
     # -- ray encoding ---------------------------------------------------------------------
     def _get_ray_embedding(self, ray_directions: torch.Tensor) -> torch.Tensor:
