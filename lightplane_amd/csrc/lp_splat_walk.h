@@ -1,12 +1,15 @@
-// lp_splat_walk.h -- the Splatter's run-merged scatter walk on voxel grids, shared by the plain Splatter
-// (lp_splatter.hip: the splatted vector sits in registers) and the MFMA MLP-Splatter (lp_splatter_mlp_loop.h:
-// in an LDS tile).
+// lp_splat_walk.h -- the Splatter's run-merged scatter walks: a wave's items (rays, or the samples of one ray) are walked in order,
+// items that share a cell are summed in registers and leave as one row-contiguous atomic per run.  Two forms:
+//   * the per-slot walk (splat_walk, its loop splat_walk_slots): one accumulator per tap slot -- plane grids;
+//   * the voxel column walks (splat_walk_vox, splat_walk_vox_feat2): columns of a cell carried over unit steps.
+// Shared by the plain Splatter (lp_splatter.hip: the splatted vector sits in registers) and the MFMA MLP-Splatter
+// (lp_splatter_mlp_loop.h: in an LDS tile); the column walk also by the gradient scatter of the Renderer families (lp_mfma_common.h).
 #pragma once
 #include "lp_device.h"
 
 namespace lp {
 
-// value sources of splat_walk_vox: load8(j, c8, out) = channels (lane & 15) + 16 j of rays 8 c8 .. 8 c8 + 7
+// value sources of the walks: load8(j, c8, out) = channels (lane & 15) + 16 j of items 8 c8 .. 8 c8 + 7
 template <int CPL, int RPW>
 struct SplatSrcRegs {
   const float (&enc)[CPL][RPW];
@@ -33,6 +36,129 @@ struct SplatSrcLds {  // tile [channel][ld] in LDS
     out[4] = d1.x; out[5] = d1.y; out[6] = d1.z; out[7] = d1.w;
   }
 };
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The per-slot walk.  Lane layout: 16 lanes per tap slot (four slots per pass), lane `sub` owns channels sub, sub + 16, ... (C / 16 of
+// them): every atomic instruction covers four rows x 64 contiguous bytes.  All slots of a grid change cell together, so the run heads are
+// a wave-uniform bit mask (ballot of run_head() in the lane = item layout): the walk is scalar-branched, the row and the validity bits
+// of a run come from v_readlane, and the only LDS traffic is the bulk (b128) load of the weights and of an LDS value source.
+// (The gradient scatter of the Renderer families -- lp_mfma_common.h: the tail of scatter_grid, scatter_plane_ax, scatter_triplane --
+// is the same loop WRITTEN OUT three times, with a single-run fast path, a scalar row base and, on compile-time planes, a sentinel row
+// instead of validity bits.  Called from there this function cost time: the layer-looped backward at hidden 64 on a triplane ran
+// 1.7 % slower in its kernel, the two-grid backward 1 %, for the same work in another block layout and register colouring.  A fix to
+// the run logic here has to be made there as well.)
+//
+// One slot's walk over the wave's RPW items.  row0 / ok: per-lane row and validity bits of the wave's items (lane r = item r); koff:
+// rows of this lane's slot relative to row0; kbit: the slot's validity bit; w: the slot's row of the weight table [slot][item]; mask:
+// the run heads.  64-bit per-lane addresses: the Splatter takes grid-lists of any size.
+template <int C, int RPW, class Src>
+LP_DEV void splat_walk_slots(float* feat, int row0, int ok, int koff, unsigned kbit, int sub, const float* w, unsigned mask,
+                             const Src& src) {
+  constexpr int CPL = C / 16;
+  const float4* wsrc = reinterpret_cast<const float4*>(w);
+  float run[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
+  int s_row = __builtin_amdgcn_readlane(row0, 0);
+  unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
+#pragma unroll
+  for (int c8 = 0; c8 < RPW / 8; ++c8) {  // 8 items at a time
+    const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
+    const float wi[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    float v[CPL][8];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) src.load8(j, c8, v[j]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int rr = 8 * c8 + i;
+      if (rr > 0 && ((mask >> rr) & 1u)) {  // a run head: the old run leaves, the new one starts at zero in item rr's cell
+        if (s_ok & kbit) {
+#pragma unroll
+          for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
+        s_row = __builtin_amdgcn_readlane(row0, rr);
+        s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
+      }
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) run[j] = fmaf(wi[i], v[j][i], run[j]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (s_ok & kbit) {
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
+  }
+}
+
+// Unit weights of a per-slot walk: ONE more walk in which lane k < 8 owns tap slot k, so that a run costs a single atomic instruction
+// for all its slots (x-neighbours share a 64-byte segment of the weight grid).  wT: the weight table [slot][RPW].
+template <int RPW>
+LP_DEV void splat_walk_unit_weights(float* wgt, const TapSet& tp, bool voxel, unsigned mask, int lane, const float* wT) {
+  const int k = lane & 7;
+  const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
+  const unsigned kbit = (lane < 8 && k < (voxel ? 8 : 4)) ? (1u << k) : 0u;
+  const int row0 = tp.row0, ok = (int)tp.ok;
+  const float4* wsrc = reinterpret_cast<const float4*>(wT + k * RPW);
+  float runw = 0.0f;
+  int s_row = __builtin_amdgcn_readlane(row0, 0);
+  unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
+#pragma unroll
+  for (int c8 = 0; c8 < RPW / 8; ++c8) {
+    const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
+    const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int rr = 8 * c8 + i;
+      if (rr > 0 && ((mask >> rr) & 1u)) {
+        if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
+        runw = 0.0f;
+        s_row = __builtin_amdgcn_readlane(row0, rr);
+        s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
+      }
+      runw += w[i];
+    }
+  }
+  if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
+}
+
+// The Splatter's forward on one grid, slot by slot (plane grids; voxel grids take splat_walk_vox / splat_walk_vox2): tap set, weight
+// table wT[slot][RPW], run heads, then the feature walk -- one pass of four slots, two on a voxel grid -- and the unit-weight walk.
+// RPW items per wave: 32 rays (C = 16 / 32), 16 rays (C = 64), or 32 samples of one ray in the transposed march.
+template <int C, int RPW, class Src>
+LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live, int lane,
+                       const Src& src, float* wT) {
+  constexpr int NQ = 64 / RPW;   // lanes per item in the lane = item layout
+  constexpr int SPQ = 8 / NQ;    // tap-weight slots each of them writes
+  const int q = lane / RPW, r = lane % RPW, sub = lane & 15, grp = lane >> 4;
+  TapSet tp;
+  grid_tapset<true>(g, b, x, y, z, tp);
+  if (!live) {
+    tp.ok = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tp.w[k] = 0.0f;
+  }
+#pragma unroll
+  for (int i = 0; i < SPQ; ++i) {
+    float v = tp.w[i];
+#pragma unroll
+    for (int qq = 1; qq < NQ; ++qq) v = (q == qq) ? tp.w[qq * SPQ + i] : v;
+    wT[(q * SPQ + i) * RPW + r] = v;
+  }
+  const int row0 = tp.row0, ok = (int)tp.ok;
+  const int prow_ = lane_prev(row0), pok_ = lane_prev(ok);  // all lanes enabled: see run_head()
+  const bool head = run_head(r, row0, prow_, ok, pok_);
+  const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(head));
+  const bool voxel = g.D > 1 && g.H > 1 && g.W > 1;
+  const int n_pass = voxel ? 2 : 1;
+  for (int p = 0; p < n_pass; ++p) {
+    const int k = p * 4 + grp;
+    const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
+    splat_walk_slots<C, RPW>(feat, row0, ok, koff, 1u << k, sub, wT + k * RPW, mask, src);
+  }
+  splat_walk_unit_weights<RPW>(wgt, tp, voxel, mask, lane, wT);
+}
 
 // Unit weights of a voxel walk: x-neighbouring rows are neighbouring floats of the weight grid, so a 16-cell window of x per
 // (y, z) pair is kept in the lanes (lane = pair * 16 + x - window base) and written with ONE atomic

@@ -59,117 +59,23 @@ __global__ void __launch_bounds__(256) splat_fwd_kernel(const LpSplatterArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------
-// Forward, run-merged ("walk") variant for C in {16, 32}: one wave = 32 rays.
+// Forward, run-merged ("walk") variant for C in {16, 32, 64}: one wave = RPW rays (32; 16 at C = 64).
 // The encodings of the wave's rays are transposed once (LDS) so that every lane holds ONE channel
-// of all 32 rays in registers; lane group `grp` (C lanes) works on tap slot k of the current sample.
-// Rays are walked in order and consecutive rays that fall into the same cell (neighbouring pixels
-// usually do) are summed in a register: one row-contiguous atomic (+ one weight atomic) per RUN
-// instead of per ray.  Run boundaries are the same for all slots of a grid, i.e. one wave-uniform
-// bit mask (ballot in the lane = ray layout): the walk is scalar-branched, tap rows come from
-// v_readlane.  Same scheme as the Renderer's gradient scatter (lp_mfma_common.h).
+// of all RPW rays in registers.  Rays are walked in order and consecutive rays that fall into the
+// same cell (neighbouring pixels usually do) are summed in a register: one row-contiguous atomic
+// (+ one weight atomic) per RUN instead of per ray.  The walks themselves are those of
+// lp_splat_walk.h, shared with the MLP-Splatter: voxel grids take a column walk (splat_walk_vox,
+// also the Renderer's gradient scatter; or splat_walk_vox2 in the W2 kernels), plane grids the
+// per-slot walk (splat_walk), reading the registers through SplatSrcRegs.
 // ---------------------------------------------------------------------------------------
-// RPW rays per wave: 32 (C = 16 / 32), 16 (C = 64), 32 samples of one ray in the transposed march.
-// (Enc: enc[j][item] -- a register array [C / 16][RPW] of the wave's rays, or SplatEncConst for the transposed march)
+// The splatted vector of the transposed march (one ray: the same for every item) in the indexable form of splat_walk_vox2 --
+// enc[j][item], where the wave kernels pass a register array [C / 32][RPW]; the other walks take it as SplatSrcConst.
 template <int CPL>
 struct SplatEncConst {
   float v[CPL];
   struct Row { float x; LP_DEV float operator[](int) const { return x; } };
   LP_DEV Row operator[](int j) const { return Row{v[j]}; }
 };
-template <int C, int RPW, class Enc>
-LP_DEV void splat_walk(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live,
-                       int lane, const Enc& enc, float* wT) {
-  constexpr int CPL = C / 16;        // channels per lane: 16 lanes per tap slot, four slots per pass
-  constexpr int NQ = 64 / RPW;       // lanes per ray in the lane = ray layout
-  constexpr int SPQ = 8 / NQ;        // tap-weight slots each of them writes
-  const int q = lane / RPW, r = lane % RPW, sub = lane & 15, grp = lane >> 4;
-  TapSet tp;
-  grid_tapset<true>(g, b, x, y, z, tp);
-  if (!live) {
-    tp.ok = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tp.w[k] = 0.0f;
-  }
-#pragma unroll
-  for (int i = 0; i < SPQ; ++i) {
-    float v = tp.w[i];
-#pragma unroll
-    for (int qq = 1; qq < NQ; ++qq) v = (q == qq) ? tp.w[qq * SPQ + i] : v;
-    wT[(q * SPQ + i) * RPW + r] = v;
-  }
-  const int row0 = tp.row0;
-  const int ok = (int)tp.ok;
-  const int prow_ = lane_prev(row0), pok_ = lane_prev(ok);  // all lanes enabled: see run_head()
-  const bool head = run_head(r, row0, prow_, ok, pok_);
-  const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(head));
-  const bool voxel = g.D > 1 && g.H > 1 && g.W > 1;
-  const int n_pass = voxel ? 2 : 1;
-  for (int p = 0; p < n_pass; ++p) {
-    const int k = p * 4 + grp;
-    const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
-    const unsigned kbit = 1u << k;
-    const float4* wsrc = reinterpret_cast<const float4*>(wT + k * RPW);
-    float run[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
-    int s_row = __builtin_amdgcn_readlane(row0, 0);
-    unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
-#pragma unroll
-    for (int c8 = 0; c8 < RPW / 8; ++c8) {
-      const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
-      const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = 8 * c8 + i;
-        if (rr > 0 && ((mask >> rr) & 1u)) {
-          if (s_ok & kbit) {
-#pragma unroll
-            for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
-          }
-#pragma unroll
-          for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
-          s_row = __builtin_amdgcn_readlane(row0, rr);
-          s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
-        }
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) run[j] = fmaf(w[i], enc[j][rr], run[j]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (s_ok & kbit) {
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
-    }
-  }
-  // unit weights: ONE more walk in which lane j < 8 owns tap slot j, so that a run costs a single
-  // atomic instruction for all its slots (x-neighbours share a 64-byte segment of the weight grid)
-  {
-    const int k = lane & 7;
-    const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
-    const unsigned kbit = (lane < 8 && k < (voxel ? 8 : 4)) ? (1u << k) : 0u;
-    const float4* wsrc = reinterpret_cast<const float4*>(wT + k * RPW);
-    float runw = 0.0f;
-    int s_row = __builtin_amdgcn_readlane(row0, 0);
-    unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
-#pragma unroll
-    for (int c8 = 0; c8 < RPW / 8; ++c8) {
-      const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
-      const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = 8 * c8 + i;
-        if (rr > 0 && ((mask >> rr) & 1u)) {
-          if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
-          runw = 0.0f;
-          s_row = __builtin_amdgcn_readlane(row0, rr);
-          s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
-        }
-        runw += w[i];
-      }
-    }
-    if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
-  }
-}
 
 // W2 (all output grids voxel grids, C a multiple of 32): the voxel walk with two carry axes (splat_walk_vox2, lp_splat_walk.h) --
 // lane = channel of 32, lane group = corner along the third axis
@@ -236,7 +142,7 @@ __global__ void __launch_bounds__(256) splat_fwd_walk_kernel(const LpSplatterArg
         if (og.D > 1 && og.H > 1 && og.W > 1)
           splat_walk_vox<C, RPW, SplatSrcRegs<CPL, RPW>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, SplatSrcRegs<CPL, RPW>{enc}, wT);
         else
-          splat_walk<C, RPW>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
+          splat_walk<C, RPW>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, SplatSrcRegs<CPL, RPW>{enc}, wT);
       }
     }
   }
@@ -287,7 +193,7 @@ __global__ void __launch_bounds__(256) splat_fwd_ray_kernel(const LpSplatterArgs
           if (og.D > 1 && og.H > 1 && og.W > 1)
             splat_walk_vox<C, 32, SplatSrcConst<CPL>, true, WLD>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, src, wT);
           else
-            splat_walk<C, 32>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, enc, wT);
+            splat_walk<C, 32>(a.out_feature, a.out_weight, og, ray.b, x, y, z, live, lane, src, wT);
         }
       }
     }

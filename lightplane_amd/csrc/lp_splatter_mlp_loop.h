@@ -79,102 +79,6 @@ LP_DEV void sloop_load_encoding(const LpSplatterArgs& a, int64_t rid, int h, flo
   }
 }
 
-// Splatter-side walk of one plane output grid: the vector to splat sits in LDS as [channel][ray] (tile `vT`); features per
-// run and slot, then the unit weights eight slots at a time 
-template <int C>
-LP_DEV void sloop_walk_lds(float* feat, float* wgt, const LpGrid& g, int b, float x, float y, float z, bool live, int lane,
-                           const float* vT, float* wT) {
-  constexpr int CPL = C / 16;
-  const int h = lane >> 5, r = lane & 31, sub = lane & 15, grp = lane >> 4;
-  TapSet tp;
-  grid_tapset<true>(g, b, x, y, z, tp);
-  if (!live) {
-    tp.ok = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tp.w[k] = 0.0f;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) wT[(4 * h + i) * 32 + r] = h ? tp.w[4 + i] : tp.w[i];
-  const int row0 = tp.row0;
-  const int ok = (int)tp.ok;
-  const int prow_ = lane_prev(row0), pok_ = lane_prev(ok);
-  const bool head = run_head(r, row0, prow_, ok, pok_);
-  const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(head));
-  const bool voxel = g.D > 1 && g.H > 1 && g.W > 1;
-  const int n_pass = voxel ? 2 : 1;
-  for (int p = 0; p < n_pass; ++p) {
-    const int k = p * 4 + grp;
-    const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
-    const unsigned kbit = 1u << k;
-    const float4* wsrc = reinterpret_cast<const float4*>(wT + k * 32);
-    float run[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
-    int s_row = __builtin_amdgcn_readlane(row0, 0);
-    unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
-#pragma unroll
-    for (int c8 = 0; c8 < 4; ++c8) {
-      const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
-      const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-      float dx[CPL][8];
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) {
-        const float4* dsrc = reinterpret_cast<const float4*>(vT + (sub + 16 * j) * LT_LD);
-        const float4 d0 = dsrc[2 * c8], d1 = dsrc[2 * c8 + 1];
-        dx[j][0] = d0.x; dx[j][1] = d0.y; dx[j][2] = d0.z; dx[j][3] = d0.w;
-        dx[j][4] = d1.x; dx[j][5] = d1.y; dx[j][6] = d1.z; dx[j][7] = d1.w;
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = 8 * c8 + i;
-        if (rr > 0 && ((mask >> rr) & 1u)) {
-          if (s_ok & kbit) {
-#pragma unroll
-            for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
-          }
-#pragma unroll
-          for (int j = 0; j < CPL; ++j) run[j] = 0.0f;
-          s_row = __builtin_amdgcn_readlane(row0, rr);
-          s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
-        }
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) run[j] = fmaf(w[i], dx[j][i], run[j]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (s_ok & kbit) {
-#pragma unroll
-      for (int j = 0; j < CPL; ++j) atomic_add_f32(feat + (int64_t)(s_row + koff) * C + sub + 16 * j, run[j]);
-    }
-  }
-  {
-    const int k = lane & 7;
-    const int koff = (k & 1) * tp.su + ((k >> 1) & 1) * tp.sv + (k >> 2) * tp.st;
-    const unsigned kbit = (lane < 8 && k < (voxel ? 8 : 4)) ? (1u << k) : 0u;
-    const float4* wsrc = reinterpret_cast<const float4*>(wT + k * 32);
-    float runw = 0.0f;
-    int s_row = __builtin_amdgcn_readlane(row0, 0);
-    unsigned s_ok = (unsigned)__builtin_amdgcn_readlane(ok, 0);
-#pragma unroll
-    for (int c8 = 0; c8 < 4; ++c8) {
-      const float4 w0 = wsrc[2 * c8], w1 = wsrc[2 * c8 + 1];
-      const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int rr = 8 * c8 + i;
-        if (rr > 0 && ((mask >> rr) & 1u)) {
-          if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
-          runw = 0.0f;
-          s_row = __builtin_amdgcn_readlane(row0, rr);
-          s_ok = (unsigned)__builtin_amdgcn_readlane(ok, rr);
-        }
-        runw += w[i];
-      }
-    }
-    if (s_ok & kbit) atomic_add_f32(wgt + (int64_t)(s_row + koff), runw);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // forward: `rv` is a Renderer-shaped view of the arguments (rv.grid = the INPUT grid-list) for the Renderer's gather
 // ---------------------------------------------------------------------------------------------------------------
@@ -242,7 +146,7 @@ __global__ void __launch_bounds__(64 * NW, 2) splat_mlp_fwd_loop(const LpSplatte
       if (og.D > 1 && og.H > 1 && og.W > 1)
         splat_walk_vox<CO, 32>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, SplatSrcLds{vt, LT_LD, lane & 15}, wT);
       else
-        sloop_walk_lds<CO>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, vt, wT);
+        splat_walk<CO, 32>(a.out_feature, a.out_weight, og, ray.b, sm.x, sm.y, sm.z, live, lane, SplatSrcLds{vt, LT_LD, lane & 15}, wT);
     }
   }
 }

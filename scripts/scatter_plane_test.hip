@@ -28,8 +28,8 @@ __global__ void __launch_bounds__(64) k(float* gg, LpGrid g, const float* xyz, c
   for (int q = 0; q < C / 2; ++q) xt[featq(q, h) * DX_LD + r] = dx0[r * C + featq(q, h)];
   __syncthreads();
   const bool live = live_in[r] != 0;
-  if (mode == 0) scatter_grid<C, GM_TRIPLANE>(gg, g, 0, x, y, z, live, lane, xt, yt, 0);
-  else scatter_grid<C, GM_GENERIC>(gg, g, 0, x, y, z, live, lane, xt, yt, 0);
+  if (mode == 0) scatter_grid<C, GM_TRIPLANE>(gg, g, 0, x, y, z, live, lane, xt, yt);
+  else scatter_grid<C, GM_GENERIC>(gg, g, 0, x, y, z, live, lane, xt, yt);
 }
 
 static void cpu_ref(std::vector<float>& out, const LpGrid& g, int C, const float* xyz, const float* dx0, const int* live) {

@@ -9,8 +9,12 @@ is smaller than four bars and that the fp32 oracle meets the fp64 oracle at 2e-5
   ``oracle.splatter_sums`` -- the feature walk and the weight walk are separate code, after ``features / clamp(weights)`` an error of one is
   diluted by the other and a common one cancels --; the sets of non-zero cells exactly; the normalised output; two runs within 2e-5;
 * plain Splatter backward: one and several segments, the row-length hint with an image height that is a multiple of four and one that is not;
-* MLP-Splatter (layer-looped family, ``SplatSrcLds``): outputs and all gradients through ``check_mlp_splatter``;
-* tuned Renderer (``splat_walk_vox<.., SPLAT = false>`` of its gradient scatter), both march orders, through ``forced_oracle_check``.
+* MLP-Splatter (layer-looped family, ``SplatSrcLds``): outputs and all gradients through ``check_mlp_splatter``, with a voxel output
+  (``splat_walk_vox``) and with [voxel, xy plane] (``splat_walk``, the Splatter's per-slot walk, from the LDS tile; the backward's
+  ``scatter_grid<E, GM_GENERIC, false>`` runs the Renderer's written-out per-slot loop in two passes on the voxel input grid);
+* tuned Renderer, both march orders, through ``forced_oracle_check``: on a voxel grid (``splat_walk_vox<.., SPLAT = false>`` of its gradient
+  scatter), on a canonical triplane (``scatter_triplane``: sentinel rows) and on [voxel, xy plane] (the tail of ``scatter_grid``: rows and
+  validity bits).
 
 Bars, the project's own: 1e-4 of the tensor's largest entry against the fp64 oracle, 2e-5 between two runs / two launch orders."""
 import copy
@@ -142,34 +146,52 @@ def test_splatter_backward(name, C, row):
         _assert_close(f"{tag}: with against without the row-length hint", got, plain.cpu().numpy(), tol=RUN_TO_RUN)
 
 
+MLP_IN_BASE = (5, 6, 7)     # (D, H, W) of the MLP-Splatter's voxel input grid
+
+
+def _mlp_splatter(name, form):
+    from tests.synth import random_grids, random_splatter_mlp
+    from tests.test_gpu_coherent import check_mlp_splatter
+    case = WC.CASES[name]
+    gen = torch.Generator().manual_seed(5)
+    in_sizes = [[case.base[0], *MLP_IN_BASE, 32]]
+    out_sizes = WC.grid_sizes(case, 32, form)
+    mlp = random_splatter_mlp(gen, 2, 32, 32, 32, std=0.2)
+    d = dict(rays=WC.build_rays(case, 32), out_sizes=out_sizes, mlp=mlp, in_grids=random_grids(gen, in_sizes), in_sizes=in_sizes,
+             cfg=WC.splat_cfg(case), upstream=[torch.randn(*s, generator=gen) for s in out_sizes])
+    assert lp.mlp_splatter_kernel_family(out_sizes, mlp, in_sizes) == 3
+    check_mlp_splatter(d, _dev(), _lib.LP_KERNEL_AUTO, f"walk-transitions MLP-Splatter {name} {form}")
+
+
 @pytest.mark.parametrize("name", ["main", "main_mask"])
 def test_mlp_splatter_on_the_scripted_batch(name):
     """The MLP-Splatter's walk (``splat_walk_vox`` reading its LDS tile, lp_splatter_mlp_loop.h) on the main scripted batch, without and
     with the out-of-bounds mask (dead lanes: a carry refused by validity): a two-layer hidden-32 MLP, 32 -> 32 channels, voxel output,
     layer-looped family; outputs and every gradient as ``check_mlp_splatter`` compares them"""
-    from tests.synth import random_grids, random_splatter_mlp
-    from tests.test_gpu_coherent import check_mlp_splatter
-    case = WC.CASES[name]
-    gen = torch.Generator().manual_seed(5)
-    in_sizes = [[case.base[0], 5, 6, 7, 32]]
-    out_sizes = WC.grid_sizes(case, 32)
-    mlp = random_splatter_mlp(gen, 2, 32, 32, 32, std=0.2)
-    d = dict(rays=WC.build_rays(case, 32), out_sizes=out_sizes, mlp=mlp, in_grids=random_grids(gen, in_sizes), in_sizes=in_sizes,
-             cfg=WC.splat_cfg(case), upstream=[torch.randn(*s, generator=gen) for s in out_sizes])
-    assert lp.mlp_splatter_kernel_family(out_sizes, mlp, in_sizes) == 3
-    check_mlp_splatter(d, _dev(), _lib.LP_KERNEL_AUTO, f"walk-transitions MLP-Splatter {name}")
+    _mlp_splatter(name, "voxel")
+
+
+@pytest.mark.parametrize("name", ["main", "main_mask"])
+def test_mlp_splatter_with_a_plane_among_its_outputs(name):
+    """The same launch with [voxel, xy plane] outputs: the plane goes through the Splatter's per-slot walk (``splat_walk``: ``splat_walk_slots`` from the LDS
+    tile and ``splat_walk_unit_weights``), and the backward scatters the gradient of the voxel input grid with the two-pass
+    form of ``scatter_grid<E, GM_GENERIC, false>`` (tests/test_walk_transitions_host.py: which branches both take)"""
+    _mlp_splatter(name, "voxel+xy")
 
 
 RENDERER = [("main", 16, "rays"), ("main_mask", 32, "rays"), ("transposed_s40_mask", 16, "samples"), ("transposed_s33", 32, "samples"),
             ("long_z1500", 16, "rays")]
+RENDERER_PLANES = [(n, C, o, form) for n, C, o in (("main", 16, "rays"), ("main_mask", 32, "rays"), ("transposed_s33", 32, "samples"))
+                   for form in ("triplane", "voxel+xy")]
 
 
-def renderer_inputs(name, C):
-    """A tuned-family Renderer launch on the scripted batch: one voxel grid of the case's size, a 2/2/2 x 32 decoder"""
+def renderer_inputs(name, C, form="voxel"):
+    """A tuned-family Renderer launch on the scripted batch: the case's grid-list in ``form`` (one voxel grid of the case's size; a canonical
+    triplane; the voxel grid and an xy plane), a 2/2/2 x 32 decoder"""
     from tests.synth import random_decoder, random_grids
     case = WC.CASES[name]
     gen = torch.Generator().manual_seed(9 + C)
-    sizes = WC.grid_sizes(case, C)
+    sizes = WC.grid_sizes(case, C, form)
     dec = random_decoder(gen, 2, 2, 2, C, 32, 3, std=0.2)
     rays = WC.build_rays(case, int(dec.n_hidden_color[0]))
     n = rays.n_rays
@@ -184,9 +206,23 @@ def test_tuned_renderer_gradient_scatter(name, C, order):
     """The tuned Renderer's gradient scatter is the same one-axis walk in the Renderer's convention: every entry of ``grad_grid`` (and every
     other tensor) at 1e-4 with the backward's own ReLU decisions forced onto the fp64 oracle; both march orders; one carrier on the
     1 500-cell axis"""
-    d = renderer_inputs(name, C)
+    _tuned_renderer(name, C, order, "voxel")
+
+
+def _tuned_renderer(name, C, order, form):
+    d = renderer_inputs(name, C, form)
     assert lp.kernel_family(d["rays"], d["grids"], d["decoder"]) == 1
-    forced_oracle_check(f"walk-transitions Renderer {name} C={C} [{order}]", d, _dev(), chunk=d["rays"].n_rays, march_order=order)
+    forced_oracle_check(f"walk-transitions Renderer {name} C={C} [{order}] {form}", d, _dev(), chunk=d["rays"].n_rays, march_order=order)
     last = _lib.lib().lp_debug_last_renderer_backward
     last.restype = ctypes.c_char_p
     assert (b"transposed march" in last()) == (order == "samples"), f"march_order={order!r} launched {last()}"  # never a silent fall-back
+
+
+@pytest.mark.parametrize("name,C,order,form", RENDERER_PLANES, ids=[f"{n}-c{C}-{o}-{f}" for n, C, o, f in RENDERER_PLANES])
+def test_tuned_renderer_gradient_scatter_on_planes(name, C, order, form):
+    """The tuned Renderer's gradient scatter on plane grids, both march orders: a canonical triplane goes through ``scatter_triplane`` (the
+    per-slot run loop with sentinel rows and the single-run fast path, one plane after the other); the list [voxel, xy plane] is
+    ``GM_GENERIC`` -- the voxel grid takes the column walk, the plane the tail of ``scatter_grid`` (the same loop written out with rows and validity
+    bits).  tests/test_walk_transitions_host.py: every launch has single-run wave-samples, several-run ones and, masked, dead runs between
+    live ones"""
+    _tuned_renderer(name, C, order, form)

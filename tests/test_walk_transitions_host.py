@@ -254,3 +254,54 @@ def test_renderer_carriers_take_the_one_axis_walk_through_its_transitions(name, 
     assert not missed, f"Renderer carrier {name}: listed but not reached: {missed}"
     i64, _ = WC.cells_of(d["rays"], S, False, F64, O._unnormalize_renderer, (W, H, D))
     assert all(np.array_equal(a, b) for a, b in zip(idx, i64))
+
+
+# ---- the per-slot run loop: the launches that reach every site of it ------------------------------------------------------------------------------
+def _assert_slot_branches(tag, row, ok, masked, fast_path):
+    """One grid of one launch takes the branches of the per-slot run loop: a wave-sample that is a single live run (the fast path where
+    the site has one), one of two or more runs and, under the out-of-bounds mask, a dead run directly between two live ones."""
+    led = WC.classify_slot_runs(row, ok)
+    print(f"slot-walk ledger {tag}{' (single-run fast path)' if fast_path else ''}: {dict(led)}")
+    want = ["slot_single_live_run", "slot_several_runs"] + (["slot_dead_run_between_two_live_runs"] if masked else [])
+    missed = [p for p in want if led[p] == 0]
+    assert not missed, f"{tag}: not reached: {missed}"
+
+
+def _renderer_plane_launches():
+    from tests.test_gpu_walk_transitions import RENDERER_PLANES
+    return RENDERER_PLANES
+
+
+@pytest.mark.parametrize("name,C,order,form", _renderer_plane_launches(), ids=[f"{n}-c{C}-{o}-{f}" for n, C, o, f in _renderer_plane_launches()])
+def test_renderer_plane_launches_take_the_branches_of_the_slot_walk(name, C, order, form):
+    """The tuned backward on a canonical triplane (``scatter_triplane``: sentinel rows, per plane) and on [voxel, xy plane] (the tail of
+    ``scatter_grid`` on the plane: rows and validity bits), in the Renderer's un-normalisation, 32 rays or 32 samples of a ray per wave"""
+    import lightplane_amd as lp
+    from tests.test_gpu_walk_transitions import renderer_inputs
+    case = WC.CASES[name]
+    d = renderer_inputs(name, C, form)
+    assert lp.kernel_family(d["rays"], d["grids"], d["decoder"]) == 1
+    cfg = dict(num_samples=case.num_samples, mask_out_of_bounds_samples=case.mask)
+    dealing = "samples" if order == "samples" else "rays32"
+    tag = f"Renderer {name} C={C} [{order}] {form}"
+    if form == "triplane":
+        for g, row in enumerate(WC.triplane_sentinel_rows(d["rays"], cfg, case.base, dealing)):
+            _assert_slot_branches(f"{tag} plane {g}", row, row >= 0, case.mask, True)
+    else:
+        B, D, H, W = case.base
+        L = WC.plane_lanes(d["rays"], cfg, (B, 1, H, W), dealing, unnormalize=O._unnormalize_renderer)
+        _assert_slot_branches(f"{tag} xy plane", WC.plane_rows(L), L.ok, case.mask, True)
+
+
+@pytest.mark.parametrize("name", ["main", "main_mask"])
+def test_mlp_splatter_plane_launches_take_the_branches_of_the_slot_walk(name):
+    """The MLP-Splatter with [voxel, xy plane] outputs: its forward walks the plane slot by slot from the LDS tile (Splatter convention, no
+    fast path), its backward scatters the input-grid gradient with the two-pass form of ``scatter_grid`` (Renderer convention, voxel grid)"""
+    from tests.test_gpu_walk_transitions import MLP_IN_BASE
+    case = WC.CASES[name]
+    rays, cfg = WC.build_rays(case, 32), WC.splat_cfg(case)
+    B, D, H, W = case.base
+    L = WC.plane_lanes(rays, cfg, (B, 1, H, W), "rays32")
+    _assert_slot_branches(f"MLP-Splatter {name} forward, xy plane", WC.plane_rows(L), L.ok, case.mask, False)
+    L = WC.voxel_lanes(rays, cfg, (B,) + MLP_IN_BASE, "rays32", unnormalize=O._unnormalize_renderer)
+    _assert_slot_branches(f"MLP-Splatter {name} backward, voxel input grid", WC._rows(L), L.ok, case.mask, True)

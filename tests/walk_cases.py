@@ -1,10 +1,10 @@
 """Scripted ray batches for the run-merged scatter walks and the ledger of the transitions they take (tests/test_walk_transitions_host.py
 checks both without a GPU, tests/test_gpu_walk_transitions.py runs every user of the walks on them).
 
-The walks -- ``splat_walk`` and the two forward kernels of csrc/lp_splatter.hip, ``splat_walk_vox`` / ``splat_walk_vox_feat2`` /
-``splat_walk_vox_weights`` of csrc/lp_splat_walk.h, their mirror ``splat_bwd_walk_kernel`` -- decide what a wave does by how a lane's cell
-lies to its predecessor's.  A pinhole image or a batch of random rays reaches those decisions by chance; here a SCRIPT says which cell
-every lane of a wave sits in:
+The walks -- the two forward kernels of csrc/lp_splatter.hip, ``splat_walk`` (the per-slot loop ``splat_walk_slots`` and
+``splat_walk_unit_weights``) / ``splat_walk_vox`` / ``splat_walk_vox_feat2`` / ``splat_walk_vox_weights`` of
+csrc/lp_splat_walk.h, their mirror ``splat_bwd_walk_kernel`` -- decide what a wave does by how a lane's cell lies to its predecessor's.
+A pinhole image or a batch of random rays reaches those decisions by chance; here a SCRIPT says which cell every lane of a wave sits in:
 
 * ``march_order="rays"`` (lane = ray): a ``Wave`` is 32 lanes ``(ix, iy, iz, entry)`` plus one step per sample common to the wave, in whole
   cells, so the pattern of sample 0 moves through the grid unchanged.  Ray r is the segment from its point at sample 0 to its point at
@@ -247,11 +247,11 @@ def voxel_lanes(rays, case_or_cfg, base, dealing, row_length=0, unnormalize=O._u
     return Lanes(rays.grid_idx.numpy().astype(np.int64)[ray], i, ok, alive, (W, H, D))
 
 
-def plane_lanes(rays, cfg, shape, dealing, row_length=0) -> Lanes:
+def plane_lanes(rays, cfg, shape, dealing, row_length=0, unnormalize=O._unnormalize_splatter) -> Lanes:
     """Lanes of a plane grid ``[B, D, H, W]`` with one singleton axis (csrc/lp_device.h ``grid_tapset``: u / v axes); ``i`` = (iu, iv, 0)."""
     B, D, H, W = shape
     S, mask = cfg["num_samples"], cfg["mask_out_of_bounds_samples"]
-    idx, live = cells_of(rays, S, mask, torch.float32, O._unnormalize_splatter, (max(W, 1), max(H, 1), max(D, 1)))
+    idx, live = cells_of(rays, S, mask, torch.float32, unnormalize, (max(W, 1), max(H, 1), max(D, 1)))
     ua, va = (0, 1) if D == 1 else ((0, 2) if H == 1 else (1, 2))
     U, V = (W, H, D)[ua], (W, H, D)[va]
     ray, samp, alive = deal(rays.directions.shape[0], S, dealing, row_length)
@@ -553,10 +553,10 @@ def classify_window(L: Lanes, out: Optional[Ledger] = None) -> Ledger:
 
 
 def classify_plane(L: Lanes, out: Optional[Ledger] = None) -> Ledger:
-    """``splat_walk`` on a plane grid: runs of one row and their heads"""
+    """``splat_walk`` (``splat_walk_slots``) on a plane grid: runs of one row and their heads"""
     out = Ledger() if out is None else out
     U, V, _ = L.size
-    row = L.b * (U * V) + L.i[1] * U + L.i[0]
+    row = plane_rows(L)
     ok = L.ok
     okp, okn = ok[:, :-1], ok[:, 1:]
     dr = row[:, 1:] - row[:, :-1]
@@ -573,6 +573,48 @@ def classify_plane(L: Lanes, out: Optional[Ledger] = None) -> Ledger:
     out.reach("plane_other_entry", head & (db != 0) & both)
     out.reach("plane_dead_lane_next_to_a_live_one", (okp != 0) != (okn != 0))
     out.reach("plane_row_alias_u_end_against_next_v_line", head & (dr == 0) & (db == 0) & ((okp | okn) != 0))
+    return out
+
+
+def plane_rows(L: Lanes):
+    """row of the first tap of every lane of ``plane_lanes``"""
+    U, V, _ = L.size
+    return L.b * (U * V) + L.i[1] * U + L.i[0]
+
+
+def triplane_sentinel_rows(rays, cfg, base, dealing):
+    """csrc/lp_mfma_common.h ``scatter_triplane`` (the tuned Renderer's backward on a canonical triplane, Renderer convention): per plane
+    xy, xz, yz the row of every lane, [N, L] -- the first cell of each axis clamped to [0, size - 2] (``axis_norm``: a border cell is
+    re-expressed with all four corners in range), the sentinel -1 where the lane is not live or an axis has no tap in range."""
+    B, D, H, W = base
+    S, mask = cfg["num_samples"], cfg["mask_out_of_bounds_samples"]
+    idx, live = cells_of(rays, S, mask, torch.float32, O._unnormalize_renderer, (W, H, D))
+    ray, samp, alive = deal(rays.directions.shape[0], S, dealing)
+    lv = live[ray, samp] & alive
+    b = rays.grid_idx.numpy().astype(np.int64)[ray]
+    cell, dead = [], []
+    for a, n in zip(idx, (W, H, D)):
+        i0 = a[ray, samp]
+        dead.append(~(((i0 >= 0) & (i0 <= n - 1)) | ((i0 + 1 >= 0) & (i0 + 1 <= n - 1))))
+        cell.append(np.clip(i0, 0, n - 2))
+    (ax, ay, az), (dx, dy, dz) = cell, dead
+    return [np.where(~lv | dx | dy, -1, (b * H + ay) * W + ax), np.where(~lv | dx | dz, -1, (b * D + az) * W + ax),
+            np.where(~lv | dy | dz, -1, (b * D + az) * H + ay)]
+
+
+def classify_slot_runs(row, ok, out: Optional[Ledger] = None) -> Ledger:
+    """The branches of a per-slot run loop (csrc/lp_splat_walk.h ``splat_walk_slots``, its written-out forms in csrc/lp_mfma_common.h) over the wave-samples ``[N, L]`` of one grid: a head is lane 0 and
+    every lane whose row or validity bits differ from its predecessor's (``run_head``); a run is live if its validity bits are not 0.
+    For the sentinel-row policy pass ``ok = row >= 0``."""
+    out = Ledger() if out is None else out
+    ok = np.asarray(ok).astype(np.int64)
+    head = np.concatenate([np.ones((row.shape[0], 1), dtype=bool), (row[:, 1:] != row[:, :-1]) | (ok[:, 1:] != ok[:, :-1])], axis=1)
+    for w in range(row.shape[0]):
+        live = ok[w, np.flatnonzero(head[w])] != 0
+        out["slot_single_live_run"] += int(len(live) == 1 and live[0])
+        out["slot_single_dead_run"] += int(len(live) == 1 and not live[0])
+        out["slot_several_runs"] += int(len(live) >= 2)
+        out["slot_dead_run_between_two_live_runs"] += int(np.count_nonzero(live[:-2] & ~live[1:-1] & live[2:]))
     return out
 
 
