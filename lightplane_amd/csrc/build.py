@@ -21,9 +21,9 @@ SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_stream.hip", "lp_renderer_l
            "lp_splatter_mlp_loop.hip", "lp_splatter_mlp_loop_dump.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
            "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_dump.hip", "lp_splatter_mlp_loop_shallow.hip",
            "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_grid_tv.hip", "lp_grid_resample.hip", "lp_scaffold.hip", "lp_points.hip", "lp_point_grid.hip", "lp_ray_clip.hip", "lp_mesh.hip", "lp_composite.hip", "lp_importance.hip", "lp_api.hip"]
-HEADERS = ["lp_device.h", "lp_host.h", "lp_plane_range.h", "lp_mfma_common.h", "lp_generic_mlp.h", "lp_generic_decode.h", "lp_column_mlp.h", "lp_point_grad.h", "lp_splat_walk.h", "lp_bf3.h", "lp_loop.h", "lp_renderer_loop.h",
-           "lp_renderer_mfma_bwd.h", "lp_splatter_mlp.h", "lp_splatter_mlp_loop.h", "lp_mc_table.h", "lp_wave.h", os.path.join("..", "..", "include", "lightplane_hip.h"),
-           os.path.join("..", "..", "include", "lightplane_hip_samples.h"), os.path.join("..", "..", "include", "lightplane_hip_importance.h")]
+PUBLIC_HEADERS = [os.path.join("..", "..", "include", name) for name in ("lightplane_hip.h", "lightplane_hip_samples.h", "lightplane_hip_importance.h")]
+# every header of this directory (the rule of source_hash()) and the public ones: a change to any of them recompiles everything
+HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + PUBLIC_HEADERS
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
     "-fno-gpu-rdc", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function",
@@ -70,7 +70,7 @@ def source_hash():
     with the tree."""
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(HERE) if f.endswith((".hip", ".h")) or f == "build.py")
-    paths = [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, "..", "..", "include", name) for name in ("lightplane_hip.h", "lightplane_hip_samples.h", "lightplane_hip_importance.h")]
+    paths = [os.path.join(HERE, f) for f in files] + [os.path.join(HERE, p) for p in PUBLIC_HEADERS]
     for p in paths:
         h.update(os.path.basename(p).encode() + b"\0")
         with open(p, "rb") as f:

@@ -7,8 +7,8 @@
 // channel unit (V = 4 floats where C % 4 == 0, one float otherwise), floor(64 / CV) samples of CV = C / V units go through the wave per
 // load instruction, and lanes of equal unit are folded through LDS at the end.  CV > 64 (C = 65 .. 127, not a multiple of 4): two units
 // per lane, one sample per step.
-#include "lp_device.h"
 #include "lp_host.h"
+#include "lp_rows.h"
 #include "lp_wave.h"
 
 namespace lp {
@@ -29,12 +29,7 @@ struct RsArgs {
 // grid_idx is not read (it may be NULL): the ray's geometry only
 LP_DEV Ray load_ray_geometry(const LpRays& r, int64_t i) {
   Ray q;
-  q.ox = r.origins[3 * i + 0];
-  q.oy = r.origins[3 * i + 1];
-  q.oz = r.origins[3 * i + 2];
-  q.dx = r.directions[3 * i + 0];
-  q.dy = r.directions[3 * i + 1];
-  q.dz = r.directions[3 * i + 2];
+  load_ray_line(r.origins, r.directions, i, q);
   q.near_t = r.near_t[i];
   q.far_t = r.far_t[i];
   q.b = 0;
@@ -155,24 +150,6 @@ struct FeatLanes {
   }
 };
 
-template <int V>
-LP_DEV void load_units(const float* p, float (&f)[V]) {
-  if constexpr (V == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    f[0] = t.x, f[1] = t.y, f[2] = t.z, f[3] = t.w;
-  } else {
-    f[0] = *p;
-  }
-}
-template <int V>
-LP_DEV void store_units(float* p, const float (&f)[V]) {
-  if constexpr (V == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-  } else {
-    *p = f[0];
-  }
-}
-
 // dynamic LDS: wl[64] | fold[NB * 64 * V]
 template <int V, int NB>
 __global__ __launch_bounds__(64) void composite_fwd(CpArgs a) {
@@ -217,11 +194,10 @@ __global__ __launch_bounds__(64) void composite_fwd(CpArgs a) {
         for (int b = 0; b < NB; ++b) {
           const int u = fl.u0 + 64 * b;
           if (lane < fl.A && sl < n && u < fl.CV) {
-            float f[V];
-            load_units<V>(f0 + (int64_t)sl * C + u * V, f);
+            const Vec<V> f = vec_load<V>(f0 + (int64_t)sl * C + u * V);
             const float ws = wl[sl];
 #pragma unroll
-            for (int v = 0; v < V; ++v) acc[b][v] = fmaf(ws, f[v], acc[b][v]);
+            for (int v = 0; v < V; ++v) acc[b][v] = fmaf(ws, f.v[v], acc[b][v]);
           }
         }
       }
@@ -244,13 +220,13 @@ __global__ __launch_bounds__(64) void composite_fwd(CpArgs a) {
     for (int b = 0; b < NB; ++b) {
       const int u = lane + 64 * b;
       if (lane < (NB == 2 ? 64 : fl.CV) && u < fl.CV) {
-        float sum[V];
+        Vec<V> sum;
 #pragma unroll
-        for (int v = 0; v < V; ++v) sum[v] = 0.0f;
+        for (int v = 0; v < V; ++v) sum.v[v] = 0.0f;
         for (int g = 0; g < fl.G; ++g)
 #pragma unroll
-          for (int v = 0; v < V; ++v) sum[v] += fold[(b * 64 + g * fl.CV + lane) * V + v];
-        store_units<V>(a.feature + r * C + u * V, sum);
+          for (int v = 0; v < V; ++v) sum.v[v] += fold[(b * 64 + g * fl.CV + lane) * V + v];
+        vec_store<V>(a.feature + r * C + u * V, sum);
       }
     }
   }
@@ -324,19 +300,18 @@ __global__ __launch_bounds__(64) void composite_bwd(CpArgs a) {
             if (lane < fl.A && sl < n && u < fl.CV) {
               const int64_t at = f0 + (int64_t)sl * C + u * V;
               if (need_dot) {
-                float f[V];
-                load_units<V>(a.features + at, f);
+                const Vec<V> f = vec_load<V>(a.features + at);
                 float p = 0.0f;
 #pragma unroll
-                for (int v = 0; v < V; ++v) p = fmaf(f[v], gf[b][v], p);
+                for (int v = 0; v < V; ++v) p = fmaf(f.v[v], gf[b][v], p);
                 P[sl * stride + u] = p;
               }
               if (a.g_features) {
                 const float ws = wl[sl];
-                float g[V];
+                Vec<V> g;
 #pragma unroll
-                for (int v = 0; v < V; ++v) g[v] = ws * gf[b][v];
-                store_units<V>(a.g_features + at, g);
+                for (int v = 0; v < V; ++v) g.v[v] = ws * gf[b][v];
+                vec_store<V>(a.g_features + at, g);
               }
             }
           }
@@ -364,6 +339,7 @@ __global__ __launch_bounds__(64) void composite_bwd(CpArgs a) {
 template <int V, int NB>
 void composite_launch_as(const CpArgs& s, bool backward, hipStream_t stream) {
   const int CV = s.C / V;
+  // (one workgroup per ray: check_point_batch of lp_api.hip keeps n_rays * n_samples, hence n_rays, below 2^31)
   if (backward) {
     const size_t lds = sizeof(float) * (size_t)(64 + CB_SUPER + 64 * (CV | 1));
     hipLaunchKernelGGL((composite_bwd<V, NB>), dim3((unsigned)s.n_rays), dim3(64), lds, stream, s);
@@ -384,15 +360,16 @@ int ray_samples_launch(const LpRaySamplesArgs& a, bool backward, hipStream_t str
   s.g_points = a.grad_points, s.g_depths = a.grad_depths, s.g_deltas = a.grad_deltas;
   s.g_origins = a.grad_origins, s.g_directions = a.grad_directions, s.g_near = a.grad_near, s.g_far = a.grad_far;
   const int S_tot = a.march.num_samples + a.march.num_samples_inf;
+  unsigned blocks;
   if (backward) {
     if (!s.g_origins && !s.g_directions && !s.g_near && !s.g_far) return LP_OK;
-    const int64_t blocks = (a.rays.n_rays + RS_THREADS / 64 - 1) / (RS_THREADS / 64);
-    hipLaunchKernelGGL(ray_samples_bwd, dim3((unsigned)blocks), dim3(RS_THREADS), 0, stream, s, S_tot);
+    if (int rc = launch_blocks("lp_ray_samples_backward", a.rays.n_rays, RS_THREADS / 64, blocks)) return rc;
+    hipLaunchKernelGGL(ray_samples_bwd, dim3(blocks), dim3(RS_THREADS), 0, stream, s, S_tot);
     return check_launch("ray_samples_bwd");
   }
   const int64_t n_items = a.rays.n_rays * S_tot;
-  const int64_t blocks = (n_items + RS_THREADS - 1) / RS_THREADS;
-  hipLaunchKernelGGL(ray_samples_fwd, dim3((unsigned)blocks), dim3(RS_THREADS), 0, stream, s, S_tot, n_items);
+  if (int rc = launch_blocks("lp_ray_samples_forward", n_items, RS_THREADS, blocks)) return rc;
+  hipLaunchKernelGGL(ray_samples_fwd, dim3(blocks), dim3(RS_THREADS), 0, stream, s, S_tot, n_items);
   return check_launch("ray_samples_fwd");
 }
 

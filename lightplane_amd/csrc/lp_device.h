@@ -25,14 +25,19 @@ struct Ray {
   int b;  // grid batch index
 };
 
+// origin and direction of ray i; the other fields are the caller's
+LP_DEV void load_ray_line(const float* origins, const float* directions, int64_t i, Ray& q) {
+  q.ox = origins[3 * i + 0];
+  q.oy = origins[3 * i + 1];
+  q.oz = origins[3 * i + 2];
+  q.dx = directions[3 * i + 0];
+  q.dy = directions[3 * i + 1];
+  q.dz = directions[3 * i + 2];
+}
+
 LP_DEV Ray load_ray(const LpRays& r, int64_t i) {
   Ray q;
-  q.ox = r.origins[3 * i + 0];
-  q.oy = r.origins[3 * i + 1];
-  q.oz = r.origins[3 * i + 2];
-  q.dx = r.directions[3 * i + 0];
-  q.dy = r.directions[3 * i + 1];
-  q.dz = r.directions[3 * i + 2];
+  load_ray_line(r.origins, r.directions, i, q);
   q.near_t = r.near_t[i];
   q.far_t = r.far_t[i];
   q.b = r.grid_idx[i];
@@ -407,6 +412,23 @@ LP_DEV void grid_tapset(const LpGrid& g, int b, float x, float y, float z, TapSe
 #pragma unroll
     for (int k = 4; k < 8; ++k) t.w[k] = 0.0f;
   }
+}
+
+// (x, y, z, b) of point n = ((b D + z) H + y) W + x of a [B, D, H, W] lattice.  I: the type the divisions are done in -- int64_t for
+// any lattice, uint32_t where the caller knows n < 2^31 (a 64-bit division costs several times a 32-bit one).
+struct LatticePoint {
+  int x, y, z, b;
+};
+template <typename I>
+LP_DEV LatticePoint lattice_point(I n, int W, int H, int D) {
+  LatticePoint p;
+  p.x = (int)(n % (I)W);
+  const I r1 = n / (I)W;
+  p.y = (int)(r1 % (I)H);
+  const I r2 = r1 / (I)H;
+  p.z = (int)(r2 % (I)D);
+  p.b = (int)(r2 / (I)D);
+  return p;
 }
 
 // nearest-neighbour scaffold lookup (round-half-even like F.grid_sample(mode="nearest")),

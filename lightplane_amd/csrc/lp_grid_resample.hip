@@ -18,8 +18,8 @@
 // candidate outputs from the inverse mapping, widened by a margin, narrows the range to the outputs whose recomputed taps touch its
 // cell (they are contiguous: src is monotone in o), and sums weight * grad_out over the box in a fixed order (z, y, x ascending).
 // Correct for any size ratio (an input cell no output touches gets 0); the margin only costs time.
-#include "lp_device.h"
 #include "lp_host.h"
+#include "lp_rows.h"
 
 namespace lp {
 
@@ -37,32 +37,6 @@ struct RsGrid {
   int32_t cgn;       // lane positions per cell: C / VEC
   uint32_t tiles;    // ceil(H * W * cgn / RS_THREADS) of the lane-owning side
 };
-
-template <int VEC>
-struct RsVec {
-  float v[VEC];
-};
-
-template <int VEC>
-LP_DEV RsVec<VEC> rs_load(const float* p) {
-  RsVec<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-template <int VEC>
-LP_DEV void rs_store(float* p, const RsVec<VEC>& r) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else {
-    *p = r.v[0];
-  }
-}
 
 struct RsTap {
   int32_t i0, i1;
@@ -128,11 +102,11 @@ __global__ void __launch_bounds__(RS_THREADS) grid_resample_fwd(const RsGrid a) 
   const RsTap tx = rs_tap(l.x, a.a[2], a.align, a.sn[2]);
   const int32_t iz[2] = {tz.i0, tz.i1}, iy[2] = {ty.i0, ty.i1}, ix[2] = {tx.i0, tx.i1};
   const float wz[2] = {tz.w0, tz.w1}, wy[2] = {ty.w0, ty.w1}, wx[2] = {tx.w0, tx.w1};
-  RsVec<VEC> v[8];
+  Vec<VEC> v[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k)
-    v[k] = rs_load<VEC>(a.in + rs_elem(a.sn, l.b, iz[k >> 2], iy[(k >> 1) & 1], ix[k & 1], C) + l.c0);
-  RsVec<VEC> acc;
+    v[k] = vec_load<VEC>(a.in + rs_elem(a.sn, l.b, iz[k >> 2], iy[(k >> 1) & 1], ix[k & 1], C) + l.c0);
+  Vec<VEC> acc;
 #pragma unroll
   for (int c = 0; c < VEC; ++c) acc.v[c] = 0.0f;
 #pragma unroll
@@ -141,7 +115,7 @@ __global__ void __launch_bounds__(RS_THREADS) grid_resample_fwd(const RsGrid a) 
 #pragma unroll
     for (int c = 0; c < VEC; ++c) acc.v[c] += w * v[k].v[c];
   }
-  rs_store<VEC>(a.out + rs_elem(a.dn, l.b, l.z, l.y, l.x, C) + l.c0, acc);
+  vec_store<VEC>(a.out + rs_elem(a.dn, l.b, l.z, l.y, l.x, C) + l.c0, acc);
 }
 
 // Outputs [lo, hi] of an axis whose taps touch input cell i (empty: lo > hi).  Candidates: src(o) within (i - 1, i + 1) inverted in
@@ -188,7 +162,7 @@ __global__ void __launch_bounds__(RS_THREADS) grid_resample_bwd(const RsGrid a) 
   rs_range(l.z, a.a[0], a.ia[0], a.align, a.sn[0], a.dn[0], zlo, zhi);
   rs_range(l.y, a.a[1], a.ia[1], a.align, a.sn[1], a.dn[1], ylo, yhi);
   rs_range(l.x, a.a[2], a.ia[2], a.align, a.sn[2], a.dn[2], xlo, xhi);
-  RsVec<VEC> acc;
+  Vec<VEC> acc;
 #pragma unroll
   for (int c = 0; c < VEC; ++c) acc.v[c] = 0.0f;
   for (int32_t oz = zlo; oz <= zhi; ++oz) {
@@ -198,7 +172,7 @@ __global__ void __launch_bounds__(RS_THREADS) grid_resample_bwd(const RsGrid a) 
       const float* p = a.in + rs_elem(a.dn, l.b, oz, oy, xlo, C) + l.c0;
       for (int32_t ox = xlo; ox <= xhi; ++ox, p += C) {
         const float w = wzy * rs_weight(ox, l.x, a.a[2], a.align, a.sn[2]);
-        const RsVec<VEC> g = rs_load<VEC>(p);
+        const Vec<VEC> g = vec_load<VEC>(p);
 #pragma unroll
         for (int c = 0; c < VEC; ++c) acc.v[c] += w * g.v[c];
       }
@@ -206,11 +180,11 @@ __global__ void __launch_bounds__(RS_THREADS) grid_resample_bwd(const RsGrid a) 
   }
   float* po = a.out + rs_elem(a.sn, l.b, l.z, l.y, l.x, C) + l.c0;
   if (ACC) {
-    const RsVec<VEC> old = rs_load<VEC>(po);
+    const Vec<VEC> old = vec_load<VEC>(po);
 #pragma unroll
     for (int c = 0; c < VEC; ++c) acc.v[c] = old.v[c] + acc.v[c];
   }
-  rs_store<VEC>(po, acc);
+  vec_store<VEC>(po, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -229,10 +203,8 @@ float grid_resample_coeff(int n_in, int n_out, bool align) {
 int grid_resample_launch(const LpGridList& src, const LpGridList& dst, int align, const float* coeffs, bool backward, bool accumulate,
                          hipStream_t stream) {
   const int C = src.channels;
-  int vec = (C & 3) == 0 ? 4 : 1;
-  for (int g = 0; g < src.n_grids && vec == 4; ++g) {
-    if ((((uintptr_t)src.grids[g].data | (uintptr_t)dst.grids[g].data) & 15) != 0) vec = 1;
-  }
+  int vec = row_vec(C, {});
+  for (int g = 0; g < src.n_grids && vec == 4; ++g) vec = row_vec(C, {src.grids[g].data, dst.grids[g].data});
   for (int g = 0; g < src.n_grids; ++g) {
     const LpGrid& s = src.grids[g];
     const LpGrid& d = dst.grids[g];
@@ -253,11 +225,10 @@ int grid_resample_launch(const LpGridList& src, const LpGridList& dst, int align
     const int32_t* own = backward ? t.sn : t.dn;  // the side whose cells the lanes own
     const int64_t items = (int64_t)own[1] * own[2] * t.cgn;
     const int64_t tiles = (items + RS_THREADS - 1) / RS_THREADS;
-    const int64_t blocks = tiles * own[0] * (int64_t)t.B;
-    if (blocks >= ((int64_t)1 << 31))
-      return set_error(LP_EUNSUPPORTED, "grid_resample: grid %d needs %lld workgroups", g, (long long)blocks);
+    unsigned blocks;
+    if (int rc = launch_blocks("lp_grid_resample", tiles * own[0] * (int64_t)t.B, 1, blocks)) return rc;
     t.tiles = (uint32_t)tiles;
-    const dim3 gr((unsigned)blocks), bl(RS_THREADS);
+    const dim3 gr(blocks), bl(RS_THREADS);
     if (!backward) {
       if (vec == 4) hipLaunchKernelGGL((grid_resample_fwd<4>), gr, bl, 0, stream, t);
       else hipLaunchKernelGGL((grid_resample_fwd<1>), gr, bl, 0, stream, t);

@@ -17,8 +17,8 @@
 // the workgroup writes ONE fp64 partial into the workspace; grid_tv_finish (one workgroup) sums the partials in fp64 and writes the
 // fp32 scalar.  The gradient is in gather form: every element is computed from its six neighbours and stored once with a vector
 // store (overwrite, or read-add-store for the accumulate mode) -- bit-reproducible.
-#include "lp_device.h"
 #include "lp_host.h"
+#include "lp_rows.h"
 
 namespace lp {
 
@@ -38,32 +38,6 @@ struct TvGrid {
   float scale;             // ... times this: the factor of the stored gradient
   double* partials;        // one per workgroup of this launch
 };
-
-template <int VEC>
-struct TvVec {
-  float v[VEC];
-};
-
-template <int VEC>
-LP_DEV TvVec<VEC> tv_load(const float* p) {
-  TvVec<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-template <int VEC>
-LP_DEV void tv_store(float* p, const TvVec<VEC>& r) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else {
-    *p = r.v[0];
-  }
-}
 
 template <int P>
 LP_DEV float tv_phi(float d) {
@@ -112,19 +86,19 @@ __global__ void __launch_bounds__(TV_THREADS) grid_tv_sweep(const TvGrid a) {
     const float* px = a.x + off0;
     float s = 1.0f;
     if (GRAD) s = a.scale * (a.grad_loss ? *a.grad_loss : 1.0f);
-    TvVec<VEC> cur = tv_load<VEC>(px);
-    TvVec<VEC> prev = cur;  // a missing neighbour is the cell itself: its difference is 0, and phi(0) = phi'(0) = 0
-    if (GRAD && z0 > 0) prev = tv_load<VEC>(px - sz);
+    Vec<VEC> cur = vec_load<VEC>(px);
+    Vec<VEC> prev = cur;  // a missing neighbour is the cell itself: its difference is 0, and phi(0) = phi'(0) = 0
+    if (GRAD && z0 > 0) prev = vec_load<VEC>(px - sz);
     for (int32_t z = z0; z < z1; ++z, px += sz) {
-      const TvVec<VEC> nxt = z + 1 < a.D ? tv_load<VEC>(px + sz) : cur;
-      const TvVec<VEC> xp = has_xp ? tv_load<VEC>(px + sx) : cur;
-      const TvVec<VEC> yp = has_yp ? tv_load<VEC>(px + sy) : cur;
-      TvVec<VEC> xm = cur, ym = cur;
+      const Vec<VEC> nxt = z + 1 < a.D ? vec_load<VEC>(px + sz) : cur;
+      const Vec<VEC> xp = has_xp ? vec_load<VEC>(px + sx) : cur;
+      const Vec<VEC> yp = has_yp ? vec_load<VEC>(px + sy) : cur;
+      Vec<VEC> xm = cur, ym = cur;
       if (GRAD) {
-        if (has_xm) xm = tv_load<VEC>(px - sx);
-        if (has_ym) ym = tv_load<VEC>(px - sy);
+        if (has_xm) xm = vec_load<VEC>(px - sx);
+        if (has_ym) ym = vec_load<VEC>(px - sy);
       }
-      TvVec<VEC> out;
+      Vec<VEC> out;
 #pragma unroll
       for (int c = 0; c < VEC; ++c) {
         const float dw = xp.v[c] - cur.v[c], dh = yp.v[c] - cur.v[c], dd = nxt.v[c] - cur.v[c];
@@ -143,11 +117,11 @@ __global__ void __launch_bounds__(TV_THREADS) grid_tv_sweep(const TvGrid a) {
       if (GRAD) {
         float* pg = a.g + (px - a.x);
         if (ACC) {
-          const TvVec<VEC> old = tv_load<VEC>(pg);
+          const Vec<VEC> old = vec_load<VEC>(pg);
 #pragma unroll
           for (int c = 0; c < VEC; ++c) out.v[c] = old.v[c] + out.v[c];
         }
-        tv_store<VEC>(pg, out);
+        vec_store<VEC>(pg, out);
       }
       prev = cur;
       cur = nxt;
@@ -171,8 +145,6 @@ __global__ void __launch_bounds__(TV_THREADS) grid_tv_finish(const double* parti
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
-
-static inline int tv_vec(const LpGridList& gl) { return (gl.channels & 3) == 0 ? 4 : 1; }
 
 static inline int64_t tv_grid_blocks(const LpGrid& d, int channels, int vec) {
   const int64_t items = (int64_t)d.H * d.W * (channels / vec);
@@ -212,11 +184,8 @@ int grid_tv_launch(const LpGridList& gl, const float* weights, int p, float* los
                    float scale, float* const* grads, bool accumulate, hipStream_t stream) {
   const bool want_loss = loss != nullptr, want_grad = grads != nullptr;
   const int C = gl.channels;
-  int vec = tv_vec(gl);
-  for (int g = 0; g < gl.n_grids && vec == 4; ++g) {
-    if (((uintptr_t)gl.grids[g].data & 15) != 0) vec = 1;
-    if (want_grad && ((uintptr_t)grads[g] & 15) != 0) vec = 1;
-  }
+  int vec = row_vec(C, {});
+  for (int g = 0; g < gl.n_grids && vec == 4; ++g) vec = row_vec(C, {gl.grids[g].data, want_grad ? grads[g] : nullptr});
   int64_t done = 0;
   for (int g = 0; g < gl.n_grids; ++g) {
     const LpGrid& d = gl.grids[g];
@@ -240,14 +209,14 @@ int grid_tv_launch(const LpGridList& gl, const float* weights, int p, float* los
     t.grad_loss = grad_loss;
     t.scale = scale;
     t.partials = want_loss ? workspace + done : nullptr;
-    const int64_t blocks = tv_grid_blocks(d, C, vec);
-    if (blocks >= ((int64_t)1 << 31)) return set_error(LP_EUNSUPPORTED, "grid_tv: grid %d needs %lld workgroups", g, (long long)blocks);
+    unsigned blocks;
+    if (int rc = launch_blocks("lp_grid_tv", tv_grid_blocks(d, C, vec), 1, blocks)) return rc;
     if (p == 1) {
-      if (vec == 4) tv_launch<1, 4>(t, (unsigned)blocks, want_loss, want_grad, accumulate, stream);
-      else tv_launch<1, 1>(t, (unsigned)blocks, want_loss, want_grad, accumulate, stream);
+      if (vec == 4) tv_launch<1, 4>(t, blocks, want_loss, want_grad, accumulate, stream);
+      else tv_launch<1, 1>(t, blocks, want_loss, want_grad, accumulate, stream);
     } else {
-      if (vec == 4) tv_launch<2, 4>(t, (unsigned)blocks, want_loss, want_grad, accumulate, stream);
-      else tv_launch<2, 1>(t, (unsigned)blocks, want_loss, want_grad, accumulate, stream);
+      if (vec == 4) tv_launch<2, 4>(t, blocks, want_loss, want_grad, accumulate, stream);
+      else tv_launch<2, 1>(t, blocks, want_loss, want_grad, accumulate, stream);
     }
     const int rc = check_launch("grid_tv_sweep");
     if (rc) return rc;

@@ -6,6 +6,7 @@
 #include "../../include/lightplane_hip.h"
 #include "../../include/lightplane_hip_samples.h"
 #include "../../include/lightplane_hip_importance.h"
+#include "lp_launch.h"
 
 namespace lp {
 
@@ -13,6 +14,14 @@ namespace lp {
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // hipGetLastError() -> LP_OK or the positive hipError_t (message recorded).
 int check_launch(const char* what);
+// Workgroups of `per` items that cover `items` (workgroup_count, lp_launch.h): LP_OK and the count (0 for no item), or LP_EUNSUPPORTED
+// where a launch cannot have that many.  `what`: the entry point, for the message.
+inline int launch_blocks(const char* what, int64_t items, int64_t per, unsigned& blocks) {
+  int64_t n;
+  if (!workgroup_count(items, per, n)) return set_error(LP_EUNSUPPORTED, "%s: %lld workgroups, a launch has at most 2^31 - 1", what, (long long)n);
+  blocks = (unsigned)n;
+  return LP_OK;
+}
 
 // test hook (lp_renderer_backward_relu_dump, lp_api.hip): while non-NULL, the MFMA backwards launch their DUMP twins, which also
 // write the ReLU decisions of the recompute here.  Thread-local; NULL in every product call.

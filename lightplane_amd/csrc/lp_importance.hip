@@ -10,7 +10,6 @@
 //   3  ranks: every coarse and every new depth writes its slot of out[0 .. S')                        (include_coarse only)
 //   4  depths' / deltas' one lane per sample; points' as the ray's contiguous run of 3 S' floats
 // The bin edges are not kept: e_j = (d[j-1] + d[j]) / 2 is two LDS reads and an add where it is needed (twice per new depth).
-#include "lp_device.h"
 #include "lp_host.h"
 #include "lp_wave.h"
 
@@ -120,8 +119,7 @@ __global__ __launch_bounds__(64) void importance_fwd(ImpArgs a) {
     a.out_deltas[obase + i] = i > 0 ? v - out[i - 1] : (S_out > 1 ? out[1] - v : 1.0f);
   }
   Ray q;
-  q.ox = a.origins[3 * r + 0], q.oy = a.origins[3 * r + 1], q.oz = a.origins[3 * r + 2];
-  q.dx = a.directions[3 * r + 0], q.dy = a.directions[3 * r + 1], q.dz = a.directions[3 * r + 2];
+  load_ray_line(a.origins, a.directions, r, q);
   q.near_t = q.far_t = 0.0f;
   q.b = 0;
   float* pts = a.points + 3 * obase;
@@ -175,12 +173,14 @@ int importance_launch(const LpImportanceArgs& a, bool backward, hipStream_t stre
   s.g_points = a.grad_points, s.g_origins = a.grad_origins, s.g_directions = a.grad_directions;
   if (backward) {
     if (!s.g_origins && !s.g_directions) return LP_OK;
-    const int64_t blocks = (s.n_rays + IB_THREADS / 64 - 1) / (IB_THREADS / 64);
-    hipLaunchKernelGGL(importance_bwd, dim3((unsigned)blocks), dim3(IB_THREADS), 0, stream, s);
+    unsigned blocks;
+    if (int rc = launch_blocks("lp_importance_samples_backward", s.n_rays, IB_THREADS / 64, blocks)) return rc;
+    hipLaunchKernelGGL(importance_bwd, dim3(blocks), dim3(IB_THREADS), 0, stream, s);
     return check_launch("importance_bwd");
   }
   // at most 4 * (2049 + 2048 + 2048 + 4096) = 40 964 bytes: below the 64 KB a workgroup has without asking
   const size_t lds = sizeof(float) * (size_t)(2 * s.S + 1 + s.N + (s.merge ? s.S + s.N : 0));
+  // (one workgroup per ray: check_point_batch of lp_api.hip keeps n_rays * (S + N), hence n_rays, below 2^31)
   hipLaunchKernelGGL(importance_fwd, dim3((unsigned)s.n_rays), dim3(64), lds, stream, s);
   return check_launch("importance_fwd");
 }

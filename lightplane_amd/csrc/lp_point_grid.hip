@@ -18,6 +18,7 @@
 // No workspace; nothing but the caller's buffers is written.
 #include "lp_host.h"
 #include "lp_point_grad.h"
+#include "lp_rows.h"
 
 namespace lp {
 
@@ -180,23 +181,8 @@ struct PgNormArgs {
 __global__ void __launch_bounds__(256) point_normalize(const PgNormArgs s) {
   const int g = blockIdx.y;
   const int C = s.channels;
-  float* feature = s.data[g];
-  const float* weight = s.weight[g];
-  const int64_t n = s.n_rows[g] * C;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  if ((C & 3) == 0) {  // (a grid's first row is 16-byte aligned then: row_offset * C * 4 bytes behind an aligned base)
-    const int64_t n4 = n / 4;
-    const int c4 = C / 4;
-    float4* f4 = reinterpret_cast<float4*>(feature);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-      float4 v = f4[i];
-      const float d = fmaxf(weight[i / c4], 1e-5f);  // true division, as lp_splatter_normalize
-      v.x = v.x / d; v.y = v.y / d; v.z = v.z / d; v.w = v.w / d;
-      f4[i] = v;
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) feature[i] = feature[i] / fmaxf(weight[i / C], 1e-5f);
-  }
+  // (C % 4 == 0: a grid's first row is 16-byte aligned -- row_offset * C * 4 bytes behind an aligned base)
+  normalize_rows(s.data[g], s.weight[g], s.n_rows[g], C);
 }
 
 __global__ void __launch_bounds__(256) point_grad_points(const PgArgs s) {
@@ -217,23 +203,16 @@ __global__ void __launch_bounds__(256) point_grad_points(const PgArgs s) {
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
 
-static int pg_blocks(const char* what, int64_t threads, int per_block, unsigned& blocks) {
-  const int64_t n = (threads + per_block - 1) / per_block;
-  if (n >= ((int64_t)1 << 31)) return set_error(LP_EUNSUPPORTED, "%s: %lld workgroups are more than 2^31", what, (long long)n);
-  blocks = (unsigned)n;
-  return LP_OK;
-}
-
 int point_gather_launch(const LpPointGridArgs& a, hipStream_t stream) {
   PgArgs s;
   s.a = a;
   s.n_points = a.n_rays * a.n_pts;
   if (s.n_points == 0) return LP_OK;
   const int C = a.grid.channels;
-  const bool vec = (C & 3) == 0;
+  const bool vec = row_vec(C, {}) == 4;  // (no pointer to look at: lp_api.hip refuses under-aligned ones)
   s.lanes = vec ? C / 4 : 1;
   unsigned blocks;
-  if (int rc = pg_blocks("lp_point_gather", s.n_points * s.lanes, 256, blocks)) return rc;
+  if (int rc = launch_blocks("lp_point_gather", s.n_points * s.lanes, 256, blocks)) return rc;
   if (vec)
     hipLaunchKernelGGL(point_gather_vec, dim3(blocks), dim3(256), 0, stream, s);
   else
@@ -248,7 +227,7 @@ int point_splat_launch(const LpPointGridArgs& a, hipStream_t stream) {
   s.lanes = 0;
   if (s.n_points == 0) return LP_OK;
   unsigned blocks;
-  if (int rc = pg_blocks("lp_point_splat", s.n_points, 64, blocks)) return rc;
+  if (int rc = launch_blocks("lp_point_splat", s.n_points, 64, blocks)) return rc;
   const int C = a.grid.channels;
   if (C <= 16)
     hipLaunchKernelGGL(point_splat<4>, dim3(blocks), dim3(64), 0, stream, s);
@@ -271,7 +250,7 @@ int point_normalize_launch(const LpPointGridArgs& a, hipStream_t stream) {
     s.n_rows[g] = (int64_t)gd.B * gd.D * gd.H * gd.W;
     most = s.n_rows[g] > most ? s.n_rows[g] : most;
   }
-  const int64_t per_thread = (s.channels & 3) == 0 ? 4 : 1;
+  const int64_t per_thread = row_vec(s.channels, {});  // (normalize_rows decides by the channel count alone)
   int64_t blocks = (most * s.channels / per_thread + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks);  // (grid-stride loop)
   hipLaunchKernelGGL(point_normalize, dim3((unsigned)blocks, (unsigned)a.grid.n_grids), dim3(256), 0, stream, s);
@@ -285,7 +264,7 @@ int point_grad_points_launch(const LpPointGridArgs& a, hipStream_t stream) {
   s.lanes = 1;
   if (s.n_points == 0) return LP_OK;
   unsigned blocks;
-  if (int rc = pg_blocks("lp_point_grad_points", s.n_points, 256, blocks)) return rc;
+  if (int rc = launch_blocks("lp_point_grad_points", s.n_points, 256, blocks)) return rc;
   hipLaunchKernelGGL(point_grad_points, dim3(blocks), dim3(256), 0, stream, s);
   return check_launch("point_grad_points");
 }

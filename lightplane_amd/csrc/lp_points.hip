@@ -292,13 +292,12 @@ int points_forward_launch(const LpPointsArgs& a, hipStream_t stream) {
   const bool opacity_only = a.color_out == nullptr;
   s.maxw = widest(a, !opacity_only);
   const size_t lds = (size_t)(opacity_only ? 2 : 3) * s.maxw * SC_WAVE * sizeof(float);  // <= 96 KB (LP_MAX_WIDTH 128)
-  const int64_t blocks = (s.n_points + SC_WAVE - 1) / SC_WAVE;
-  if (blocks >= ((int64_t)1 << 31))
-    return set_error(LP_EUNSUPPORTED, "lp_points_forward: %lld points need %lld workgroups", (long long)s.n_points, (long long)blocks);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_points_forward", s.n_points, SC_WAVE, blocks)) return rc;
   const void* fn = opacity_only ? (const void*)points_fwd<true> : (const void*)points_fwd<false>;
   const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  const dim3 gr((unsigned)blocks), bl(SC_WAVE);
+  const dim3 gr(blocks), bl(SC_WAVE);
   if (opacity_only)
     hipLaunchKernelGGL((points_fwd<true>), gr, bl, lds, stream, s);
   else
@@ -367,12 +366,14 @@ int points_backward_launch(const LpPointsArgs& a, hipStream_t stream) {
   const bool lds_acc = a.grad_mlp_params && (stage_bytes + param_bytes <= 96 * 1024);
   s.ga.lds_param_accum = lds_acc ? 1 : 0;
   const size_t lds = stage_bytes + (lds_acc ? param_bytes : 0);
-  const int64_t n_tiles = (s.n_points + 63) / 64;
-  const int64_t tpb = (n_tiles + PT_BWD_BLOCKS - 1) / PT_BWD_BLOCKS;
-  if (tpb >= ((int64_t)1 << 31))
+  // n_tiles tiles of 64 points, dealt to at most PT_BWD_BLOCKS workgroups of tpb consecutive tiles (tpb is 32-bit like a workgroup count)
+  int64_t n_tiles, tpb;
+  workgroup_count(s.n_points, 64, n_tiles);
+  if (!workgroup_count(n_tiles, PT_BWD_BLOCKS, tpb))
     return set_error(LP_EUNSUPPORTED, "lp_points_backward: %lld points are more than 2^31 tiles per workgroup", (long long)s.n_points);
   s.tiles_per_block = (int32_t)tpb;
-  const unsigned blocks = (unsigned)((n_tiles + tpb - 1) / tpb);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_points_backward", n_tiles, tpb, blocks)) return rc;
 #define LP_LAUNCH_PT_BWD(CAP, ACC)                                                                          \
   do {                                                                                                      \
     hipError_t e = hipFuncSetAttribute((const void*)points_bwd<CAP, ACC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \

@@ -248,9 +248,9 @@ int rays_clip_launch(const LpRayClipArgs& a, float* near_out, float* far_out, ui
   s.W = a.scaffold ? a.scaffold_shape.W : 1;
   s.pad = a.pad;
   s.near_out = near_out, s.far_out = far_out, s.hit_out = hit_out;
-  const int64_t blocks = (a.rays.n_rays + RC_THREADS - 1) / RC_THREADS;
-  if (blocks >= ((int64_t)1 << 31)) return set_error(LP_EUNSUPPORTED, "lp_rays_clip: %lld rays need %lld workgroups", (long long)a.rays.n_rays, (long long)blocks);
-  hipLaunchKernelGGL(rays_clip, dim3((unsigned)blocks), dim3(RC_THREADS), 0, stream, s);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_rays_clip", a.rays.n_rays, RC_THREADS, blocks)) return rc;
+  hipLaunchKernelGGL(rays_clip, dim3(blocks), dim3(RC_THREADS), 0, stream, s);
   return check_launch("rays_clip");
 }
 

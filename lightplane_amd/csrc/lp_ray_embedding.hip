@@ -109,13 +109,13 @@ __global__ void __launch_bounds__(RE_THREADS) ray_embedding_bwd(const LpRayEmbed
   }
 }
 
-static unsigned re_blocks(const LpRayEmbedArgs& a) { return (unsigned)((a.n_rays + RE_THREADS - 1) / RE_THREADS); }
-
 int ray_embedding_forward_launch(const LpRayEmbedArgs& a, hipStream_t stream) {
   if (a.n_rays == 0) return LP_OK;
   const int D = 6 * a.n_harmonics + 3;
   const size_t lds = (size_t)(a.out_dim * D + a.out_dim) * sizeof(float);
-  hipLaunchKernelGGL(ray_embedding_fwd, dim3(re_blocks(a)), dim3(RE_THREADS), lds, stream, a);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_ray_embedding_forward", a.n_rays, RE_THREADS, blocks)) return rc;
+  hipLaunchKernelGGL(ray_embedding_fwd, dim3(blocks), dim3(RE_THREADS), lds, stream, a);
   return check_launch("ray_embedding_fwd");
 }
 
@@ -128,7 +128,9 @@ int ray_embedding_backward_launch(const LpRayEmbedArgs& a, hipStream_t stream) {
                      a.out_dim, lds);
   const hipError_t e = hipFuncSetAttribute((const void*)ray_embedding_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(ray_embedding_bwd, dim3(re_blocks(a)), dim3(RE_THREADS), lds, stream, a);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_ray_embedding_backward", a.n_rays, RE_THREADS, blocks)) return rc;
+  hipLaunchKernelGGL(ray_embedding_bwd, dim3(blocks), dim3(RE_THREADS), lds, stream, a);
   return check_launch("ray_embedding_bwd");
 }
 

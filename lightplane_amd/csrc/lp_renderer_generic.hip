@@ -357,7 +357,8 @@ int renderer_forward_generic(const LpRendererArgs& a, hipStream_t stream) {
   ga.relu_dump = nullptr;
   ga.dump_words = ga.dump_wps = 0;
   const size_t lds = (size_t)64 * ga.stage_ld * sizeof(float);  // <= 33 KB (LP_MAX_WIDTH 128): below the 64 KB default limit
-  const unsigned blocks = (unsigned)((a.rays.n_rays + 63) / 64);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_renderer_forward", a.rays.n_rays, 64, blocks)) return rc;
   if (blocks == 0) return LP_OK;
   if (total <= 256)
     hipLaunchKernelGGL(renderer_fwd_generic<256>, dim3(blocks), dim3(64), lds, stream, ga);
@@ -407,7 +408,8 @@ int renderer_backward_generic(const LpRendererArgs& a, hipStream_t stream) {
   const bool lds_acc = a.grad_mlp_params && (stage_bytes + param_bytes <= 96 * 1024);
   ga.lds_param_accum = lds_acc ? 1 : 0;
   const size_t lds = stage_bytes + (lds_acc ? param_bytes : 0);
-  const unsigned blocks = (unsigned)((a.rays.n_rays + 63) / 64);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_renderer_backward", a.rays.n_rays, 64, blocks)) return rc;
   if (blocks == 0) return LP_OK;
   if (total > 1024)
     return set_error(LP_EUNSUPPORTED, "generic renderer: sum of layer widths %d exceeds 1024", total);
@@ -451,7 +453,8 @@ int renderer_corner_rows_launch(const LpRendererArgs& a, int64_t* rows, hipStrea
     const LpGrid& gd = a.grid.grids[g];
     k_tot += (gd.D > 1 && gd.H > 1 && gd.W > 1) ? 8 : 4;
   }
-  const unsigned blocks = (unsigned)((a.rays.n_rays + 63) / 64);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_renderer_corner_rows", a.rays.n_rays, 64, blocks)) return rc;
   if (blocks == 0) return LP_OK;
   hipLaunchKernelGGL(renderer_corner_rows, dim3(blocks), dim3(64), 0, stream, a, rows, k_tot);
   return check_launch("renderer_corner_rows");

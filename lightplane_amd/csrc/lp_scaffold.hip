@@ -45,12 +45,8 @@ __global__ void __launch_bounds__(SC_WAVE) scaffold_lattice(const ScArgs s) {
   const bool valid = p < s.n_points;
   const int64_t q = valid ? p : s.n_points - 1;  // (a lane past the end recomputes the last point and stores nothing)
   const int W = a.shape.W, H = a.shape.H, D = a.shape.D;
-  const int ix = (int)(q % W);
-  const int64_t r1 = q / W;
-  const int iy = (int)(r1 % H);
-  const int64_t r2 = r1 / H;
-  const int iz = (int)(r2 % D);
-  const int b = (int)(r2 / D);
+  const LatticePoint at = lattice_point<int64_t>(q, W, H, D);
+  const int ix = at.x, iy = at.y, iz = at.z, b = at.b;
   const float x = lin01(ix, W) * 2.0f - 1.0f;
   const float y = lin01(iy, H) * 2.0f - 1.0f;
   const float z = lin01(iz, D) * 2.0f - 1.0f;
@@ -122,9 +118,9 @@ int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool o
     for (int l = 0; l <= m->n_layers && m->n_layers > 0; ++l) maxw = m->dims[l] > maxw ? m->dims[l] : maxw;
   s.maxw = maxw;
   const size_t lds = (size_t)2 * maxw * SC_WAVE * sizeof(float);  // <= 64 KB (LP_MAX_WIDTH 128): within the default limit
-  const int64_t blocks = (s.n_points + SC_WAVE - 1) / SC_WAVE;
-  if (blocks >= ((int64_t)1 << 31)) return set_error(LP_EUNSUPPORTED, "scaffold: %lld lattice points need %lld workgroups", (long long)s.n_points, (long long)blocks);
-  const dim3 gr((unsigned)blocks), bl(SC_WAVE);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_scaffold", s.n_points, SC_WAVE, blocks)) return rc;
+  const dim3 gr(blocks), bl(SC_WAVE);
   if (!occupancy) {
     s.out = out;
     hipLaunchKernelGGL((scaffold_lattice<SC_RAW>), gr, bl, lds, stream, s);
@@ -141,8 +137,9 @@ int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool o
   hipLaunchKernelGGL((scaffold_lattice<SC_OCC_BYTE>), gr, bl, lds, stream, s);
   int rc = check_launch("scaffold_lattice");
   if (rc) return rc;
-  const int64_t dblocks = (s.n_points + SC_DIL_THREADS - 1) / SC_DIL_THREADS;
-  const dim3 dgr((unsigned)dblocks), dbl(SC_DIL_THREADS);
+  unsigned dblocks;
+  if ((rc = launch_blocks("lp_scaffold", s.n_points, SC_DIL_THREADS, dblocks))) return rc;
+  const dim3 dgr(dblocks), dbl(SC_DIL_THREADS);
   const int W = a.shape.W, H = a.shape.H, D = a.shape.D;
   hipLaunchKernelGGL((scaffold_dilate<false>), dgr, dbl, 0, stream, ws, (void*)ob, s.n_points, W, (int64_t)1, a.dilate < W ? a.dilate : W);
   if ((rc = check_launch("scaffold_dilate (W)"))) return rc;

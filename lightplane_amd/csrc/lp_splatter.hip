@@ -13,6 +13,7 @@
 
 #include "lp_device.h"
 #include "lp_host.h"
+#include "lp_rows.h"
 #include "lp_splat_walk.h"
 
 namespace lp {
@@ -397,23 +398,7 @@ splat_bwd_walk_kernel(const LpSplatterArgs a, int n_seg) {
 
 __global__ void __launch_bounds__(256) splat_normalize_kernel(float* feature, const float* weight,
                                                               int64_t n_rows, int C) {
-  const int64_t n = n_rows * C;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  if ((C & 3) == 0) {
-    const int64_t n4 = n / 4;
-    const int c4 = C / 4;
-    float4* f4 = reinterpret_cast<float4*>(feature);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-      float4 v = f4[i];
-      // true division (matches torch's feat / clamp(weight)) -- the pass is HBM bound anyway
-      const float d = fmaxf(weight[i / c4], 1e-5f);
-      v.x = v.x / d; v.y = v.y / d; v.z = v.z / d; v.w = v.w / d;
-      f4[i] = v;
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-      feature[i] = feature[i] / fmaxf(weight[i / C], 1e-5f);
-  }
+  normalize_rows(feature, weight, n_rows, C);
 }
 
 __global__ void __launch_bounds__(256) hash_randn_kernel(const int32_t* x1, const int32_t* x2, float* out,
@@ -430,8 +415,8 @@ __global__ void __launch_bounds__(256) hash_randn_kernel(const int32_t* x1, cons
     int lpr = 1;                                                                               \
     while (lpr < C && lpr < 64) lpr <<= 1;                                                     \
     const int cpl = (C + lpr - 1) / lpr;                                                       \
-    const int64_t threads = a.rays.n_rays * lpr;                                               \
-    const unsigned blocks = (unsigned)((threads + 255) / 256);                                 \
+    unsigned blocks;                                                                           \
+    if (int rc = launch_blocks("lp_splatter", a.rays.n_rays * lpr, 256, blocks)) return rc;       \
     if (blocks == 0) return LP_OK;                                                             \
     if (cpl > 2) return set_error(LP_EUNSUPPORTED, "splatter: %d channels > 128", C);          \
     switch (lpr) {                                                                             \
@@ -495,7 +480,8 @@ int splatter_forward_launch(const LpSplatterArgs& a, hipStream_t stream) {
       if (a.rays.n_rays == 0) return LP_OK;
       int rays_pw = 32;  // (rays per wave: fewer while the batch leaves workgroup slots idle -- 4 workgroups per CU)
       while (rays_pw > 1 && (a.rays.n_rays + 4 * rays_pw - 1) / (4 * rays_pw) < 1024) rays_pw >>= 1;
-      const unsigned blocks = (unsigned)((a.rays.n_rays + 4 * rays_pw - 1) / (4 * rays_pw));
+      unsigned blocks;
+      if (int rc = launch_blocks("lp_splatter_forward", a.rays.n_rays, 4 * rays_pw, blocks)) return rc;
       if (all_voxel && Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64, true>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
       else if (all_voxel && Cw == 32) hipLaunchKernelGGL((splat_fwd_ray_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
       else if (Cw == 64) hipLaunchKernelGGL((splat_fwd_ray_kernel<64>), dim3(blocks), dim3(256), 0, stream, a, rays_pw);
@@ -508,10 +494,11 @@ int splatter_forward_launch(const LpSplatterArgs& a, hipStream_t stream) {
     // (profiles/r04_splat_fwd_rpw32_ab.txt).  (64 channels -- the reference's own speed benchmark splats into [1,160,160,160,64] --:
     // 16 rays per wave, four channels per lane.)
     const int rpw = Cw == 64 ? 16 : 32;
-    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * rpw - 1) / (4 * rpw));
+    unsigned ray_blocks, blocks;
+    if (int rc = launch_blocks("lp_splatter_forward", a.rays.n_rays, 4 * rpw, ray_blocks)) return rc;
     if (ray_blocks == 0) return LP_OK;
     const int n_seg = splat_forward_segments(a);
-    const unsigned blocks = ray_blocks * (unsigned)n_seg;
+    if (int rc = launch_blocks("lp_splatter_forward", (int64_t)ray_blocks * n_seg, 1, blocks)) return rc;
     const int grp = splat_forward_group(a, ray_blocks);
     if (all_voxel && Cw == 64) hipLaunchKernelGGL((splat_fwd_walk_kernel<64, 16, true>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
     else if (all_voxel && Cw == 32) hipLaunchKernelGGL((splat_fwd_walk_kernel<32, 32, true>), dim3(blocks), dim3(256), 0, stream, a, n_seg, grp);
@@ -532,7 +519,8 @@ int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream) {
   if ((Cw == 16 || Cw == 32 || Cw == 64) && a.out.n_grids > 0 && a.out.n_rows < ((int64_t)1 << 31)) {
     // 8 rays per wave (round 4): cfg 3 backward 2.32 -> 2.01 ms -- 146 instead of 210 registers (C = 32), three waves per SIMD
     // instead of two, i.e. 1.5x the gathers in flight of a latency-bound walk
-    const unsigned ray_blocks = (unsigned)((a.rays.n_rays + 4 * 8 - 1) / (4 * 8));
+    unsigned ray_blocks, blocks;
+    if (int rc = launch_blocks("lp_splatter_backward", a.rays.n_rays, 4 * 8, ray_blocks)) return rc;
     if (ray_blocks == 0) return LP_OK;
     int n_seg = splat_segments(a, (ray_blocks + 1) / 2);
     // Mid-sized batches: fill whole rounds of resident waves.  cfg 3 = 8 192 waves of 8 rays on 3 072 wave slots (C = 32: three waves
@@ -580,7 +568,7 @@ int splatter_backward_launch(const LpSplatterArgs& a, hipStream_t stream) {
       const hipError_t e = hipMemsetAsync(a.grad_encoding, 0, (size_t)a.rays.n_rays * Cw * sizeof(float), stream);
       if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync(grad_encoding): %s", hipGetErrorString(e));
     }
-    const unsigned blocks = ray_blocks * (unsigned)n_seg;
+    if (int rc = launch_blocks("lp_splatter_backward", (int64_t)ray_blocks * n_seg, 1, blocks)) return rc;
     // batches of 8 rays; batches of 4 at three waves/SIMD measured the same (cfg 3)
     if (Cw == 16) hipLaunchKernelGGL((splat_bwd_walk_kernel<16, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
     else if (Cw == 32) hipLaunchKernelGGL((splat_bwd_walk_kernel<32, 8, 8>), dim3(blocks), dim3(256), 0, stream, a, n_seg);
@@ -606,8 +594,9 @@ int splatter_normalize_launch(float* feature, const float* weight, int64_t n_row
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream) {
   if (n == 0) return LP_OK;
-  hipLaunchKernelGGL(hash_randn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x1, x2, out, n,
-                     seed);
+  unsigned blocks;
+  if (int rc = launch_blocks("lp_hash_randn", n, 256, blocks)) return rc;
+  hipLaunchKernelGGL(hash_randn_kernel, dim3(blocks), dim3(256), 0, stream, x1, x2, out, n, seed);
   return check_launch("hash_randn_kernel");
 }
 

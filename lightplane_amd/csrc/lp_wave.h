@@ -1,6 +1,6 @@
 // lp_wave.h -- sums and scans over the 64 lanes of a wavefront, shared by the one-wavefront-per-ray kernels (lp_composite.hip,
-// lp_importance.hip).  The scans add the shifted copy under a lane mask (an exclusive value is the inclusive one shifted by a lane,
-// never `inclusive - x`: no cancellation).
+// lp_importance.hip) and the mesh's counting passes (lp_mesh.hip).  The float scans add the shifted copy under a lane mask (an
+// exclusive value is the inclusive one shifted by a lane, never `inclusive - x`: no cancellation).
 #pragma once
 
 #include "lp_device.h"
@@ -13,10 +13,11 @@ LP_DEV float wave_sum(float x) {
   return x;
 }
 // inclusive prefix sum over the wave, lane 0 first
-LP_DEV float wave_scan(float x, int lane) {
+template <typename T>
+LP_DEV T wave_scan(T x, int lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    const float y = __shfl_up(x, d, 64);
+    const T y = __shfl_up(x, d, 64);
     if (lane >= d) x += y;
   }
   return x;

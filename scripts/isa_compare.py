@@ -61,7 +61,7 @@ def kernels(path):
 
 def demangle(names):
     txt = subprocess.run(["c++filt"], input="\n".join(names), stdout=subprocess.PIPE, text=True).stdout.splitlines()
-    return {n: re.sub(r"\(.*", "", d).replace("void lp::", "") for n, d in zip(names, txt)}
+    return {n: re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void lp::", "") for n, d in zip(names, txt)}
 
 
 def main():
