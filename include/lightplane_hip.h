@@ -350,7 +350,9 @@ const char* lp_last_error(void);
  * pin those answers as "the first selector that does not exist", so the next addition took the one after.
  * (18 and 20 answer for the two structs of lightplane_hip_samples.h -- sample placement and compositing of the march as entry
  * points of their own, declared in that header so that the tables of this one stay as they are; 17, 19 and 21 return -1.
- * 22 answers for LpImportanceArgs of lightplane_hip_importance.h, importance resampling of those samples; 23 returns -1.) */
+ * 22 answers for LpImportanceArgs of lightplane_hip_importance.h, importance resampling of those samples; 23 returns -1.
+ * 24 and 26 answer for LpDistortionArgs and LpInterlevelArgs of lightplane_hip_losses.h, two losses on those samples; 25 and 27
+ * return -1.) */
 int lp_abi_sizeof(int which);
 
 /* Number of ray segments the backward of these arguments can be split into (see LpRendererArgs.seg_prefix): 1 when the

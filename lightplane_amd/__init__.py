@@ -35,6 +35,7 @@ from .point_grid import sample_grid_at_points, splat_points  # noqa: E402
 from .mesh import extract_mesh, marching_cubes, mesh_workspace_bytes  # noqa: E402
 from .compositing import RaySamples, composite_samples, ray_samples  # noqa: E402
 from .importance import importance_samples  # noqa: E402
+from .ray_losses import distortion_loss, interlevel_loss  # noqa: E402
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -63,6 +64,7 @@ __all__ = [
     "marching_cubes", "extract_mesh", "mesh_workspace_bytes",
     "ray_samples", "composite_samples", "RaySamples",
     "importance_samples",
+    "distortion_loss", "interlevel_loss",
 ]
 
 _NOT_PROVIDED = {

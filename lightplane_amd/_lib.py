@@ -172,6 +172,22 @@ class LpImportanceArgs(C.Structure):  # include/lightplane_hip_importance.h
     ]
 
 
+class LpDistortionArgs(C.Structure):  # include/lightplane_hip_losses.h
+    _fields_ = [
+        ("weights", C.c_void_p), ("depths", C.c_void_p), ("deltas", C.c_void_p), ("grad_loss", C.c_void_p), ("loss", C.c_void_p),
+        ("grad_weights", C.c_void_p), ("grad_depths", C.c_void_p), ("grad_deltas", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class LpInterlevelArgs(C.Structure):  # include/lightplane_hip_losses.h
+    _fields_ = [
+        ("weights", C.c_void_p), ("depths", C.c_void_p), ("proposal_weights", C.c_void_p), ("proposal_depths", C.c_void_p),
+        ("grad_loss", C.c_void_p), ("loss", C.c_void_p), ("grad_proposal_weights", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("n_proposal", C.c_int32), ("eps", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -200,6 +216,11 @@ SAMPLES_EXPORTS = ("lp_ray_samples_forward", "lp_ray_samples_backward", "lp_comp
 IMPORTANCE_EXPORTS = ("lp_importance_samples_forward", "lp_importance_samples_backward")
 #: the most coarse samples and the most new samples per ray (LP_IMPORTANCE_MAX of that header: a ray's working set stays in LDS)
 LP_IMPORTANCE_MAX = 2048
+
+#: every symbol include/lightplane_hip_losses.h declares (a header and a table of their own as well)
+LOSSES_EXPORTS = ("lp_distortion_forward", "lp_distortion_backward", "lp_interlevel_forward", "lp_interlevel_backward")
+#: the most samples (and proposal samples) per ray of the two losses (LP_RAY_LOSS_MAX of that header: a ray's working set stays in LDS)
+LP_RAY_LOSS_MAX = 2048
 
 
 def _signatures():
@@ -249,6 +270,9 @@ def _signatures():
         (SAMPLES_EXPORTS[2:], C.c_int, (P(LpCompositeArgs), vp)),
         # importance resampling of a ray's samples (include/lightplane_hip_importance.h): args, stream
         (IMPORTANCE_EXPORTS, C.c_int, (P(LpImportanceArgs), vp)),
+        # distortion and interlevel loss of a ray's samples (include/lightplane_hip_losses.h): args, stream
+        (LOSSES_EXPORTS[:2], C.c_int, (P(LpDistortionArgs), vp)),
+        (LOSSES_EXPORTS[2:], C.c_int, (P(LpInterlevelArgs), vp)),
     )
 
 
@@ -279,7 +303,8 @@ def lib() -> C.CDLL:
                       (7, LpRayEmbedArgs), (8, LpScaffoldArgs), (10, LpPointsArgs), (12, LpRayClipArgs),
                       (14, LpPointGridArgs), (16, LpMeshArgs),  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
                       (18, LpRaySamplesArgs), (20, LpCompositeArgs),  # (nor 17, 19 and 21: lightplane_hip_samples.h)
-                      (22, LpImportanceArgs)):  # (nor 23: lightplane_hip_importance.h)
+                      (22, LpImportanceArgs),  # (nor 23: lightplane_hip_importance.h)
+                      (24, LpDistortionArgs), (26, LpInterlevelArgs)):  # (nor 25 and 27: lightplane_hip_losses.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

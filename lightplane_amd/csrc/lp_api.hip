@@ -768,6 +768,59 @@ static int check_importance(const LpImportanceArgs* args, bool backward) {
   return LP_OK;
 }
 
+// everything lp_distortion_forward / _backward check.  Messages begin with the field.
+static int check_distortion(const LpDistortionArgs* args, bool backward) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, grad_loss);
+  LP_ALIGNED(*args, loss);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_depths);
+  LP_ALIGNED(*args, grad_deltas);
+  if (args->n_samples < 1) return set_error(LP_EINVAL, "n_samples %d < 1", args->n_samples);
+  if (args->n_samples > LP_RAY_LOSS_MAX) return set_error(LP_EUNSUPPORTED, "n_samples %d > %d", args->n_samples, LP_RAY_LOSS_MAX);
+  if ((rc = check_point_batch(nullptr, args->n_rays, args->n_samples, true))) return rc;
+  if (args->n_rays == 0) return LP_OK;
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"weights", args->weights, true}, {"depths", args->depths, true}, {"deltas", args->deltas, true}, {"loss", args->loss, !backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
+// everything lp_interlevel_forward / _backward check.  Messages begin with the field.
+static int check_interlevel(const LpInterlevelArgs* args, bool backward) {
+  if (!args) return set_error(LP_ENULL, "args is NULL");
+  int rc;
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, proposal_weights);
+  LP_ALIGNED(*args, proposal_depths);
+  LP_ALIGNED(*args, grad_loss);
+  LP_ALIGNED(*args, loss);
+  LP_ALIGNED(*args, grad_proposal_weights);
+  if (args->n_samples < 2) return set_error(LP_EINVAL, "n_samples %d < 2", args->n_samples);
+  if (args->n_proposal < 2) return set_error(LP_EINVAL, "n_proposal %d < 2", args->n_proposal);
+  if (!std::isfinite(args->eps) || !(args->eps > 0.0f)) return set_error(LP_EINVAL, "eps %g has to be finite and > 0", (double)args->eps);
+  if (args->n_samples > LP_RAY_LOSS_MAX) return set_error(LP_EUNSUPPORTED, "n_samples %d > %d", args->n_samples, LP_RAY_LOSS_MAX);
+  if (args->n_proposal > LP_RAY_LOSS_MAX) return set_error(LP_EUNSUPPORTED, "n_proposal %d > %d", args->n_proposal, LP_RAY_LOSS_MAX);
+  if ((rc = check_point_batch(nullptr, args->n_rays, std::max(args->n_samples, args->n_proposal), true))) return rc;
+  if (args->n_rays == 0) return LP_OK;
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"weights", args->weights, true},
+      {"depths", args->depths, true},
+      {"proposal_weights", args->proposal_weights, true},
+      {"proposal_depths", args->proposal_depths, true},
+      {"loss", args->loss, !backward},
+      {"grad_proposal_weights", args->grad_proposal_weights, backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -820,6 +873,8 @@ int lp_abi_sizeof(int which) {
     case 18: return (int)sizeof(LpRaySamplesArgs);  // (and 17; this one and the next: lightplane_hip_samples.h)
     case 20: return (int)sizeof(LpCompositeArgs);  // (and 19)
     case 22: return (int)sizeof(LpImportanceArgs);  // (and 21: lightplane_hip_importance.h)
+    case 24: return (int)sizeof(LpDistortionArgs);  // (and 23; this one and the next: lightplane_hip_losses.h)
+    case 26: return (int)sizeof(LpInterlevelArgs);  // (and 25)
     default: return -1;
   }
 }
@@ -1231,6 +1286,30 @@ int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {
   const int rc = check_importance(args, true);
   if (rc || args->n_rays == 0) return rc;
   return importance_launch(*args, true, (hipStream_t)stream);
+}
+
+int lp_distortion_forward(const LpDistortionArgs* args, void* stream) {
+  const int rc = check_distortion(args, false);
+  if (rc || args->n_rays == 0) return rc;
+  return distortion_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_distortion_backward(const LpDistortionArgs* args, void* stream) {
+  const int rc = check_distortion(args, true);
+  if (rc || args->n_rays == 0) return rc;
+  return distortion_launch(*args, true, (hipStream_t)stream);
+}
+
+int lp_interlevel_forward(const LpInterlevelArgs* args, void* stream) {
+  const int rc = check_interlevel(args, false);
+  if (rc || args->n_rays == 0) return rc;
+  return interlevel_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_interlevel_backward(const LpInterlevelArgs* args, void* stream) {
+  const int rc = check_interlevel(args, true);
+  if (rc || args->n_rays == 0) return rc;
+  return interlevel_launch(*args, true, (hipStream_t)stream);
 }
 
 int lp_rays_clip(const LpRayClipArgs* args, float* near_out, float* far_out, uint8_t* hit_out, void* stream) {

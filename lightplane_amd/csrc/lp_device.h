@@ -101,6 +101,14 @@ LP_DEV float sample_delta(int i, const LpMarch& m, float near_t, float far_t, fl
   return depth_i - sample_depth(i - 1, m, near_t, far_t);
 }
 
+// edge j of the S cells around a ray's depths d[0 .. S) (the histogram importance resampling and the interlevel loss read the
+// compositing weights as): the ends of the ray's span, midpoints in between
+LP_DEV float bin_edge(const float* d, int j, int S) {
+  if (j <= 0) return d[0];
+  if (j >= S) return d[S - 1];
+  return 0.5f * (d[j - 1] + d[j]);
+}
+
 // -log T checkpoints: index of the checkpoint taken right after sample i, or -1.
 LP_DEV int ckpt_index(int i, const LpMarch& m) {
   if (i < m.num_samples) {

@@ -6,6 +6,7 @@
 #include "../../include/lightplane_hip.h"
 #include "../../include/lightplane_hip_samples.h"
 #include "../../include/lightplane_hip_importance.h"
+#include "../../include/lightplane_hip_losses.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -160,6 +161,9 @@ int ray_samples_launch(const LpRaySamplesArgs& a, bool backward, hipStream_t str
 int composite_launch(const LpCompositeArgs& a, bool backward, hipStream_t stream);
 // importance resampling of a ray's samples from its compositing weights: lp_importance.hip (`a` checked by lp_api.hip; n_rays > 0)
 int importance_launch(const LpImportanceArgs& a, bool backward, hipStream_t stream);
+// distortion and interlevel loss of a ray's samples: lp_ray_losses.hip (`a` checked by lp_api.hip; n_rays > 0)
+int distortion_launch(const LpDistortionArgs& a, bool backward, hipStream_t stream);
+int interlevel_launch(const LpInterlevelArgs& a, bool backward, hipStream_t stream);
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -30,13 +30,6 @@ struct ImpArgs {
   float *g_origins, *g_directions;
 };
 
-// edge j of the S bins over the coarse depths d[0 .. S): the ends of the ray's span, midpoints in between
-LP_DEV float bin_edge(const float* d, int j, int S) {
-  if (j <= 0) return d[0];
-  if (j >= S) return d[S - 1];
-  return 0.5f * (d[j - 1] + d[j]);
-}
-
 // the number of entries of the non-decreasing v[0 .. n) that are < x (STRICT) or <= x
 template <bool STRICT>
 LP_DEV int count_below(const float* v, int n, float x) {
