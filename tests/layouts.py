@@ -62,6 +62,8 @@ class Layout:
     ``view`` maps a base tensor (on any device) to the view with the values' shape; ``covered()`` is the boolean mask of the base's
     elements the view covers."""
 
+    identity = False  # (True: the values in a fresh dense tensor of their own -- base and view are the same tensor)
+
     def __init__(self, values, base_shape, view, seed=0):
         gen = torch.Generator().manual_seed(1234 + seed)
         self.view = view
@@ -106,7 +108,23 @@ def strided_layout(values, kind, seed=0):
     return Layout(values, (shape[-1],) + shape[:-1], lambda b: b.permute(*perm), seed)
 
 
+def identity_layout(values):
+    """The values in a fresh dense tensor of their own: what the other GPU tests hand over."""
+    lay = Layout(values, tuple(values.shape), lambda b: b)
+    lay.identity = True
+    return lay
+
+
 def make_layout(values, variant, kind="rows", seed=0):
+    """``kind`` picks the strided view (``strided_layout``) and, besides: "as_is" -- an input the front-end hands to the library as it is
+    and refuses in any other layout: fresh in EVERY variant (the refusals have a test of their own); "offset_only" -- an input the
+    front-end copies when it is under-aligned but refuses when it is not dense: fresh in the strided variant.  An integer input
+    (``ray_grid_idx``) arrives as int32 at the element offset -- int32, so that the front-end's dtype conversion does not realign it by
+    accident -- and as every other element of an int64 tensor."""
+    if not values.dtype.is_floating_point:
+        values = values.to(torch.int64 if variant == "strided" else torch.int32)
+    if kind == "as_is" or (kind == "offset_only" and variant == "strided"):
+        return identity_layout(values)
     if variant == "off4":
         return offset_layout(values, 1, seed)
     if variant == "off8":

@@ -7,7 +7,11 @@
   buffer is copied; the copy of a grid warns once per process.
 * Mutation proof: with ``lib()`` replaced by a recorder, every pointer the wrappers hand over for inputs at a 4-byte aligned base is
   16-byte aligned, and with ``_lib.aligned`` replaced by the identity every one of those call sites hands over the under-aligned
-  pointer -- the helper alone stands between such an input and the kernels, and a dropped call is noticed.
+  pointer -- the helper alone stands between such an input and the kernels, and a dropped call is noticed.  Four drives: the Renderer
+  and the Splatter, the MLP-Splatter and the ray embedding, the modular march (ray_samples, composite_samples, importance_samples, both
+  ray losses) and the point ops (gather, splat, ``lightplane_eval_mlp``, the ray clip).  Three kinds of pointer: the wrappers' own
+  buffers (``_OWN`` / ``_OWN_BY_ENTRY``: always aligned), the caller's inputs (aligned by the helper, the caller's own pointer without
+  it) and ``AS_IS`` -- the few inputs a front-end hands over uncopied on purpose, the caller's pointer in both proofs.
 """
 import contextlib
 import ctypes
@@ -96,8 +100,9 @@ ENTRY_POINTS = _entry_points()
 def test_the_walk_finds_every_pointer_of_the_argument_blocks():
     """The field list comes from the struct definitions: as many slots as the header declares pointers (a slot the walk missed would be a
     slot the alignment test never shifts)."""
-    got = {st.__name__: [p for p, _, _ in pointer_fields(st())] for st in (_lib.LpRays, _lib.LpGridList, _lib.LpRendererArgs,
-                                                                         _lib.LpSplatterArgs, _lib.LpRayEmbedArgs)}
+    got = {st.__name__: [p for p, _, _ in pointer_fields(st())] for st in (
+        _lib.LpRays, _lib.LpGridList, _lib.LpRendererArgs, _lib.LpSplatterArgs, _lib.LpRayEmbedArgs, _lib.LpPointsArgs, _lib.LpPointGridArgs,
+        _lib.LpRayClipArgs, _lib.LpRaySamplesArgs, _lib.LpCompositeArgs, _lib.LpImportanceArgs, _lib.LpDistortionArgs, _lib.LpInterlevelArgs)}
     assert got["LpRays"] == ["directions", "origins", "grid_idx", "near_t", "far_t", "encoding"]
     assert len(got["LpGridList"]) == 1 + _lib.LP_MAX_GRIDS
     # LpRendererArgs: rays 6, two grid-lists 2 x 9, scaffold + scaffold_shape.data, mlp_params, 3 outputs, ckpt, 3 upstream grads,
@@ -106,6 +111,25 @@ def test_the_walk_finds_every_pointer_of_the_argument_blocks():
     assert len(got["LpSplatterArgs"]) == 6 + 18 + 2 + 1 + 5 + 8
     assert len(got["LpRayEmbedArgs"]) == 7
     assert "grid.grids[7].data" in got["LpRendererArgs"] and "grad_color_grid_list[7]" in got["LpRendererArgs"]
+    # LpPointsArgs (lightplane_hip.h): two grid-lists 2 x 9, mlp_params, points + grid_idx + encoding, scaffold + scaffold_shape.data,
+    # 2 outputs + 2 upstream grads, 2 flat grid gradients, 2 x 8 list entries, grad_mlp_params + grad_encoding + grad_points
+    assert len(got["LpPointsArgs"]) == 18 + 1 + 3 + 2 + 4 + 2 + 16 + 3
+    # LpPointGridArgs: grid-list 9, row_weight[8], points + grid_idx, vectors + out_features + grad_points
+    assert len(got["LpPointGridArgs"]) == 9 + 8 + 2 + 3
+    # LpRayClipArgs: rays 6, scaffold + scaffold_shape.data (near_out / far_out / hit_out are arguments of lp_rays_clip, not fields)
+    assert len(got["LpRayClipArgs"]) == 6 + 2
+    # lightplane_hip_samples.h -- LpRaySamplesArgs: rays 6, 3 results, 3 upstream grads, 4 gradients; LpCompositeArgs: 4 inputs,
+    # 4 results, 4 upstream grads, 4 gradients
+    assert len(got["LpRaySamplesArgs"]) == 6 + 3 + 3 + 4
+    assert len(got["LpCompositeArgs"]) == 4 + 4 + 4 + 4
+    # lightplane_hip_importance.h -- 5 inputs, 3 results, grad_points, 2 gradients
+    assert len(got["LpImportanceArgs"]) == 5 + 3 + 1 + 2
+    # lightplane_hip_losses.h -- LpDistortionArgs: 3 inputs, grad_loss + loss, 3 gradients; LpInterlevelArgs: 4 inputs, grad_loss +
+    # loss, 1 gradient
+    assert len(got["LpDistortionArgs"]) == 3 + 2 + 3
+    assert len(got["LpInterlevelArgs"]) == 4 + 2 + 1
+    assert "row_weight[7]" in got["LpPointGridArgs"] and "color_grid.grids[7].data" in got["LpPointsArgs"]
+    assert "rays.near_t" in got["LpRayClipArgs"] and "rays.far_t" in got["LpRaySamplesArgs"]
     for paths in got.values():
         assert len(set(paths)) == len(paths)
 
@@ -238,6 +262,8 @@ class _Recorder:
                             out.append(((name, path), p))
             if name == "lp_splatter_normalize":
                 out += [((name, "feature"), args[0]), ((name, "weight"), args[1])]
+            if name == "lp_rays_clip":  # (args, near_out, far_out, hit_out, stream)
+                out += [((name, field), p) for field, p in zip(("near_out", "far_out", "hit_out"), args[1:4])]
         return out
 
     def pointers(self):
@@ -274,13 +300,58 @@ def _off4_rays(rays):
 #: Every OTHER non-NULL pointer of a recorded call is a caller's tensor.
 _OWN = re.compile(r"^(ray_length|neg_log_t|feature|neg_log_t_ckpt|alpha|seg_prefix|out\.data|out_feature|out_weight|weight|out"
                   r"|grad_(grid|color_grid|mlp_params|encoding|input_grid|weight|bias)|grad_(grid|color_grid|input_grid)_list\[\d\])$")
+_GRID_FIELDS = r"grid\.data|grid\.grids\[\d\]\.data"
 _OWN_BY_ENTRY = {"lp_ray_embedding_forward": ("out",), "lp_ray_embedding_backward": ("grad_weight", "grad_bias"),
-                 "lp_splatter_normalize": ("feature", "weight")}
+                 "lp_splatter_normalize": ("feature", "weight"),
+                 # the modular march (compositing.py, importance.py, ray_losses.py): results; gradients; of the saved tensors the
+                 # importance backward's ``out_depths`` is a result of the forward (every other saved tensor is an input's aligned copy
+                 # with the helper and the caller's tensor without it: an input)
+                 "lp_ray_samples_forward": ("points", "depths", "deltas"),
+                 "lp_ray_samples_backward": ("grad_origins", "grad_directions", "grad_near", "grad_far"),
+                 "lp_composite_forward": ("ray_length", "neg_log_t", "feature", "weights"),
+                 "lp_composite_backward": ("grad_opacity", "grad_features", "grad_depths", "grad_deltas"),
+                 "lp_importance_samples_forward": ("out_points", "out_depths", "out_deltas"),
+                 "lp_importance_samples_backward": ("out_depths", "grad_origins", "grad_directions"),
+                 "lp_distortion_forward": ("loss",), "lp_distortion_backward": ("grad_weights", "grad_depths", "grad_deltas"),
+                 "lp_interlevel_forward": ("loss",), "lp_interlevel_backward": ("grad_proposal_weights",),
+                 # gather / splat at points (point_grid.py): the gather reads a caller's grid-list (the grids; a splat's upstream grids)
+                 # and writes features, dividing by the splat's saved ``row_weight``; the splat and the normalisation write a grid-list
+                 # of the wrapper's own (the result; the gather's grid gradient)
+                 "lp_point_gather": re.compile(r"out_features|row_weight\[\d\]"),
+                 "lp_point_splat": re.compile(_GRID_FIELDS + r"|row_weight\[\d\]"),
+                 "lp_point_normalize": re.compile(_GRID_FIELDS + r"|row_weight\[\d\]"),
+                 "lp_point_grad_points": ("grad_points",),
+                 # the decoder at points (points.py)
+                 "lp_points_forward": ("opacity_out", "color_out"),
+                 "lp_points_backward": re.compile(r"grad_(grid|color_grid|mlp_params|encoding|points)|grad_(grid|color_grid)_list\[\d\]"),
+                 # the ray clip (ray_clip.py): the three results, unless they are the caller's ``out=`` in place (AS_IS)
+                 "lp_rays_clip": ("near_out", "far_out", "hit_out")}
+
+#: (entry point, fields) whose pointer is the CALLER'S in both proofs, helper or not, and why.  The drives name the pointers they expect
+#: there; a pointer at one of these fields that is not one of those is classified like any other.
+AS_IS = {
+    ("lp_points_forward", "lp_points_backward"): (
+        re.compile(r"(color_)?(" + _GRID_FIELDS + ")"),
+        "lightplane_eval_mlp hands grids over as they are (a grid of GBs is never copied behind the caller's back); the library refuses "
+        "an under-aligned one by name (tests/test_points_host.py, tests/test_gpu_layouts.py::test_as_is_inputs_are_refused)"),
+    ("lp_rays_clip",): (
+        re.compile(r"near_out|far_out|rays\.near_t|rays\.far_t"),
+        "out=(rays.near, rays.far, hit): the results have to land in the caller's own tensors, so neither side of the alias can be "
+        "copied; the library refuses an under-aligned one by name"),
+}
+
+
+def _as_is_rule(entry, path):
+    for entries, (fields, _) in AS_IS.items():
+        if entry in entries and fields.fullmatch(path):
+            return True
+    return False
 
 
 def _is_input(entry, path):
     if entry in _OWN_BY_ENTRY:
-        return path not in _OWN_BY_ENTRY[entry]
+        own = _OWN_BY_ENTRY[entry]
+        return not own.fullmatch(path) if isinstance(own, re.Pattern) else path not in own
     if entry.startswith("lp_splatter") and path == "weight":
         return False  # the splat weights the forward saved
     return not _OWN.match(path)
@@ -356,17 +427,153 @@ def _drive_mlp_splatter_and_embedding():
     return sites
 
 
-DRIVES = pytest.mark.parametrize("drive", [_drive_every_wrapper, _drive_mlp_splatter_and_embedding],
-                                 ids=["renderer_splatter", "mlp_splatter_embedding"])
+def _drive_the_modular_march():
+    """ray_samples, composite_samples, importance_samples and both ray losses, forward and backward: every input and every upstream
+    gradient at a 4-byte aligned base.  (Small shapes of the ops' own case files: nothing is launched.)"""
+    from tests import compositing_cases as CC
+    from tests import importance_cases as IC
+    from tests import ray_loss_cases as LC
+    from tests.synth import random_rays
+    sites = []
+    n, s_reg, s_inf, chn, n_new, n_prop = 7, 4, 1, 4, 3, 6
+    s = s_reg + s_inf
+    ray_sites = ["rays." + f for f in ("directions", "origins", "near_t", "far_t")]
+    # ray_samples
+    r = random_rays(torch.Generator().manual_seed(1), n, 2, None)
+    rays = lp.Rays(directions=_off4(r.directions, True), origins=_off4(r.origins, True), grid_idx=r.grid_idx, near=_off4(r.near, True),
+                   far=_off4(r.far, True))
+    out = lp.ray_samples(rays, s_reg, s_inf)
+    torch.autograd.backward(list(out), [_off4(torch.randn(n, s, 3)), _off4(torch.randn(n, s)), _off4(torch.randn(n, s))])
+    sites += [(e, f) for e in ("lp_ray_samples_forward", "lp_ray_samples_backward") for f in ray_sites]
+    sites += [("lp_ray_samples_backward", f) for f in ("grad_points", "grad_depths", "grad_deltas")]
+    # composite_samples with features and weights
+    c = CC.inputs(n, s, chn, "mixed")
+    names = ("opacity", "features", "depths", "deltas")
+    out = lp.composite_samples(*(_off4(c[k], True) for k in names), return_weights=True)
+    torch.autograd.backward(list(out), [_off4(torch.randn(n)), _off4(torch.randn(n)), _off4(torch.randn(n, chn)), _off4(torch.randn(n, s))])
+    sites += [(e, f) for e in ("lp_composite_forward", "lp_composite_backward") for f in names]
+    sites += [("lp_composite_backward", f) for f in ("grad_ray_length", "grad_neg_log_t", "grad_feature", "grad_weights")]
+    # importance_samples with jitter
+    c = IC.inputs(n, s, n_new, "transparent")
+    rays = lp.Rays(directions=_off4(c["directions"], True), origins=_off4(c["origins"], True), grid_idx=r.grid_idx, near=r.near, far=r.far)
+    out = lp.importance_samples(rays, _off4(c["depths"]), _off4(c["weights"]), n_new, jitter=_off4(c["jitter"]))
+    out.points.backward(_off4(torch.randn(n, s + n_new, 3)))
+    sites += [("lp_importance_samples_forward", f) for f in ("origins", "directions", "depths", "weights", "jitter")]
+    sites += [("lp_importance_samples_backward", f) for f in ("directions", "grad_points")]
+    # distortion_loss
+    c = LC.distortion_inputs(n, s, "mixed")
+    names = ("weights", "depths", "deltas")
+    lp.distortion_loss(*(_off4(c[k], True) for k in names)).backward(_off4(torch.randn(n)))
+    sites += [(e, f) for e in ("lp_distortion_forward", "lp_distortion_backward") for f in names] + [("lp_distortion_backward", "grad_loss")]
+    # interlevel_loss
+    c = LC.interlevel_inputs(n, s, n_prop, "violating")
+    names = ("weights", "depths", "proposal_weights", "proposal_depths")
+    lp.interlevel_loss(*(_off4(c[k], k == "proposal_weights") for k in names)).backward(_off4(torch.randn(n)))
+    sites += [(e, f) for e in ("lp_interlevel_forward", "lp_interlevel_backward") for f in names] + [("lp_interlevel_backward", "grad_loss")]
+    return sites
+
+
+def _drive_the_point_ops():
+    """The gather in list and flat form, the raw and the normalised splat, ``lightplane_eval_mlp`` with a scaffold and a colour
+    grid-list, its opacity-only twin on a flat grid, and the ray clip -- on its default path and in place.  Returns the sites and the
+    AS_IS pointers: ``{(entry point, field): the caller's pointers expected there}``."""
+    from tests import point_grid_cases as GC
+    from tests import points_cases as PC
+    from tests import ray_clip_cases as RC
+    sites, as_is = [], {}
+    idx = lambda c: _off4(c["gidx"].to(torch.int32))  # noqa: E731
+    pts_sites = ["points", "grid_idx"]
+    # gather: a list of three planes, then a flat tensor
+    for name in ("triplane_c16", "voxel_c32_flat"):
+        c = GC.case(name)
+        flat = c["form"] == "flat"
+        grid = _off4(torch.cat([g.reshape(-1, g.shape[-1]) for g in c["grids"]]), True) if flat else [_off4(g, True) for g in c["grids"]]
+        out = lp.sample_grid_at_points(_off4(c["pts"], True), grid, idx(c), grid_sizes=c["sizes"] if flat else None)
+        out.backward(_off4(torch.randn(out.shape)))
+        fields = ["grid.data"] if flat else [f"grid.grids[{k}].data" for k in range(3)]
+        sites += [(e, f) for e in ("lp_point_gather", "lp_point_grad_points") for f in fields + pts_sites]
+        sites += [(e, "vectors") for e in ("lp_point_grad_points", "lp_point_splat")] + [("lp_point_splat", f) for f in pts_sites]
+    # splat: raw (differentiable in the points too), then normalised; the upstream grids reach the gather and the point gradient
+    c = GC.case("triplane_c16")
+    for normalize in (False, True):
+        outs = lp.splat_points(_off4(c["pts"], not normalize), _off4(c["vec"], True), c["sizes"], idx(c), normalize=normalize)
+        torch.autograd.backward(outs, [_off4(torch.randn(o.shape)) for o in outs])
+    sites += [(e, f) for e in ("lp_point_splat", "lp_point_normalize") for f in pts_sites + ["vectors"]]
+    # the decoder at points: two-grid decoder (a colour grid-list), a scaffold; the grids are AS_IS
+    c = PC.case("voxel_c32_twogrid_022x32")
+    d = c["dec"]
+    dec = lp.DecoderParams(_off4(d.mlp_params, True), d.n_hidden_trunk, d.n_hidden_opacity, d.n_hidden_color, d.color_chn)
+    grid, cgrid = [_off4(g, True) for g in c["grids"]], [_off4(g, True) for g in c["cgrids"]]
+    scaffold = _off4((torch.rand(2, 3, 4, 5) < 0.6).float())
+    op, col = lp.lightplane_eval_mlp(_off4(c["pts"], True), grid, idx(c), dec, _off4(c["enc"], True), PC.GAIN, scaffold=scaffold, color_grid=cgrid)
+    torch.autograd.backward([op, col], [_off4(torch.randn(op.shape)), _off4(torch.randn(col.shape))])
+    fwd, bwd = "lp_points_forward", "lp_points_backward"
+    sites += [(e, f) for e in (fwd, bwd) for f in pts_sites + ["mlp_params", "encoding", "scaffold"]]
+    sites += [(bwd, "grad_opacity"), (bwd, "grad_color")]
+    for e in (fwd, bwd):
+        as_is[(e, "grid.grids[0].data")] = [grid[0].data_ptr()]
+        as_is[(e, "color_grid.grids[0].data")] = [cgrid[0].data_ptr()]
+    # ... opacity only, a flat grid
+    c = PC.case("triplane_c20_222x33_scaffold")
+    d = c["dec"]
+    dec = lp.DecoderParams(_off4(d.mlp_params, True), d.n_hidden_trunk, d.n_hidden_opacity, d.n_hidden_color, d.color_chn)
+    flat = _off4(torch.cat([g.reshape(-1, g.shape[-1]) for g in c["grids"]]), True)
+    op = lp.lightplane_eval_mlp_opacity_only(_off4(c["pts"], True), flat, idx(c), dec, PC.GAIN, scaffold=_off4(c["scaffold"]),
+                                             grid_sizes=[list(g.shape) for g in c["grids"]])
+    op.backward(_off4(torch.randn(op.shape)))
+    for e in (fwd, bwd):
+        as_is[(e, "grid.data")] = [flat.data_ptr()]
+    # the ray clip: out of place, then in place on the rays' own near / far
+    c = RC.case("random_2x5x6x7")
+    clip = "lp_rays_clip"
+
+    def rays():
+        return lp.Rays(directions=_off4(c["d"]), origins=_off4(c["o"]), grid_idx=_off4(c["grid_idx"]), near=_off4(c["near"]), far=_off4(c["far"]))
+
+    first = rays()  # (kept alive: the in-place call's tensors must not reuse its addresses)
+    lp.clip_rays_to_scaffold(first, _off4(c["scaffold"]))
+    sites += [(clip, f) for f in ("rays.directions", "rays.origins", "rays.grid_idx", "rays.near_t", "rays.far_t", "scaffold")]
+    r = rays()
+    lp.clip_rays_to_scaffold(r, _off4(c["scaffold"]), out=(r.near, r.far, torch.empty(r.near.shape[0], dtype=torch.uint8)))
+    for f, t in (("near_out", r.near), ("rays.near_t", r.near), ("far_out", r.far), ("rays.far_t", r.far)):
+        as_is[(clip, f)] = [t.data_ptr()]
+    assert first.near.data_ptr() != r.near.data_ptr() and first.far.data_ptr() != r.far.data_ptr()
+    return sites, as_is
+
+
+def _run(drive):
+    """(sites, AS_IS pointers) of a drive; the drives of the first four front-ends have no AS_IS input"""
+    got = drive()
+    sites, as_is = got if isinstance(got, tuple) else (got, {})
+    for (entry, path), ptrs in as_is.items():
+        assert _as_is_rule(entry, path), f"{entry}: {path} is not listed in AS_IS"
+        assert all(p % 16 == 4 for p in ptrs), "the drive's AS_IS tensors sit at a 4-byte aligned base as well"
+    return sites, as_is
+
+
+def _split_as_is(seen, as_is):
+    """(the record without the AS_IS pointers, the AS_IS pointers found): an AS_IS pointer is one the drive named, at its field"""
+    found = [(k, p) for k, p in seen if p in as_is.get(k, ())]
+    rest = [(k, p) for k, p in seen if p not in as_is.get(k, ())]
+    missing = {k: [hex(p) for p in ptrs] for k, ptrs in as_is.items() if not set(ptrs) <= {p for kk, p in found if kk == k}}
+    assert not missing, f"AS_IS inputs that did not arrive as the caller's pointer (copied?): {missing}"
+    return rest, found
+
+
+DRIVES = pytest.mark.parametrize("drive", [_drive_every_wrapper, _drive_mlp_splatter_and_embedding, _drive_the_modular_march,
+                                           _drive_the_point_ops],
+                                 ids=["renderer_splatter", "mlp_splatter_embedding", "modular_march", "point_ops"])
 
 
 @pytest.mark.filterwarnings("ignore:lightplane_amd")
 @DRIVES
 def test_every_pointer_of_an_off4_input_arrives_aligned(recorder, drive):
-    """With the helper in place no pointer of any recorded call is under-aligned: a helper call dropped at any site shows here."""
-    sites = drive()
+    """With the helper in place no pointer of any recorded call is under-aligned: a helper call dropped at any site shows here.  (The
+    AS_IS inputs are the caller's pointer: the library's to refuse.)"""
+    sites, as_is = _run(drive)
     ptrs = recorder.pointers()
-    bad = {k: hex(p) for k, p in recorder.all_pointers() if p % 16}
+    seen, _ = _split_as_is(recorder.all_pointers(), as_is)
+    bad = {k: hex(p) for k, p in seen if p % 16}
     assert not bad, f"under-aligned pointers reached the library: {bad}"
     for s in sites:
         assert s in ptrs, f"{s} was never handed to the library"
@@ -377,10 +584,11 @@ def test_every_pointer_of_an_off4_input_arrives_aligned(recorder, drive):
 def test_without_the_helper_every_input_pointer_arrives_under_aligned(recorder, monkeypatch, drive):
     """``_lib.aligned`` -> identity: EVERY pointer of every recorded call that is not a buffer the wrappers allocate themselves is the
     caller's, 4 bytes past a 16-byte boundary -- the expected set is derived from the record, not listed by hand.  Nothing else
-    (``.contiguous()``, a dtype conversion, autograd) realigns an input, so the helper call at each site is load-bearing."""
+    (``.contiguous()``, a dtype conversion, autograd) realigns an input, so the helper call at each site is load-bearing.  (The AS_IS
+    inputs are the caller's pointer here as well.)"""
     monkeypatch.setattr(_lib, "aligned", lambda t, grid=False: t)
-    sites = drive()
-    seen = recorder.all_pointers()
+    sites, as_is = _run(drive)
+    seen, _ = _split_as_is(recorder.all_pointers(), as_is)
     inputs = [(k, p) for k, p in seen if _is_input(*k)]
     own = [(k, p) for k, p in seen if not _is_input(*k)]
     assert inputs and own
