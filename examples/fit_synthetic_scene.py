@@ -10,7 +10,7 @@ GPU boxes have no datasets.
     python examples/fit_synthetic_scene.py [--steps 300] [--rays 8192] [--stop-transmittance 0] [--tv-weight 0] [--upsample-steps 100,200]
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
                                             [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0] [--modular]
-                                            [--importance N] [--distortion-weight W]
+                                            [--importance N] [--distortion-weight W] [--render-samples]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -55,6 +55,11 @@ ray from them (stratified, jittered with ``torch.rand``) and merges them into th
 ``W * mean(lp.distortion_loss(weights, depths, deltas) / (far - near))`` on the weights ``composite_samples(..., return_weights=True)``
 hands back -- one fused kernel, with gradients through the weights into the decoder and the planes (the JSON line gains
 ``distortion_weight`` and the first / last value of the term).  0 leaves the run as it is without it.
+
+``--render-samples`` (with ``--modular``) runs the fitted march -- the fine pass with ``--importance`` -- through
+``renderer.render_samples`` (``lp.render_samples``): the decoder and the compositing in one launch at the samples' depths, with no
+points, opacity or colour tensor in between; the distortion loss then reads the weights that op hands back (the JSON line gains
+``render_samples``).  The coarse pass of ``--importance`` stays on the chain.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -114,10 +119,12 @@ def heldout_psnr(renderer, grids, n_rays, num_samples, seed, dev, scaffold=None,
     return -10.0 * math.log10(mse)
 
 
-def render_modular(renderer, rays, grids, scaffold=None, importance=0, distortion=False):
+def render_modular(renderer, rays, grids, scaffold=None, importance=0, distortion=False, fused_fine=False):
     """``(alpha, rgb, distortion)`` of ``renderer(rays, grids)`` through ray_samples -> the decoder at points -> composite_samples
     (background 0); ``importance`` > 0: that march only for its weights, and the result from the samples ``importance_samples`` makes
-    of them; ``distortion``: the mean distortion loss of the fitted march on distances normalised by ``far - near`` (else ``None``)"""
+    of them; ``distortion``: the mean distortion loss of the fitted march on distances normalised by ``far - near`` (else ``None``);
+    ``fused_fine``: the fitted march runs through ``renderer.render_samples`` -- decoder and compositing in one launch at the samples'
+    depths, without the per-sample tensors"""
     samples = renderer.ray_samples(rays)
     if importance > 0:
         with torch.no_grad():
@@ -126,6 +133,10 @@ def render_modular(renderer, rays, grids, scaffold=None, importance=0, distortio
             weights = lp.composite_samples(opacity, None, samples.depths, samples.deltas, return_weights=True)[3]
             jitter = torch.rand(weights.shape[0], importance, device=weights.device)
         samples = renderer.importance_samples(rays, samples, weights, importance, jitter=jitter)
+    if fused_fine:
+        out = renderer.render_samples(rays, grids, samples, scaffold=scaffold, return_weights=distortion)
+        dist = (lp.distortion_loss(out[3], samples.depths, samples.deltas) / (rays.far - rays.near)).mean() if distortion else None
+        return out[1], out[2], dist
     opacity, color = renderer.eval_decoder_at_points(samples.points, rays.grid_idx, None, grids, scaffold=scaffold,
                                                      directions=rays.directions)
     if not distortion:
@@ -138,7 +149,8 @@ def render_modular(renderer, rays, grids, scaffold=None, importance=0, distortio
 
 def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_transmittance=0.0, verbose=False, tv_weight=0.0,
         upsample_steps=(), scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, export_pointcloud=None, clip_rays=False,
-        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None, modular=False, importance=0, distortion_weight=0.0):
+        export_mesh=None, mesh_size=64, mesh_level=1.0, on_fitted=None, modular=False, importance=0, distortion_weight=0.0,
+        fused_fine=False):
     """``on_fitted(renderer, grids)``: called after the last step, before the exports, with the fitted module and its planes"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
@@ -180,7 +192,7 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         if modular:
-            alpha, rgb, dist = render_modular(renderer, rays, list(grids), scaffold, importance, distortion_weight > 0.0)
+            alpha, rgb, dist = render_modular(renderer, rays, list(grids), scaffold, importance, distortion_weight > 0.0, fused_fine)
         else:
             _, alpha, rgb = renderer(rays, list(grids), scaffold=scaffold)
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
@@ -202,6 +214,8 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
         out.update(modular=True)
     if importance > 0:
         out.update(importance=importance)
+    if fused_fine:
+        out.update(render_samples=True)
     if distortion_weight > 0.0:
         out.update(distortion_weight=distortion_weight, first_distortion=dists[0], last_distortion=dists[-1])
     if upsample_steps:
@@ -286,16 +300,19 @@ def main(argv=None):
                     help="render the training batches through ray_samples -> eval_decoder_at_points -> composite_samples")
     ap.add_argument("--importance", type=int, default=0,
                     help="with --modular: new samples per ray drawn from the weights of a coarse pass (importance_samples); 0 = none")
+    ap.add_argument("--render-samples", action="store_true",
+                    help="with --modular: the fitted march through render_samples (decoder + compositing in one launch at the samples' depths)")
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="with --modular: weight of the distortion loss of the fitted march (distortion_loss); 0 = none")
     a = ap.parse_args(argv)
     assert a.importance == 0 or a.modular, "--importance resamples the modular march: pass --modular as well"
+    assert not a.render_samples or a.modular, "--render-samples runs the fitted pass of the modular march: pass --modular as well"
     assert a.distortion_weight == 0.0 or a.modular, "--distortion-weight needs the weights of the modular march: pass --modular as well"
     out = fit(a.steps, a.rays, res=a.res, stop_transmittance=a.stop_transmittance, verbose=True, tv_weight=a.tv_weight,
               upsample_steps=a.upsample_steps, scaffold_steps=a.scaffold_steps, scaffold_size=a.scaffold_size,
               scaffold_threshold=a.scaffold_threshold, export_pointcloud=a.export_pointcloud, clip_rays=a.clip_rays,
               export_mesh=a.export_mesh, mesh_size=a.mesh_size, mesh_level=a.mesh_level, modular=a.modular, importance=a.importance,
-              distortion_weight=a.distortion_weight)
+              distortion_weight=a.distortion_weight, fused_fine=a.render_samples)
     print(json.dumps(out))
     return out
 

@@ -188,6 +188,22 @@ class LpInterlevelArgs(C.Structure):  # include/lightplane_hip_losses.h
     ]
 
 
+class LpRenderSamplesArgs(C.Structure):  # include/lightplane_hip_render_samples.h
+    _fields_ = [
+        ("grid", LpGridList), ("color_grid", LpGridList), ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64),
+        ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("color_chn", C.c_int32), ("gain", C.c_float), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32),
+        ("origins", C.c_void_p), ("directions", C.c_void_p), ("grid_idx", C.c_void_p), ("encoding", C.c_void_p),
+        ("encoding_dim", C.c_int32), ("n_samples", C.c_int32), ("n_rays", C.c_int64), ("depths", C.c_void_p), ("deltas", C.c_void_p),
+        ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("ray_length", C.c_void_p), ("neg_log_t", C.c_void_p), ("feature", C.c_void_p), ("weights", C.c_void_p), ("chunk_nlt", C.c_void_p),
+        ("grad_ray_length", C.c_void_p), ("grad_neg_log_t", C.c_void_p), ("grad_feature", C.c_void_p), ("grad_weights", C.c_void_p),
+        ("grad_grid", C.c_void_p), ("grad_color_grid", C.c_void_p),
+        ("grad_grid_list", C.c_void_p * LP_MAX_GRIDS), ("grad_color_grid_list", C.c_void_p * LP_MAX_GRIDS),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -221,6 +237,9 @@ LP_IMPORTANCE_MAX = 2048
 LOSSES_EXPORTS = ("lp_distortion_forward", "lp_distortion_backward", "lp_interlevel_forward", "lp_interlevel_backward")
 #: the most samples (and proposal samples) per ray of the two losses (LP_RAY_LOSS_MAX of that header: a ray's working set stays in LDS)
 LP_RAY_LOSS_MAX = 2048
+
+#: every symbol include/lightplane_hip_render_samples.h declares (once more a header and a table of their own)
+RENDER_SAMPLES_EXPORTS = ("lp_render_samples_forward", "lp_render_samples_backward", "lp_render_samples_chunks")
 
 
 def _signatures():
@@ -273,6 +292,9 @@ def _signatures():
         # distortion and interlevel loss of a ray's samples (include/lightplane_hip_losses.h): args, stream
         (LOSSES_EXPORTS[:2], C.c_int, (P(LpDistortionArgs), vp)),
         (LOSSES_EXPORTS[2:], C.c_int, (P(LpInterlevelArgs), vp)),
+        # decoder + compositing at caller-given depths (include/lightplane_hip_render_samples.h): args, stream; n_samples
+        (RENDER_SAMPLES_EXPORTS[:2], C.c_int, (P(LpRenderSamplesArgs), vp)),
+        (RENDER_SAMPLES_EXPORTS[2:], C.c_int, (i32,)),
     )
 
 
@@ -304,7 +326,8 @@ def lib() -> C.CDLL:
                       (14, LpPointGridArgs), (16, LpMeshArgs),  # (selectors 9, 11, 13 and 15 do not exist: lightplane_hip.h)
                       (18, LpRaySamplesArgs), (20, LpCompositeArgs),  # (nor 17, 19 and 21: lightplane_hip_samples.h)
                       (22, LpImportanceArgs),  # (nor 23: lightplane_hip_importance.h)
-                      (24, LpDistortionArgs), (26, LpInterlevelArgs)):  # (nor 25 and 27: lightplane_hip_losses.h)
+                      (24, LpDistortionArgs), (26, LpInterlevelArgs),  # (nor 25 and 27: lightplane_hip_losses.h)
+                      (30, LpRenderSamplesArgs)):  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

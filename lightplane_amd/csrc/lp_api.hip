@@ -4,6 +4,7 @@
 #include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "lp_host.h"
 #include "lp_mfma_common.h"
@@ -821,6 +822,78 @@ static int check_interlevel(const LpInterlevelArgs* args, bool backward) {
   return LP_OK;
 }
 
+// everything lp_render_samples_forward / _backward share; fills the normalised copy.  The decoder, the grid-lists and the scaffold go
+// through the checks of the decoder at points (the colour head always takes part in the forward; in the backward with grad_feature).
+// Messages begin with the field where a field is at fault.
+static int check_render_samples(const char* what, const LpRenderSamplesArgs* args, bool backward, LpRenderSamplesArgs& a) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_feature != nullptr : true;
+  if ((rc = check_grid_list_aligned("grid", args->grid))) return rc;
+  if ((rc = check_grid_list_aligned("color_grid", args->color_grid))) return rc;
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, origins);
+  LP_ALIGNED(*args, directions);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, ray_length);
+  LP_ALIGNED(*args, neg_log_t);
+  LP_ALIGNED(*args, feature);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, chunk_nlt);
+  LP_ALIGNED(*args, grad_ray_length);
+  LP_ALIGNED(*args, grad_neg_log_t);
+  LP_ALIGNED(*args, grad_feature);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_grid);
+  LP_ALIGNED(*args, grad_color_grid);
+  if ((rc = check_ptr_list_aligned("grad_grid_list", args->grad_grid_list))) return rc;
+  if ((rc = check_ptr_list_aligned("grad_color_grid_list", args->grad_color_grid_list))) return rc;
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  if (args->n_samples < 1) return set_error(LP_EINVAL, "n_samples %d < 1", args->n_samples);
+  if ((rc = check_point_batch(what, args->n_rays, args->n_samples, true))) return rc;
+  if ((rc = check_grid_list("grid", args->grid, SAMPLED))) return rc;
+  if ((rc = check_grid_list("color_grid", args->color_grid, SAMPLED_OR_ABSENT))) return rc;
+  if ((rc = check_color_grid(what, args->grid, args->color_grid, args->trunk))) return rc;
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, args->grid.channels, args->trunk, args->opacity, head_in))) return rc;
+  const int64_t n_to = mlp_numel(args->trunk) + mlp_numel(args->opacity);
+  if ((rc = check_color_head(what, args->color, head_in, n_to, true, args->color_chn, args->encoding_dim))) return rc;
+  if ((rc = check_param_count(what, n_to + mlp_numel(args->color), args->n_mlp_params, false))) return rc;
+  if (args->scaffold && (rc = check_scaffold_for_grid(what, args->scaffold_shape, args->grid))) return rc;
+  if (!args->mlp_params) return set_error(LP_ENULL, "%s: mlp_params is NULL", what);
+  if (args->n_rays > 0) {  // (an empty batch has no tensors to point at)
+    const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+        {"origins", args->origins, true}, {"directions", args->directions, true}, {"grid_idx", args->grid_idx, true},
+        {"encoding", args->encoding, true}, {"depths", args->depths, true}, {"deltas", args->deltas, true},
+        {"chunk_nlt", args->chunk_nlt, backward}};
+    for (const auto& f : ptrs)
+      if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  }
+  a = *args;
+  if (!normalize_grid_list(a.grid)) return set_error(LP_ENULL, "%s: grid.data is NULL (and a grid has no pointer of its own)", what);
+  if (color && !normalize_grid_list(a.color_grid))
+    return set_error(LP_ENULL, "%s: color_grid.data is NULL (and a grid has no pointer of its own)", what);
+  if (backward) {
+    if ((rc = normalize_grad_list("grad_grid", a.grad_grid_list, a.grad_grid, a.grid.n_grids))) return rc;
+    if ((rc = normalize_grad_list("grad_color_grid", a.grad_color_grid_list, a.grad_color_grid, a.color_grid.n_grids))) return rc;
+  }
+  return LP_OK;
+}
+
+// the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
+// with the compositing): the top-level keys of the text stay as they are
+static const char* build_info_points_family() {
+  static char text[2048];
+  const char* p = build_info_points();
+  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s}", (int)strlen(p) - 1, p, build_info_render_samples());
+  return text;
+}
+
 }  // namespace lp
 
 using namespace lp;
@@ -838,7 +911,7 @@ const char* lp_build_info(void) {
       {"test_hooks", build_info_tuned_bwd_aux}, {"tuned_bwd", build_info_tuned_bwd},          {"loop_bwd_deep", build_info_loop_deep},
       {"loop_bwd_shallow", build_info_loop_shallow}, {"mlp_splatter_bwd", build_info_splatter_mlp}, {"loop_fwd_stream", build_info_loop_stream},
       {"grid_tv", build_info_grid_tv},          {"grid_resample", build_info_grid_resample},  {"scaffold", build_info_scaffold},
-      {"points", build_info_points},            {"ray_clip", build_info_ray_clip},            {"point_grid", build_info_point_grid},
+      {"points", build_info_points_family},     {"ray_clip", build_info_ray_clip},           {"point_grid", build_info_point_grid},
       {"mesh", build_info_mesh}};
   static const bool once = [] {
     size_t n = (size_t)snprintf(info, sizeof(info), "{\"version\": %d, \"src_hash\": \"%s\"", lp_version(), LP_BUILD_SRC_HASH);
@@ -875,6 +948,7 @@ int lp_abi_sizeof(int which) {
     case 22: return (int)sizeof(LpImportanceArgs);  // (and 21: lightplane_hip_importance.h)
     case 24: return (int)sizeof(LpDistortionArgs);  // (and 23; this one and the next: lightplane_hip_losses.h)
     case 26: return (int)sizeof(LpInterlevelArgs);  // (and 25)
+    case 30: return (int)sizeof(LpRenderSamplesArgs);  // (and 27, 28, 29: lightplane_hip_render_samples.h)
     default: return -1;
   }
 }
@@ -1280,6 +1354,22 @@ int lp_importance_samples_forward(const LpImportanceArgs* args, void* stream) {
   const int rc = check_importance(args, false);
   if (rc || args->n_rays == 0) return rc;
   return importance_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_render_samples_chunks(int32_t n_samples) { return n_samples < 1 ? 0 : (int)(((int64_t)n_samples + 63) / 64); }
+
+int lp_render_samples_forward(const LpRenderSamplesArgs* args, void* stream) {
+  LpRenderSamplesArgs a;
+  const int rc = check_render_samples("lp_render_samples_forward", args, false, a);
+  if (rc != LP_OK || a.n_rays == 0) return rc;
+  return render_samples_launch(a, false, (hipStream_t)stream);
+}
+
+int lp_render_samples_backward(const LpRenderSamplesArgs* args, void* stream) {
+  LpRenderSamplesArgs a;
+  const int rc = check_render_samples("lp_render_samples_backward", args, true, a);
+  if (rc != LP_OK || a.n_rays == 0) return rc;
+  return render_samples_launch(a, true, (hipStream_t)stream);
 }
 
 int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {

@@ -70,14 +70,20 @@ LP_DEV void sc_gather(const LpGridList& gl, int b, float x, float y, float z, bo
 // y[o] = b[o] + sum_i x[i] * Wm[i * ldw + o], o < n_out, optionally through a ReLU.  x, y: LDS columns of the lane (stride 64), x != y.
 // Wm, bias and every index into them are wave-uniform: scalar loads.  Blocks of eight outputs; the last, partial block (the opacity
 // head's single output) re-reads its last column in the spare slots and does not store them.
-LP_DEV void sc_dense(const float* __restrict__ Wm, const float* __restrict__ bias, int d_in, int ldw, int n_out, const float* x, float* y,
-                     bool relu) {
+// WP: const float*, or sc_const_ptr -- the same address in the constant address space, for a kernel that stores to global memory
+// before it reads the weights again (a loop over chunks: lp_render_samples.hip).  The compiler issues scalar loads only for memory it
+// knows the kernel does not write; behind a store it cannot tell, and the weights come through per-lane vector loads instead.
+typedef const __attribute__((address_space(4))) float* sc_const_ptr;
+LP_DEV sc_const_ptr sc_const(const float* p) { return (sc_const_ptr)p; }  // (p: global memory this kernel never writes)
+
+template <typename WP>
+LP_DEV void sc_dense(WP __restrict__ Wm, WP __restrict__ bias, int d_in, int ldw, int n_out, const float* x, float* y, bool relu) {
   int o0 = 0;
   for (; o0 + 8 <= n_out; o0 += 8) {
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = bias[o0 + k];
-    const float* w = Wm + o0;
+    WP w = Wm + o0;
 #pragma unroll 4
     for (int i = 0; i < d_in; ++i) {
       const float xi = x[i * SC_WAVE];
@@ -96,7 +102,7 @@ LP_DEV void sc_dense(const float* __restrict__ Wm, const float* __restrict__ bia
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = bias[o0 + kk[k]];
-    const float* w = Wm + o0;
+    WP w = Wm + o0;
 #pragma unroll 4
     for (int i = 0; i < d_in; ++i) {
       const float xi = x[i * SC_WAVE];

@@ -7,6 +7,7 @@
 #include "../../include/lightplane_hip_samples.h"
 #include "../../include/lightplane_hip_importance.h"
 #include "../../include/lightplane_hip_losses.h"
+#include "../../include/lightplane_hip_render_samples.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -164,6 +165,10 @@ int importance_launch(const LpImportanceArgs& a, bool backward, hipStream_t stre
 // distortion and interlevel loss of a ray's samples: lp_ray_losses.hip (`a` checked by lp_api.hip; n_rays > 0)
 int distortion_launch(const LpDistortionArgs& a, bool backward, hipStream_t stream);
 int interlevel_launch(const LpInterlevelArgs& a, bool backward, hipStream_t stream);
+// rendering at caller-given sample depths, decoder + compositing in one launch: lp_render_samples.hip (`a` normalised and checked by
+// lp_api.hip; n_rays > 0)
+int render_samples_launch(const LpRenderSamplesArgs& a, bool backward, hipStream_t stream);
+const char* build_info_render_samples();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

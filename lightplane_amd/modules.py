@@ -34,6 +34,7 @@ from .renderer import _render, lightplane_renderer
 from .ray_clip import clip_rays_to_scaffold as _clip_rays_to_scaffold
 from .compositing import ray_samples as _ray_samples
 from .importance import importance_samples as _importance_samples
+from .render_samples import render_samples as _render_samples
 from .scaffold import calculate_scaffold as _fused_calculate_scaffold
 from .mesh import extract_mesh as _fused_extract_mesh
 from .splatter import lightplane_mlp_splatter, lightplane_splatter
@@ -380,6 +381,32 @@ class LightplaneRenderer(torch.nn.Module):
         ``num_importance`` new samples per ray drawn from the compositing ``weights`` of the coarse pass, merged into the coarse
         ones -- the samples of the fine pass.  Keywords (``include_coarse``, ``pad``, ``jitter``) are passed on."""
         return _importance_samples(rays, samples.depths, weights, num_importance, **kw)
+
+    def render_samples(self, rays: Rays, feature_grid, samples, *, return_weights: bool = False, color_feature_grid=None,
+                       scaffold: Optional[torch.Tensor] = None, grid_sizes=None, color_grid_sizes=None, bg_color=None,
+                       gain: Optional[float] = None, mask_out_of_bounds_samples: Optional[bool] = None,
+                       contract_coords: Optional[bool] = None, return_log_transmittance: Optional[bool] = None):
+        """``forward`` at the caller's ``samples`` (a ``RaySamples``, as ``ray_samples`` / ``importance_samples`` return; its depths and
+        deltas are read, its points are not): :func:`lightplane_amd.render_samples` with the module's decoder, gain, flags and ray
+        encoding, then the background / alpha epilogue of ``forward``.  Returns ``(ray_length_render, alpha, feature_render)`` and, with
+        ``return_weights=True``, the compositing weights ``[R, S]`` as a fourth result.  Sample positions are a stop-gradient."""
+        return_log_t = if_not_none_else(return_log_transmittance, self.return_log_transmittance)
+        bg = self._process_bg_color(if_not_none_else(bg_color, self.bg_color)).to(rays.device)
+        _check_renderer_ray_encoding_input(rays.encoding, self.ray_embedding_num_harmonics,
+                                           self.rays_encoding_dim, self.enable_direction_dependent_colors)
+        r = copy.copy(rays)
+        r.encoding = self._get_ray_encoding(rays.encoding, rays.directions)
+        out = _render_samples(
+            r, samples.depths.detach(), samples.deltas.detach(), feature_grid, self.get_decoder_params(),
+            gain=if_not_none_else(gain, self.gain),
+            mask_out_of_bounds_samples=if_not_none_else(mask_out_of_bounds_samples, self.mask_out_of_bounds_samples),
+            contract_coords=if_not_none_else(contract_coords, self.contract_coords), scaffold=scaffold, color_grid=color_feature_grid,
+            grid_sizes=grid_sizes, color_grid_sizes=color_grid_sizes, return_weights=return_weights)
+        ray_length, nlt, feature = out[:3]
+        transmittance = torch.exp(-nlt)
+        feature = feature + transmittance[..., None] * bg
+        alpha = -nlt if return_log_t else 1 - transmittance
+        return (ray_length, alpha, feature) + tuple(out[3:])
 
     # -- ray encoding ---------------------------------------------------------------------
     def _get_ray_embedding(self, ray_directions: torch.Tensor) -> torch.Tensor:
