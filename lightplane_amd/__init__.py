@@ -37,6 +37,7 @@ from .compositing import RaySamples, composite_samples, ray_samples  # noqa: E40
 from .importance import importance_samples  # noqa: E402
 from .ray_losses import distortion_loss, interlevel_loss  # noqa: E402
 from .render_samples import render_samples  # noqa: E402
+from .ray_grid import gather_along_rays, splat_along_rays  # noqa: E402
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -67,6 +68,7 @@ __all__ = [
     "importance_samples",
     "distortion_loss", "interlevel_loss",
     "render_samples",
+    "splat_along_rays", "gather_along_rays",
 ]
 
 _NOT_PROVIDED = {

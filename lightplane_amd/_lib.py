@@ -204,6 +204,16 @@ class LpRenderSamplesArgs(C.Structure):  # include/lightplane_hip_render_samples
     ]
 
 
+class LpRayGridArgs(C.Structure):  # include/lightplane_hip_ray_grid.h
+    _fields_ = [
+        ("grid", LpGridList), ("row_weight", C.c_void_p * LP_MAX_GRIDS),
+        ("origins", C.c_void_p), ("directions", C.c_void_p), ("grid_idx", C.c_void_p), ("depths", C.c_void_p), ("weights", C.c_void_p),
+        ("vectors", C.c_void_p), ("out_features", C.c_void_p), ("grad_weights", C.c_void_p), ("grad_depths", C.c_void_p),
+        ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("channels", C.c_int32),
+        ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -240,6 +250,9 @@ LP_RAY_LOSS_MAX = 2048
 
 #: every symbol include/lightplane_hip_render_samples.h declares (once more a header and a table of their own)
 RENDER_SAMPLES_EXPORTS = ("lp_render_samples_forward", "lp_render_samples_backward", "lp_render_samples_chunks")
+
+#: every symbol include/lightplane_hip_ray_grid.h declares (and once more)
+RAY_GRID_EXPORTS = ("lp_ray_grid_splat", "lp_ray_grid_gather", "lp_ray_grid_grad_samples")
 
 
 def _signatures():
@@ -295,6 +308,8 @@ def _signatures():
         # decoder + compositing at caller-given depths (include/lightplane_hip_render_samples.h): args, stream; n_samples
         (RENDER_SAMPLES_EXPORTS[:2], C.c_int, (P(LpRenderSamplesArgs), vp)),
         (RENDER_SAMPLES_EXPORTS[2:], C.c_int, (i32,)),
+        # weighted splat / gather of a grid-list along rays at caller-given depths (include/lightplane_hip_ray_grid.h): args, stream
+        (RAY_GRID_EXPORTS, C.c_int, (P(LpRayGridArgs), vp)),
     )
 
 
@@ -327,7 +342,8 @@ def lib() -> C.CDLL:
                       (18, LpRaySamplesArgs), (20, LpCompositeArgs),  # (nor 17, 19 and 21: lightplane_hip_samples.h)
                       (22, LpImportanceArgs),  # (nor 23: lightplane_hip_importance.h)
                       (24, LpDistortionArgs), (26, LpInterlevelArgs),  # (nor 25 and 27: lightplane_hip_losses.h)
-                      (30, LpRenderSamplesArgs)):  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
+                      (30, LpRenderSamplesArgs),  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
+                      (34, LpRayGridArgs)):  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -20,9 +20,9 @@ OUT = os.path.join(PKG, "liblightplane_hip.so")
 SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_stream.hip", "lp_renderer_loop_dump.hip", "lp_renderer_mfma_bwd.hip", "lp_renderer_mfma_bwd_dump.hip", "lp_renderer_mfma_bwd_c32.hip", "lp_renderer_mfma_bwd_aux.hip", "lp_renderer_mfma_bwd_tm.hip",
            "lp_splatter_mlp_loop.hip", "lp_splatter_mlp_loop_dump.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
            "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_dump.hip", "lp_splatter_mlp_loop_shallow.hip",
-           "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_grid_tv.hip", "lp_grid_resample.hip", "lp_scaffold.hip", "lp_points.hip", "lp_render_samples.hip", "lp_point_grid.hip", "lp_ray_clip.hip", "lp_mesh.hip", "lp_composite.hip", "lp_importance.hip", "lp_ray_losses.hip", "lp_api.hip"]
+           "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_grid_tv.hip", "lp_grid_resample.hip", "lp_scaffold.hip", "lp_points.hip", "lp_render_samples.hip", "lp_point_grid.hip", "lp_ray_grid.hip", "lp_ray_clip.hip", "lp_mesh.hip", "lp_composite.hip", "lp_importance.hip", "lp_ray_losses.hip", "lp_api.hip"]
 PUBLIC_HEADERS = [os.path.join("..", "..", "include", name) for name in ("lightplane_hip.h", "lightplane_hip_samples.h", "lightplane_hip_importance.h", "lightplane_hip_losses.h",
-                                                                          "lightplane_hip_render_samples.h")]
+                                                                          "lightplane_hip_render_samples.h", "lightplane_hip_ray_grid.h")]
 # every header of this directory (the rule of source_hash()) and the public ones: a change to any of them recompiles everything
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + PUBLIC_HEADERS
 FLAGS = [

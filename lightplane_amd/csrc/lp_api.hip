@@ -885,6 +885,47 @@ static int check_render_samples(const char* what, const LpRenderSamplesArgs* arg
   return LP_OK;
 }
 
+// everything the three lp_ray_grid_* entry points check; fills the normalised copy.  mode: 0 splat, 1 gather, 2 grad_samples.  Messages
+// begin with the field where a field is at fault.  The NULL checks do not wait for a non-empty batch: the Python front-end never
+// calls with one, and a C caller's mistake shows whatever the sizes are.
+static int check_ray_grid(const char* what, const LpRayGridArgs* args, int mode, LpRayGridArgs& a) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  if ((rc = check_grid_list_aligned("grid", args->grid))) return rc;
+  if ((rc = check_ptr_list_aligned("row_weight", args->row_weight))) return rc;
+  LP_ALIGNED(*args, origins);
+  LP_ALIGNED(*args, directions);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, vectors);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_depths);
+  if (args->n_rays < 0) return set_error(LP_EINVAL, "n_rays %lld < 0", (long long)args->n_rays);
+  if (args->n_samples < 0) return set_error(LP_EINVAL, "n_samples %d < 0", args->n_samples);
+  if ((rc = check_point_batch(what, args->n_rays, args->n_samples, true))) return rc;
+  if ((rc = check_grid_list("grid", args->grid, SAMPLED))) return rc;
+  if (args->channels != args->grid.channels)
+    return set_error(LP_EINVAL, "channels %d of the per-ray vectors != grid channels %d", args->channels, args->grid.channels);
+  int have = 0;
+  for (int g = 0; g < args->grid.n_grids; ++g) have += args->row_weight[g] != nullptr;
+  if (mode == 0 && have != 0 && have != args->grid.n_grids)
+    return set_error(LP_EINVAL, "row_weight given for %d of %d grids (all or none)", have, args->grid.n_grids);
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"origins", args->origins, true},   {"directions", args->directions, true},  {"grid_idx", args->grid_idx, true},
+      {"depths", args->depths, true},     {"weights", args->weights, true},        {"vectors", args->vectors, mode != 1},
+      {"out_features", args->out_features, mode == 1}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  if (mode == 2 && !args->grad_weights && !args->grad_depths)
+    return set_error(LP_ENULL, "grad_weights and grad_depths are both NULL: %s has no result to write", what);
+  a = *args;
+  if (!normalize_grid_list(a.grid)) return set_error(LP_ENULL, "%s: grid.data is NULL (and a grid has no pointer of its own)", what);
+  for (int g = a.grid.n_grids; g < LP_MAX_GRIDS; ++g) a.row_weight[g] = nullptr;
+  return LP_OK;
+}
+
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
 // with the compositing): the top-level keys of the text stay as they are
 static const char* build_info_points_family() {
@@ -949,6 +990,7 @@ int lp_abi_sizeof(int which) {
     case 24: return (int)sizeof(LpDistortionArgs);  // (and 23; this one and the next: lightplane_hip_losses.h)
     case 26: return (int)sizeof(LpInterlevelArgs);  // (and 25)
     case 30: return (int)sizeof(LpRenderSamplesArgs);  // (and 27, 28, 29: lightplane_hip_render_samples.h)
+    case 34: return (int)sizeof(LpRayGridArgs);  // (and 31, 32, 33: lightplane_hip_ray_grid.h)
     default: return -1;
   }
 }
@@ -1370,6 +1412,27 @@ int lp_render_samples_backward(const LpRenderSamplesArgs* args, void* stream) {
   const int rc = check_render_samples("lp_render_samples_backward", args, true, a);
   if (rc != LP_OK || a.n_rays == 0) return rc;
   return render_samples_launch(a, true, (hipStream_t)stream);
+}
+
+int lp_ray_grid_splat(const LpRayGridArgs* args, void* stream) {
+  LpRayGridArgs a;
+  const int rc = check_ray_grid("lp_ray_grid_splat", args, 0, a);
+  if (rc != LP_OK || a.n_rays == 0 || a.n_samples == 0) return rc;
+  return ray_grid_splat_launch(a, (hipStream_t)stream);
+}
+
+int lp_ray_grid_gather(const LpRayGridArgs* args, void* stream) {
+  LpRayGridArgs a;
+  const int rc = check_ray_grid("lp_ray_grid_gather", args, 1, a);
+  if (rc != LP_OK || a.n_rays == 0 || a.n_samples == 0) return rc;
+  return ray_grid_gather_launch(a, (hipStream_t)stream);
+}
+
+int lp_ray_grid_grad_samples(const LpRayGridArgs* args, void* stream) {
+  LpRayGridArgs a;
+  const int rc = check_ray_grid("lp_ray_grid_grad_samples", args, 2, a);
+  if (rc != LP_OK || a.n_rays == 0 || a.n_samples == 0) return rc;
+  return ray_grid_grad_samples_launch(a, (hipStream_t)stream);
 }
 
 int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {

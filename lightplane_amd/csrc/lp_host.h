@@ -8,6 +8,7 @@
 #include "../../include/lightplane_hip_importance.h"
 #include "../../include/lightplane_hip_losses.h"
 #include "../../include/lightplane_hip_render_samples.h"
+#include "../../include/lightplane_hip_ray_grid.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -169,6 +170,11 @@ int interlevel_launch(const LpInterlevelArgs& a, bool backward, hipStream_t stre
 // lp_api.hip; n_rays > 0)
 int render_samples_launch(const LpRenderSamplesArgs& a, bool backward, hipStream_t stream);
 const char* build_info_render_samples();
+// weighted splat / gather of a grid-list along rays at caller-given depths: lp_ray_grid.hip (`a` normalised and checked by lp_api.hip;
+// n_rays * n_samples > 0)
+int ray_grid_splat_launch(const LpRayGridArgs& a, hipStream_t stream);
+int ray_grid_gather_launch(const LpRayGridArgs& a, hipStream_t stream);
+int ray_grid_grad_samples_launch(const LpRayGridArgs& a, hipStream_t stream);
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 
