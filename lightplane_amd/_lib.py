@@ -214,6 +214,21 @@ class LpRayGridArgs(C.Structure):  # include/lightplane_hip_ray_grid.h
     ]
 
 
+LP_HASH_MAX_LEVELS = 32
+
+
+class LpHashGridArgs(C.Structure):  # include/lightplane_hip_hash_grid.h
+    _fields_ = [
+        ("table", C.c_void_p), ("grad_table", C.c_void_p), ("points", C.c_void_p), ("grid_idx", C.c_void_p),
+        ("out_features", C.c_void_p), ("grad_features", C.c_void_p), ("grad_points", C.c_void_p),
+        ("entries", C.c_int64), ("n_rays", C.c_int64), ("n_pts", C.c_int64),
+        ("offset", C.c_int64 * LP_HASH_MAX_LEVELS), ("resolution", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("size", C.c_int32 * LP_HASH_MAX_LEVELS), ("hashed", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("batch", C.c_int32), ("features_per_level", C.c_int32), ("n_levels", C.c_int32),
+        ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -253,6 +268,9 @@ RENDER_SAMPLES_EXPORTS = ("lp_render_samples_forward", "lp_render_samples_backwa
 
 #: every symbol include/lightplane_hip_ray_grid.h declares (and once more)
 RAY_GRID_EXPORTS = ("lp_ray_grid_splat", "lp_ray_grid_gather", "lp_ray_grid_grad_samples")
+
+#: every symbol include/lightplane_hip_hash_grid.h declares (and again)
+HASH_GRID_EXPORTS = ("lp_hash_grid_forward", "lp_hash_grid_backward_table", "lp_hash_grid_backward_points")
 
 
 def _signatures():
@@ -310,6 +328,8 @@ def _signatures():
         (RENDER_SAMPLES_EXPORTS[2:], C.c_int, (i32,)),
         # weighted splat / gather of a grid-list along rays at caller-given depths (include/lightplane_hip_ray_grid.h): args, stream
         (RAY_GRID_EXPORTS, C.c_int, (P(LpRayGridArgs), vp)),
+        # multiresolution hash-grid encoding of points (include/lightplane_hip_hash_grid.h): args, stream
+        (HASH_GRID_EXPORTS, C.c_int, (P(LpHashGridArgs), vp)),
     )
 
 
@@ -343,7 +363,8 @@ def lib() -> C.CDLL:
                       (22, LpImportanceArgs),  # (nor 23: lightplane_hip_importance.h)
                       (24, LpDistortionArgs), (26, LpInterlevelArgs),  # (nor 25 and 27: lightplane_hip_losses.h)
                       (30, LpRenderSamplesArgs),  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
-                      (34, LpRayGridArgs)):  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
+                      (34, LpRayGridArgs),  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
+                      (38, LpHashGridArgs)):  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -926,6 +926,52 @@ static int check_ray_grid(const char* what, const LpRayGridArgs* args, int mode,
   return LP_OK;
 }
 
+// everything the three lp_hash_grid_* entry points check.  mode: 0 forward, 1 backward_table, 2 backward_points.  Messages begin with
+// the field where a field is at fault.  The layout is held to the rules of lightplane_hip_hash_grid.h: the kernels index with it.
+static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mode) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, table);
+  LP_ALIGNED(*args, grad_table);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_features);
+  LP_ALIGNED(*args, grad_points);
+  if ((rc = check_point_batch(what, args->n_rays, args->n_pts, true))) return rc;
+  if (args->batch < 1) return set_error(LP_EINVAL, "batch %d < 1", args->batch);
+  const int L = args->n_levels, F = args->features_per_level;
+  if (L < 1 || L > LP_HASH_MAX_LEVELS) return set_error(LP_EINVAL, "n_levels %d outside [1, %d]", L, LP_HASH_MAX_LEVELS);
+  if (F != 1 && F != 2 && F != 4 && F != 8) return set_error(LP_EUNSUPPORTED, "features_per_level %d is not one of 1, 2, 4, 8", F);
+  if (L * F > LP_MAX_WIDTH) return set_error(LP_EUNSUPPORTED, "n_levels %d x features_per_level %d = %d channels > %d", L, F, L * F, LP_MAX_WIDTH);
+  int64_t end = 0;  // of the level before
+  for (int l = 0; l < L; ++l) {
+    const int64_t n = args->resolution[l], size = args->size[l];
+    if (n < 1 || n > 65536) return set_error(LP_EINVAL, "resolution[%d] = %lld outside [1, 65536]", l, (long long)n);
+    if (args->offset[l] < end)
+      return set_error(LP_EINVAL, "offset[%d] = %lld begins before the end %lld of the level before: offsets have to increase", l,
+                       (long long)args->offset[l], (long long)end);
+    if (args->hashed[l]) {
+      if (size < 8 || size > ((int64_t)1 << 24) || (size & (size - 1)) != 0)
+        return set_error(LP_EINVAL, "size[%d] = %lld of a hashed level is not a power of two in [2^3, 2^24]", l, (long long)size);
+    } else {
+      const int64_t cube = (n + 1) * (n + 1) * (n + 1);
+      if (cube > ((int64_t)1 << 24) || size != (cube + 7) / 8 * 8)
+        return set_error(LP_EINVAL, "size[%d] = %lld of a dense level of resolution %lld is not (N + 1)^3 = %lld rounded up to a multiple of 8 (at most 2^24)",
+                         l, (long long)size, (long long)n, (long long)cube);
+    }
+    end = args->offset[l] + size;
+  }
+  if (end > args->entries) return set_error(LP_EINVAL, "entries %lld < %lld, where the last level ends", (long long)args->entries, (long long)end);
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"points", args->points, true},          {"grid_idx", args->grid_idx, true},          {"table", args->table, mode != 1},
+      {"out_features", args->out_features, mode == 0}, {"grad_features", args->grad_features, mode != 0},
+      {"grad_table", args->grad_table, mode == 1},     {"grad_points", args->grad_points, mode == 2}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
 // with the compositing): the top-level keys of the text stay as they are
 static const char* build_info_points_family() {
@@ -991,6 +1037,7 @@ int lp_abi_sizeof(int which) {
     case 26: return (int)sizeof(LpInterlevelArgs);  // (and 25)
     case 30: return (int)sizeof(LpRenderSamplesArgs);  // (and 27, 28, 29: lightplane_hip_render_samples.h)
     case 34: return (int)sizeof(LpRayGridArgs);  // (and 31, 32, 33: lightplane_hip_ray_grid.h)
+    case 38: return (int)sizeof(LpHashGridArgs);  // (and 36, 37, 39: lightplane_hip_hash_grid.h)
     default: return -1;
   }
 }
@@ -1433,6 +1480,24 @@ int lp_ray_grid_grad_samples(const LpRayGridArgs* args, void* stream) {
   const int rc = check_ray_grid("lp_ray_grid_grad_samples", args, 2, a);
   if (rc != LP_OK || a.n_rays == 0 || a.n_samples == 0) return rc;
   return ray_grid_grad_samples_launch(a, (hipStream_t)stream);
+}
+
+int lp_hash_grid_forward(const LpHashGridArgs* args, void* stream) {
+  const int rc = check_hash_grid("lp_hash_grid_forward", args, 0);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return hash_grid_forward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_hash_grid_backward_table(const LpHashGridArgs* args, void* stream) {
+  const int rc = check_hash_grid("lp_hash_grid_backward_table", args, 1);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return hash_grid_backward_table_launch(*args, (hipStream_t)stream);
+}
+
+int lp_hash_grid_backward_points(const LpHashGridArgs* args, void* stream) {
+  const int rc = check_hash_grid("lp_hash_grid_backward_points", args, 2);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return hash_grid_backward_points_launch(*args, (hipStream_t)stream);
 }
 
 int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {

@@ -9,6 +9,7 @@
 #include "../../include/lightplane_hip_losses.h"
 #include "../../include/lightplane_hip_render_samples.h"
 #include "../../include/lightplane_hip_ray_grid.h"
+#include "../../include/lightplane_hip_hash_grid.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -175,6 +176,10 @@ const char* build_info_render_samples();
 int ray_grid_splat_launch(const LpRayGridArgs& a, hipStream_t stream);
 int ray_grid_gather_launch(const LpRayGridArgs& a, hipStream_t stream);
 int ray_grid_grad_samples_launch(const LpRayGridArgs& a, hipStream_t stream);
+// multiresolution hash-grid encoding of points: lp_hash_grid.hip (`a` checked by lp_api.hip; n_rays * n_pts > 0)
+int hash_grid_forward_launch(const LpHashGridArgs& a, hipStream_t stream);
+int hash_grid_backward_table_launch(const LpHashGridArgs& a, hipStream_t stream);
+int hash_grid_backward_points_launch(const LpHashGridArgs& a, hipStream_t stream);
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 
