@@ -11,6 +11,8 @@ GPU boxes have no datasets.
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
                                             [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0] [--modular]
                                             [--importance N] [--distortion-weight W] [--render-samples]
+                                            [--hash-grid] [--hash-levels 8] [--hash-features 2] [--hash-log2-size 15]
+                                            [--hash-base-res 4] [--hash-finest-res 64]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
 planes' ``.grad`` by one fused sweep after ``loss.backward()`` (``lp.add_grid_tv_grad_``); 0 leaves the run as it is without it.
@@ -60,6 +62,12 @@ hands back -- one fused kernel, with gradients through the weights into the deco
 ``renderer.render_samples`` (``lp.render_samples``): the decoder and the compositing in one launch at the samples' depths, with no
 points, opacity or colour tensor in between; the distortion loss then reads the weights that op hands back (the JSON line gains
 ``render_samples``).  The coarse pass of ``--importance`` stays on the chain.
+
+``--hash-grid`` (with ``--modular``) fits another student: a multiresolution hash table (``lp.hash_grid_layout`` from the
+``--hash-*`` flags, ``lp.init_hash_grid``) and a 2/2/2 x 32 decoder of ``lp.init_decoder_params``, rendered through
+``lp.ray_samples -> lp.hash_grid_eval_mlp -> lp.composite_samples`` -- encoding and decoder in one launch, no feature tensor --
+with a zero ray encoding (the scene's colours do not depend on the direction).  Training and held-out evaluation use that path;
+the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -245,6 +253,46 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     return out
 
 
+def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, **layout):
+    """the fit of ``fit`` with a hash table + decoder as the student, through ray_samples -> hash_grid_eval_mlp -> composite_samples"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    lay = lp.hash_grid_layout(**layout)
+    table = torch.nn.Parameter(lp.init_hash_grid(lay, 1, device=dev))
+    dec = lp.init_decoder_params(dev, 2, 2, 2, input_chn=lay.channels, hidden_chn=32, color_chn=3, opacity_init_bias=-2.0)
+    params = torch.nn.Parameter(dec.mlp_params)
+    dec = lp.DecoderParams(params, dec.n_hidden_trunk, dec.n_hidden_opacity, dec.n_hidden_color, dec.color_chn)
+    opt = torch.optim.Adam([{"params": [table], "lr": 3e-2}, {"params": [params], "lr": 3e-3}])
+
+    def render(rays):
+        samples = lp.ray_samples(rays, num_samples)
+        enc = torch.zeros(rays.directions.shape[0], 32, device=dev)
+        opacity, color = lp.hash_grid_eval_mlp(samples.points, table, rays.grid_idx, lay, dec, enc, 1.0)
+        _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
+        return 1.0 - torch.exp(-nlt), rgb
+
+    losses = []
+    for it in range(steps):
+        rays = random_rays(n_rays, gen, dev)
+        with torch.no_grad():
+            tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
+        alpha, rgb = render(rays)
+        loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        if verbose and (it % 50 == 0 or it == steps - 1):
+            print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
+    rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
+    with torch.no_grad():
+        tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
+        psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
+    return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
+            "rays_per_step": n_rays, "modular": True, "hash_grid": True, "hash_layout": dict(layout), "table_entries": lay.entries}
+
+
 def write_ply(path, vertices, faces, normals, colors):
     """ASCII PLY: ``x y z nx ny nz red green blue`` per vertex (colours as 8-bit), ``3 i j k`` per face"""
     rgb = np.clip(np.rint(colors[:, :3] * 255.0), 0, 255).astype(np.int64)
@@ -304,7 +352,20 @@ def main(argv=None):
                     help="with --modular: the fitted march through render_samples (decoder + compositing in one launch at the samples' depths)")
     ap.add_argument("--distortion-weight", type=float, default=0.0,
                     help="with --modular: weight of the distortion loss of the fitted march (distortion_loss); 0 = none")
+    ap.add_argument("--hash-grid", action="store_true",
+                    help="with --modular: fit a hash table + decoder through ray_samples -> hash_grid_eval_mlp -> composite_samples")
+    ap.add_argument("--hash-levels", type=int, default=8)
+    ap.add_argument("--hash-features", type=int, default=2)
+    ap.add_argument("--hash-log2-size", type=int, default=15)
+    ap.add_argument("--hash-base-res", type=int, default=4)
+    ap.add_argument("--hash-finest-res", type=int, default=64)
     a = ap.parse_args(argv)
+    if a.hash_grid:
+        assert a.modular, "--hash-grid renders through the modular march: pass --modular as well"
+        out = fit_hash_grid(a.steps, a.rays, verbose=True, n_levels=a.hash_levels, features_per_level=a.hash_features,
+                            log2_table_size=a.hash_log2_size, base_resolution=a.hash_base_res, finest_resolution=a.hash_finest_res)
+        print(json.dumps(out))
+        return out
     assert a.importance == 0 or a.modular, "--importance resamples the modular march: pass --modular as well"
     assert not a.render_samples or a.modular, "--render-samples runs the fitted pass of the modular march: pass --modular as well"
     assert a.distortion_weight == 0.0 or a.modular, "--distortion-weight needs the weights of the modular march: pass --modular as well"

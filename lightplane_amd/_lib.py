@@ -229,6 +229,22 @@ class LpHashGridArgs(C.Structure):  # include/lightplane_hip_hash_grid.h
     ]
 
 
+class LpHashPointsArgs(C.Structure):  # include/lightplane_hip_hash_points.h
+    _fields_ = [
+        ("table", C.c_void_p), ("grad_table", C.c_void_p), ("points", C.c_void_p), ("grid_idx", C.c_void_p),
+        ("entries", C.c_int64), ("n_rays", C.c_int64), ("n_pts", C.c_int64),
+        ("offset", C.c_int64 * LP_HASH_MAX_LEVELS), ("resolution", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("size", C.c_int32 * LP_HASH_MAX_LEVELS), ("hashed", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("batch", C.c_int32), ("features_per_level", C.c_int32), ("n_levels", C.c_int32),
+        ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("color_chn", C.c_int32),
+        ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64), ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("encoding", C.c_void_p), ("encoding_dim", C.c_int32), ("gain", C.c_float),
+        ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("opacity_out", C.c_void_p), ("color_out", C.c_void_p), ("grad_opacity", C.c_void_p), ("grad_color", C.c_void_p),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p), ("grad_points", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -271,6 +287,9 @@ RAY_GRID_EXPORTS = ("lp_ray_grid_splat", "lp_ray_grid_gather", "lp_ray_grid_grad
 
 #: every symbol include/lightplane_hip_hash_grid.h declares (and again)
 HASH_GRID_EXPORTS = ("lp_hash_grid_forward", "lp_hash_grid_backward_table", "lp_hash_grid_backward_points")
+
+#: every symbol include/lightplane_hip_hash_points.h declares (and again)
+HASH_POINTS_EXPORTS = ("lp_hash_points_forward", "lp_hash_points_backward")
 
 
 def _signatures():
@@ -330,6 +349,8 @@ def _signatures():
         (RAY_GRID_EXPORTS, C.c_int, (P(LpRayGridArgs), vp)),
         # multiresolution hash-grid encoding of points (include/lightplane_hip_hash_grid.h): args, stream
         (HASH_GRID_EXPORTS, C.c_int, (P(LpHashGridArgs), vp)),
+        # the decoder on a hash grid at points (include/lightplane_hip_hash_points.h): args, stream
+        (HASH_POINTS_EXPORTS, C.c_int, (P(LpHashPointsArgs), vp)),
     )
 
 
@@ -364,7 +385,8 @@ def lib() -> C.CDLL:
                       (24, LpDistortionArgs), (26, LpInterlevelArgs),  # (nor 25 and 27: lightplane_hip_losses.h)
                       (30, LpRenderSamplesArgs),  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
                       (34, LpRayGridArgs),  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
-                      (38, LpHashGridArgs)):  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
+                      (38, LpHashGridArgs),  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
+                      (42, LpHashPointsArgs)):  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

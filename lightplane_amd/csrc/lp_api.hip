@@ -926,18 +926,11 @@ static int check_ray_grid(const char* what, const LpRayGridArgs* args, int mode,
   return LP_OK;
 }
 
-// everything the three lp_hash_grid_* entry points check.  mode: 0 forward, 1 backward_table, 2 backward_points.  Messages begin with
-// the field where a field is at fault.  The layout is held to the rules of lightplane_hip_hash_grid.h: the kernels index with it.
-static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mode) {
+// the batch and the layout of a hash grid, held to the rules of lightplane_hip_hash_grid.h: the kernels index with them.  For the
+// lp_hash_grid_* entry points and, through a copy of these fields, for lp_hash_points_*.
+static int check_hash_layout(const char* what, const LpHashGridArgs& g) {
+  const LpHashGridArgs* args = &g;
   int rc;
-  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
-  LP_ALIGNED(*args, table);
-  LP_ALIGNED(*args, grad_table);
-  LP_ALIGNED(*args, points);
-  LP_ALIGNED(*args, grid_idx);
-  LP_ALIGNED(*args, out_features);
-  LP_ALIGNED(*args, grad_features);
-  LP_ALIGNED(*args, grad_points);
   if ((rc = check_point_batch(what, args->n_rays, args->n_pts, true))) return rc;
   if (args->batch < 1) return set_error(LP_EINVAL, "batch %d < 1", args->batch);
   const int L = args->n_levels, F = args->features_per_level;
@@ -963,12 +956,73 @@ static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mod
     end = args->offset[l] + size;
   }
   if (end > args->entries) return set_error(LP_EINVAL, "entries %lld < %lld, where the last level ends", (long long)args->entries, (long long)end);
+  return LP_OK;
+}
+
+// everything the three lp_hash_grid_* entry points check.  mode: 0 forward, 1 backward_table, 2 backward_points.  Messages begin with
+// the field where a field is at fault.  The layout is held to the rules of lightplane_hip_hash_grid.h: the kernels index with it.
+static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mode) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, table);
+  LP_ALIGNED(*args, grad_table);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_features);
+  LP_ALIGNED(*args, grad_points);
+  if ((rc = check_hash_layout(what, *args))) return rc;
   const struct { const char* field; const void* p; bool needed; } ptrs[] = {
       {"points", args->points, true},          {"grid_idx", args->grid_idx, true},          {"table", args->table, mode != 1},
       {"out_features", args->out_features, mode == 0}, {"grad_features", args->grad_features, mode != 0},
       {"grad_table", args->grad_table, mode == 1},     {"grad_points", args->grad_points, mode == 2}};
   for (const auto& f : ptrs)
     if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
+// everything lp_hash_points_forward / lp_hash_points_backward check.  `color`: the colour head takes part (forward: color_out given;
+// backward: grad_color given) -- only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
+static int check_hash_points(const char* what, const LpHashPointsArgs* args, bool backward) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_color != nullptr : args->color_out != nullptr;
+  LP_ALIGNED(*args, table);
+  LP_ALIGNED(*args, grad_table);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, opacity_out);
+  LP_ALIGNED(*args, color_out);
+  LP_ALIGNED(*args, grad_opacity);
+  LP_ALIGNED(*args, grad_color);
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  LP_ALIGNED(*args, grad_points);
+  const LpHashGridArgs g = hash_points_view(*args);  // the layout fields, for the one place that judges them
+  if ((rc = check_hash_layout(what, g))) return rc;
+  const int C = args->n_levels * args->features_per_level;
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, C, args->trunk, args->opacity, head_in))) return rc;
+  const int64_t n_to = mlp_numel(args->trunk) + mlp_numel(args->opacity);
+  if ((rc = check_color_head(what, args->color, head_in, n_to, color, args->color_chn, args->encoding_dim))) return rc;
+  if ((rc = check_param_count(what, n_to + mlp_numel(args->color), args->n_mlp_params, false))) return rc;
+  if (args->scaffold) {
+    if ((rc = check_shape(what, "scaffold", args->scaffold_shape))) return rc;
+    if (args->scaffold_shape.B != args->batch)
+      return set_error(LP_EINVAL, "scaffold_shape: batch %d != batch %d of the table", args->scaffold_shape.B, args->batch);
+  }
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"table", args->table, true},   {"points", args->points, true},     {"grid_idx", args->grid_idx, true},
+      {"mlp_params", args->mlp_params, true}, {"encoding", args->encoding, color}, {"opacity_out", args->opacity_out, !backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  if (backward) {
+    const int total = hash_points_backward_total_width(*args);
+    if (total > 1024) return set_error(LP_EUNSUPPORTED, "%s: sum of layer widths %d exceeds 1024", what, total);
+  }
   return LP_OK;
 }
 
@@ -1038,6 +1092,7 @@ int lp_abi_sizeof(int which) {
     case 30: return (int)sizeof(LpRenderSamplesArgs);  // (and 27, 28, 29: lightplane_hip_render_samples.h)
     case 34: return (int)sizeof(LpRayGridArgs);  // (and 31, 32, 33: lightplane_hip_ray_grid.h)
     case 38: return (int)sizeof(LpHashGridArgs);  // (and 36, 37, 39: lightplane_hip_hash_grid.h)
+    case 42: return (int)sizeof(LpHashPointsArgs);  // (and 40, 41, 43: lightplane_hip_hash_points.h)
     default: return -1;
   }
 }
@@ -1498,6 +1553,18 @@ int lp_hash_grid_backward_points(const LpHashGridArgs* args, void* stream) {
   const int rc = check_hash_grid("lp_hash_grid_backward_points", args, 2);
   if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
   return hash_grid_backward_points_launch(*args, (hipStream_t)stream);
+}
+
+int lp_hash_points_forward(const LpHashPointsArgs* args, void* stream) {
+  const int rc = check_hash_points("lp_hash_points_forward", args, false);
+  if (rc != LP_OK) return rc;
+  return hash_points_forward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_hash_points_backward(const LpHashPointsArgs* args, void* stream) {
+  const int rc = check_hash_points("lp_hash_points_backward", args, true);
+  if (rc != LP_OK) return rc;
+  return hash_points_backward_launch(*args, (hipStream_t)stream);
 }
 
 int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {

@@ -43,16 +43,14 @@ LP_DEV void dense_any(const float* W, const float* b, int d_in, int ldw, int n_o
     dense(W, b, d_in, ldw, n_out, x, y, relu);
 }
 
-LP_DEV float decode(const GenArgs& ga, const Ray& ray, float x, float y, float z,
-                    const float* enc, float* act, float* Xs, int lane) {
+// The decoder behind the gather: act[p.x0 ..] (and act[p.cx0 ..] of a two-grid decoder) hold the features -- a caller that has no grid-list
+// (the hash grid of lp_hash_points.hip) fills them itself.
+LP_DEV float decode_gathered(const GenArgs& ga, const float* enc, float* act, float* Xs, int lane) {
   const LpRendererArgs& a = ga.a;
   const GenPlan& p = ga.p;
-  const bool mask = a.march.mask_out_of_bounds != 0;
   const bool two_grids = a.color_grid.n_grids > 0;
   const int C = a.grid.channels;
-  sample_list(a.grid, ray.b, x, y, z, mask, act + p.x0);
   if (two_grids) {
-    sample_list(a.color_grid, ray.b, x, y, z, mask, act + p.cx0);
     for (int c = 0; c < C; ++c) {
       act[p.op_in + c] = fmaxf(act[p.x0 + c], 0.0f);
       act[p.col_in + c] = fmaxf(act[p.cx0 + c], 0.0f) + enc[c];
@@ -110,13 +108,21 @@ LP_DEV float decode(const GenArgs& ga, const Ray& ray, float x, float y, float z
   return act[p.op[a.opacity.n_layers - 1]];
 }
 
+LP_DEV float decode(const GenArgs& ga, const Ray& ray, float x, float y, float z,
+                    const float* enc, float* act, float* Xs, int lane) {
+  const LpRendererArgs& a = ga.a;
+  const bool mask = a.march.mask_out_of_bounds != 0;
+  sample_list(a.grid, ray.b, x, y, z, mask, act + ga.p.x0);
+  if (a.color_grid.n_grids > 0) sample_list(a.color_grid, ray.b, x, y, z, mask, act + ga.p.cx0);
+  return decode_gathered(ga, enc, act, Xs, lane);
+}
+
 // The same without the colour branch (the point-evaluation backward without a colour gradient): grid-list -> trunk -> opacity head.
 // The colour grid-list is not sampled and the colour head not evaluated; act[] holds nothing for them.
-LP_DEV float decode_opacity(const GenArgs& ga, const Ray& ray, float x, float y, float z, float* act, float* Xs, int lane) {
+LP_DEV float decode_opacity_gathered(const GenArgs& ga, float* act, float* Xs, int lane) {
   const LpRendererArgs& a = ga.a;
   const GenPlan& p = ga.p;
   const int C = a.grid.channels;
-  sample_list(a.grid, ray.b, x, y, z, a.march.mask_out_of_bounds != 0, act + p.x0);
   const float* cur = act + p.x0;
   for (int l = 0; l < a.trunk.n_layers; ++l) {
     dense_any(mlp_w(a.mlp_params, a.trunk, l), mlp_b(a.mlp_params, a.trunk, l), a.trunk.dims[l], a.trunk.dims[l + 1],
@@ -135,6 +141,11 @@ LP_DEV float decode_opacity(const GenArgs& ga, const Ray& ray, float x, float y,
     cur = act + p.op[l];
   }
   return act[p.op[m.n_layers - 1]];
+}
+
+LP_DEV float decode_opacity(const GenArgs& ga, const Ray& ray, float x, float y, float z, float* act, float* Xs, int lane) {
+  sample_list(ga.a.grid, ray.b, x, y, z, ga.a.march.mask_out_of_bounds != 0, act + ga.p.x0);
+  return decode_opacity_gathered(ga, act, Xs, lane);
 }
 
 inline int make_plan(const LpRendererArgs& a, GenPlan& p) {
@@ -167,6 +178,35 @@ inline int generic_stage_ld(const LpRendererArgs& a) {
   for (const LpMlp* m : ms)
     for (int l = 0; l <= m->n_layers && m->n_layers > 0; ++l) maxw = m->dims[l] > maxw ? m->dims[l] : maxw;
   return maxw + 1;
+}
+
+// grad_encoding[ray] += sum of dx over the ray's points inside this tile.  The lanes' dx go through the tile Xs[64][ld]; then lanes =
+// channels walk the tile's rows, which are consecutive points, and add a run's sum when the ray changes: (rays in the tile) x E atomics
+// instead of 64 x E on a handful of addresses.  first: the tile's first point; rows: its points inside the array.  Wave-uniform.
+LP_DEV void encoding_grad_wave(float* genc, int E, const float* dx, bool live, int64_t first, int64_t n_pts, int rows, float* Xs, int ld,
+                               int lane) {
+  stage(Xs, ld, lane, dx, E, !live);
+  __syncthreads();
+  const int64_t r0 = first / n_pts;
+  const int64_t rem0 = first - r0 * n_pts;
+  for (int c = lane; c < E; c += 64) {
+    float sum = 0.0f;
+    int64_t r = r0, rem = rem0;
+    bool pending = false;
+    for (int row = 0; row < rows; ++row) {
+      sum += Xs[row * ld + c];
+      pending = true;
+      if (++rem == n_pts) {
+        atomic_add_f32(genc + r * E + c, sum);
+        sum = 0.0f;
+        rem = 0;
+        ++r;
+        pending = false;
+      }
+    }
+    if (pending) atomic_add_f32(genc + r * E + c, sum);
+  }
+  __syncthreads();
 }
 
 }  // namespace lp

@@ -10,6 +10,7 @@
 #include "../../include/lightplane_hip_render_samples.h"
 #include "../../include/lightplane_hip_ray_grid.h"
 #include "../../include/lightplane_hip_hash_grid.h"
+#include "../../include/lightplane_hip_hash_points.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -180,6 +181,11 @@ int ray_grid_grad_samples_launch(const LpRayGridArgs& a, hipStream_t stream);
 int hash_grid_forward_launch(const LpHashGridArgs& a, hipStream_t stream);
 int hash_grid_backward_table_launch(const LpHashGridArgs& a, hipStream_t stream);
 int hash_grid_backward_points_launch(const LpHashGridArgs& a, hipStream_t stream);
+// the decoder on a hash grid at points, encoding and decoder in one launch: lp_hash_points.hip (`a` checked by lp_api.hip)
+int hash_points_forward_launch(const LpHashPointsArgs& a, hipStream_t stream);
+int hash_points_backward_launch(const LpHashPointsArgs& a, hipStream_t stream);
+LpHashGridArgs hash_points_view(const LpHashPointsArgs& a);       // its layout, table, points and flags as an LpHashGridArgs
+int hash_points_backward_total_width(const LpHashPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

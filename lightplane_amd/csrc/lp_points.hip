@@ -115,35 +115,6 @@ struct PtBwdArgs {
   int32_t color;            // the colour head takes part
 };
 
-// grad_encoding[ray] += sum of dx over the ray's points inside this tile.  The lanes' dx go through the tile Xs[64][ld]; then lanes =
-// channels walk the tile's rows, which are consecutive points, and add a run's sum when the ray changes: (rays in the tile) x E atomics
-// instead of 64 x E on a handful of addresses.  first: the tile's first point; rows: its points inside the array.  Wave-uniform.
-LP_DEV void encoding_grad_wave(float* genc, int E, const float* dx, bool live, int64_t first, int64_t n_pts, int rows, float* Xs, int ld,
-                               int lane) {
-  stage(Xs, ld, lane, dx, E, !live);
-  __syncthreads();
-  const int64_t r0 = first / n_pts;
-  const int64_t rem0 = first - r0 * n_pts;
-  for (int c = lane; c < E; c += 64) {
-    float sum = 0.0f;
-    int64_t r = r0, rem = rem0;
-    bool pending = false;
-    for (int row = 0; row < rows; ++row) {
-      sum += Xs[row * ld + c];
-      pending = true;
-      if (++rem == n_pts) {
-        atomic_add_f32(genc + r * E + c, sum);
-        sum = 0.0f;
-        rem = 0;
-        ++r;
-        pending = false;
-      }
-    }
-    if (pending) atomic_add_f32(genc + r * E + c, sum);
-  }
-  __syncthreads();
-}
-
 template <int ACT_CAP, bool LDS_ACC>
 __global__ void __launch_bounds__(64) points_bwd(const PtBwdArgs s) {
   extern __shared__ __attribute__((aligned(16))) float lds[];

@@ -18,6 +18,17 @@ and all gradients exactly 0.  Per axis ``x = clamp((q + 1) / 2, 0, 1) N_l``, ``i
 ``ray_grid_idx``.  fp32 coordinates limit a level's interpolation weights to about ``N_l * 2^-24`` cells.  The table gradient is
 accumulated with fp32 atomics (values and point gradients are bit-reproducible).  No host synchronisation (graph-capturable); there is
 no double backward and no CPU path.
+
+``hash_grid_eval_mlp`` / ``hash_grid_eval_mlp_opacity_only`` (``csrc/lp_hash_points.hip``; C ABI ``lp_hash_points_forward`` /
+``lp_hash_points_backward``) evaluate the decoder of ``lightplane_eval_mlp`` on this encoding in ONE launch, so that the features
+``[n_rays, n_pts, L F]`` and their gradient never reach memory: ``ray_samples -> hash_grid_eval_mlp -> composite_samples`` is a
+hash-grid renderer.  With ``feat`` the encoding above::
+
+    t = relu(trunk(feat)) (relu(feat) without trunk layers);  raw = opacity_mlp(t);  craw = color_mlp(t + rays_encoding[r])
+    opacity = gain * softplus(raw) * occ;   colour = sigmoid(craw)[:color_chn] * occ;   occ = scaffold at q (1 without a scaffold)
+
+Gradients go to ``table``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``; the backward recomputes every point and
+reads nothing the forward wrote.
 """
 from __future__ import annotations
 
@@ -27,8 +38,10 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
+from .params import DecoderParams, int_list_of
 
-__all__ = ["HashGridLayout", "hash_grid_layout", "init_hash_grid", "hash_grid_encode"]
+__all__ = ["HashGridLayout", "hash_grid_layout", "init_hash_grid", "hash_grid_encode", "hash_grid_eval_mlp",
+           "hash_grid_eval_mlp_opacity_only"]
 
 
 class HashGridLayout(NamedTuple):
@@ -80,9 +93,10 @@ class _Cfg(NamedTuple):
     contract: bool
 
 
-def _args(cfg: _Cfg, points, grid_idx, batch: int) -> _lib.LpHashGridArgs:
+def _args(cfg: _Cfg, points, grid_idx, batch: int, a=None):
+    """the layout, the points and the flags in ``a`` (a fresh ``LpHashGridArgs`` by default)"""
     lay = cfg.layout
-    a = _lib.LpHashGridArgs()
+    a = _lib.LpHashGridArgs() if a is None else a
     a.points, a.grid_idx = _lib.ptr(points), _lib.ptr(grid_idx)
     a.n_rays, a.n_pts = points.shape[0], points.shape[1]
     a.batch, a.entries = batch, lay.entries
@@ -146,11 +160,8 @@ class _HashGridEncode(torch.autograd.Function):
         return None, d_points, d_table, None
 
 
-def hash_grid_encode(points, table, ray_grid_idx, layout: HashGridLayout, *, mask_out_of_bounds_samples: bool = False,
-                     contract_coords: bool = False) -> torch.Tensor:
-    """``features [n_rays, n_pts, L F]``: the hash-grid encoding (module docstring) of ``points [n_rays, n_pts, 3]`` with the
-    ``table [B, layout.entries, F]`` of ``init_hash_grid``; ``ray_grid_idx [n_rays]`` (any integer dtype): the scene of each row's
-    points.  Differentiable with respect to ``table`` and ``points``."""
+def _check_inputs(points, table, ray_grid_idx, layout) -> None:
+    """what every front-end of this module asks of its points, table, ray_grid_idx and layout (before any device is touched)"""
     assert torch.is_tensor(points) and points.ndim == 3 and points.shape[-1] == 3, "points has to be a [n_rays, n_pts, 3] tensor"
     n_rays = points.shape[0]
     assert torch.is_tensor(ray_grid_idx) and tuple(ray_grid_idx.shape) == (n_rays,), f"ray_grid_idx has to be a [{n_rays}] tensor"
@@ -162,8 +173,141 @@ def hash_grid_encode(points, table, ray_grid_idx, layout: HashGridLayout, *, mas
     if not torch.is_tensor(table) or table.ndim != 3 or table.shape[0] < 1 or tuple(table.shape[1:]) != (layout.entries, layout.features_per_level):
         shape = tuple(table.shape) if torch.is_tensor(table) else type(table).__name__
         raise ValueError(f"table has to be a [B, {layout.entries}, {layout.features_per_level}] tensor for this layout (got {shape})")
+
+
+def hash_grid_encode(points, table, ray_grid_idx, layout: HashGridLayout, *, mask_out_of_bounds_samples: bool = False,
+                     contract_coords: bool = False) -> torch.Tensor:
+    """``features [n_rays, n_pts, L F]``: the hash-grid encoding (module docstring) of ``points [n_rays, n_pts, 3]`` with the
+    ``table [B, layout.entries, F]`` of ``init_hash_grid``; ``ray_grid_idx [n_rays]`` (any integer dtype): the scene of each row's
+    points.  Differentiable with respect to ``table`` and ``points``."""
+    _check_inputs(points, table, ray_grid_idx, layout)
     _lib.check_tensors(points.device, {"points": points, "table": table}, {"ray_grid_idx": ray_grid_idx})
     _lib.current_stream(points.device)  # (raises for anything but a GPU: there is no CPU path)
     grid_idx = _lib.int32_index(ray_grid_idx)
     cfg = _Cfg(layout, bool(mask_out_of_bounds_samples), bool(contract_coords))
     return _HashGridEncode.apply(cfg, points, table, grid_idx)
+
+
+class _EvalCfg(NamedTuple):
+    hash: _Cfg
+    dims_t: tuple
+    dims_o: tuple
+    dims_c: tuple
+    color_chn: int
+    gain: float
+    opacity_only: bool
+
+
+def _eval_args(cfg: _EvalCfg, points, table, mlp_params, encoding, grid_idx, scaffold, with_color: bool) -> _lib.LpHashPointsArgs:
+    a = _args(cfg.hash, points, grid_idx, table.shape[0], _lib.LpHashPointsArgs())
+    a.table = _lib.ptr(table)
+    a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
+    _lib.make_decoder(a, cfg.dims_t, cfg.dims_o, cfg.dims_c)
+    a.color_chn, a.gain = cfg.color_chn, cfg.gain
+    if with_color:
+        a.encoding, a.encoding_dim = _lib.ptr(encoding), encoding.shape[1]
+    if scaffold is not None:
+        a.scaffold = _lib.ptr(scaffold)
+        a.scaffold_shape = _lib.LpGrid(*[int(v) for v in scaffold.shape], 0, None)
+    return a
+
+
+class _HashGridEval(torch.autograd.Function):
+    """(opacity[, colour]) = decoder(encode(points, table)): one forward launch; the backward is one launch that recomputes every
+    point and fills the gradients ``needs_input_grad`` asks for (a gradient nobody asks for is a NULL pointer: its work is skipped;
+    without an upstream gradient for the colour, the colour head is not evaluated)."""
+
+    @staticmethod
+    def forward(ctx, cfg: _EvalCfg, points, table, mlp_params, encoding, grid_idx, scaffold):
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        points, table = _lib.aligned(points.contiguous()), _lib.aligned(table.contiguous(), grid=True)
+        mlp_params = _lib.aligned(mlp_params.contiguous())
+        encoding = None if encoding is None else _lib.aligned(encoding.contiguous())
+        n_rays, n_pts = points.shape[0], points.shape[1]
+        with torch.cuda.device(dev):
+            opacity = torch.empty(n_rays, n_pts, device=dev, dtype=torch.float32)
+            color = None if cfg.opacity_only else torch.empty(n_rays, n_pts, cfg.color_chn, device=dev, dtype=torch.float32)
+            a = _eval_args(cfg, points, table, mlp_params, encoding, grid_idx, scaffold, not cfg.opacity_only)
+            a.opacity_out, a.color_out = _lib.ptr(opacity), _lib.ptr(color)
+            if opacity.numel():  # (an empty batch has no tensors to point at)
+                _call("lp_hash_points_forward", a, stream)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(points, table, mlp_params, encoding, grid_idx, scaffold)
+        return opacity if cfg.opacity_only else (opacity, color)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_opacity, g_color=None):
+        cfg: _EvalCfg = ctx.cfg
+        points, table, mlp_params, encoding, grid_idx, scaffold = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if (g_opacity is None and g_color is None) or not any(need):
+            return (None,) * 7
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        with_color = g_color is not None and not cfg.opacity_only
+        g_opacity = None if g_opacity is None else _lib.aligned(g_opacity.to(torch.float32).contiguous())
+        g_color = _lib.aligned(g_color.to(torch.float32).contiguous()) if with_color else None
+        with torch.cuda.device(dev):
+            d_points = torch.empty_like(points) if need[1] else None
+            d_table = torch.zeros_like(table) if need[2] else None
+            d_params = torch.zeros_like(mlp_params) if need[3] else None
+            d_enc = torch.zeros_like(encoding) if (need[4] and encoding is not None) else None
+            a = _eval_args(cfg, points, table, mlp_params, encoding, grid_idx, scaffold, with_color)
+            a.grad_opacity, a.grad_color = _lib.ptr(g_opacity), _lib.ptr(g_color)
+            a.grad_points, a.grad_table, a.grad_mlp_params = _lib.ptr(d_points), _lib.ptr(d_table), _lib.ptr(d_params)
+            a.grad_encoding = _lib.ptr(d_enc) if with_color else None
+            if points.numel():
+                _call("lp_hash_points_backward", a, stream)
+        return None, d_points, d_table, d_params, d_enc, None, None
+
+
+def _eval(points, table, ray_grid_idx, layout, decoder_params: DecoderParams, rays_encoding, gain, mask, contract, scaffold,
+          opacity_only: bool):
+    _check_inputs(points, table, ray_grid_idx, layout)
+    n_rays = points.shape[0]
+    dims_t, dims_o, dims_c = (tuple(int_list_of(v)) for v in (decoder_params.n_hidden_trunk, decoder_params.n_hidden_opacity,
+                                                              decoder_params.n_hidden_color))
+    width = dims_t[0] if len(dims_t) > 1 else dims_o[0]
+    if width != layout.channels:
+        raise ValueError(f"the decoder reads {width} features, the layout has n_levels x features_per_level = {layout.channels}")
+    if opacity_only:
+        rays_encoding = None
+    else:
+        assert torch.is_tensor(rays_encoding) and tuple(rays_encoding.shape) == (n_rays, dims_c[0]), (
+            f"rays_encoding has to be a [{n_rays}, {dims_c[0]}] tensor (the colour head's input width)")
+    mlp_params = decoder_params.mlp_params
+    assert mlp_params.ndim == 1, "decoder_params.mlp_params has to be the flat parameter vector"
+    if scaffold is not None:
+        assert torch.is_tensor(scaffold) and scaffold.ndim == 4, "scaffold has to be a [B, D, H, W] tensor"
+    dev = points.device
+    _lib.check_tensors(dev, {"points": points, "table": table, "decoder_params.mlp_params": mlp_params, "rays_encoding": rays_encoding,
+                             "scaffold": scaffold}, {"ray_grid_idx": ray_grid_idx})
+    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    grid_idx = _lib.int32_index(ray_grid_idx)
+    scaffold = None if scaffold is None else _lib.aligned(scaffold.detach().contiguous())
+    cfg = _EvalCfg(_Cfg(layout, bool(mask), bool(contract)), dims_t, dims_o, dims_c, int(decoder_params.color_chn), float(gain),
+                   opacity_only)
+    return _HashGridEval.apply(cfg, points, table, mlp_params, rays_encoding, grid_idx, scaffold)
+
+
+def hash_grid_eval_mlp(points, table, ray_grid_idx, layout: HashGridLayout, decoder_params: DecoderParams, rays_encoding, gain: float, *,
+                       mask_out_of_bounds_samples: bool = False, contract_coords: bool = False,
+                       scaffold: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(opacity [n_rays, n_pts], colour [n_rays, n_pts, color_chn])`` of the decoder on the hash-grid encoding of
+    ``points [n_rays, n_pts, 3]`` (module docstring), in one launch.  ``table``, ``ray_grid_idx``, ``layout``: as ``hash_grid_encode``;
+    ``decoder_params``: a decoder whose trunk (without trunk layers: whose heads) reads ``layout.channels`` features;
+    ``rays_encoding [n_rays, E]``: added to the colour head's input; ``scaffold``: ``[B, D, H, W]`` occupancy or ``None``.
+    Differentiable with respect to ``table``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``."""
+    return _eval(points, table, ray_grid_idx, layout, decoder_params, rays_encoding, gain, mask_out_of_bounds_samples, contract_coords,
+                 scaffold, False)
+
+
+def hash_grid_eval_mlp_opacity_only(points, table, ray_grid_idx, layout: HashGridLayout, decoder_params: DecoderParams, gain: float, *,
+                                    mask_out_of_bounds_samples: bool = False, contract_coords: bool = False,
+                                    scaffold: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``opacity [n_rays, n_pts]`` alone: the opacity of ``hash_grid_eval_mlp``, bit for bit, without the colour head -- there is no
+    encoding, and the colour MLP's parameters are never read (they get exactly zero gradient)."""
+    return _eval(points, table, ray_grid_idx, layout, decoder_params, None, gain, mask_out_of_bounds_samples, contract_coords, scaffold, True)
