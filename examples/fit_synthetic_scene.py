@@ -65,7 +65,9 @@ points, opacity or colour tensor in between; the distortion loss then reads the 
 
 ``--hash-grid`` (with ``--modular``) fits another student: a multiresolution hash table (``lp.hash_grid_layout`` from the
 ``--hash-*`` flags, ``lp.init_hash_grid``) and a 2/2/2 x 32 decoder of ``lp.init_decoder_params``, rendered through
-``lp.ray_samples -> lp.hash_grid_eval_mlp -> lp.composite_samples`` -- encoding and decoder in one launch, no feature tensor --
+``lp.ray_samples -> lp.hash_grid_eval_mlp -> lp.composite_samples`` -- encoding and decoder in one launch, no feature tensor -- or,
+with ``--render-samples``, through ``lp.hash_grid_render_samples``: encoding, decoder and compositing in one launch, no per-sample
+tensor at all; ``--importance N`` then adds a coarse pass that only asks for the weights (``with_color=False``) --
 with a zero ray encoding (the scene's colours do not depend on the direction).  Training and held-out evaluation use that path;
 the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
 
@@ -253,8 +255,10 @@ def fit(steps=300, n_rays=8192, num_samples=96, res=64, chn=16, seed=0, stop_tra
     return out
 
 
-def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, **layout):
-    """the fit of ``fit`` with a hash table + decoder as the student, through ray_samples -> hash_grid_eval_mlp -> composite_samples"""
+def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, fused=False, importance=0, **layout):
+    """the fit of ``fit`` with a hash table + decoder as the student, through ray_samples -> hash_grid_eval_mlp -> composite_samples or,
+    ``fused``, through ``lp.hash_grid_render_samples`` (one launch, no per-sample tensors); ``importance`` (with ``fused``): a coarse
+    pass that only asks for the weights (``with_color=False``), ``importance`` new samples from them, and the fused fine pass"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -268,8 +272,17 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
     def render(rays):
         samples = lp.ray_samples(rays, num_samples)
         enc = torch.zeros(rays.directions.shape[0], 32, device=dev)
-        opacity, color = lp.hash_grid_eval_mlp(samples.points, table, rays.grid_idx, lay, dec, enc, 1.0)
-        _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
+        if fused:
+            rays = lp.Rays(directions=rays.directions, origins=rays.origins, grid_idx=rays.grid_idx, near=rays.near, far=rays.far, encoding=enc)
+            if importance:
+                with torch.no_grad():
+                    w = lp.hash_grid_render_samples(rays, samples.depths, samples.deltas, table, lay, dec, return_weights=True,
+                                                    with_color=False)[3]
+                    samples = lp.importance_samples(rays, samples.depths, w, importance)
+            _, nlt, rgb = lp.hash_grid_render_samples(rays, samples.depths.detach(), samples.deltas.detach(), table, lay, dec)
+        else:
+            opacity, color = lp.hash_grid_eval_mlp(samples.points, table, rays.grid_idx, lay, dec, enc, 1.0)
+            _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
         return 1.0 - torch.exp(-nlt), rgb
 
     losses = []
@@ -290,7 +303,8 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
     return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
-            "rays_per_step": n_rays, "modular": True, "hash_grid": True, "hash_layout": dict(layout), "table_entries": lay.entries}
+            "rays_per_step": n_rays, "modular": True, "hash_grid": True, "hash_layout": dict(layout), "table_entries": lay.entries,
+            "render_samples": bool(fused), "importance": int(importance)}
 
 
 def write_ply(path, vertices, faces, normals, colors):
@@ -362,7 +376,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.hash_grid:
         assert a.modular, "--hash-grid renders through the modular march: pass --modular as well"
-        out = fit_hash_grid(a.steps, a.rays, verbose=True, n_levels=a.hash_levels, features_per_level=a.hash_features,
+        assert a.importance == 0 or a.render_samples, "--hash-grid --importance resamples for the fused fine pass: pass --render-samples as well"
+        out = fit_hash_grid(a.steps, a.rays, verbose=True, fused=a.render_samples, importance=a.importance, n_levels=a.hash_levels, features_per_level=a.hash_features,
                             log2_table_size=a.hash_log2_size, base_resolution=a.hash_base_res, finest_resolution=a.hash_finest_res)
         print(json.dumps(out))
         return out

@@ -245,6 +245,23 @@ class LpHashPointsArgs(C.Structure):  # include/lightplane_hip_hash_points.h
     ]
 
 
+class LpHashRenderArgs(C.Structure):  # include/lightplane_hip_hash_render.h
+    _fields_ = [
+        ("table", C.c_void_p), ("grad_table", C.c_void_p), ("entries", C.c_int64),
+        ("offset", C.c_int64 * LP_HASH_MAX_LEVELS), ("resolution", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("size", C.c_int32 * LP_HASH_MAX_LEVELS), ("hashed", C.c_int32 * LP_HASH_MAX_LEVELS),
+        ("batch", C.c_int32), ("features_per_level", C.c_int32), ("n_levels", C.c_int32),
+        ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("color_chn", C.c_int32),
+        ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64), ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("gain", C.c_float), ("encoding_dim", C.c_int32), ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("origins", C.c_void_p), ("directions", C.c_void_p), ("grid_idx", C.c_void_p), ("encoding", C.c_void_p),
+        ("depths", C.c_void_p), ("deltas", C.c_void_p), ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("reserved", C.c_int32),
+        ("ray_length", C.c_void_p), ("neg_log_t", C.c_void_p), ("feature", C.c_void_p), ("weights", C.c_void_p), ("chunk_nlt", C.c_void_p),
+        ("grad_ray_length", C.c_void_p), ("grad_neg_log_t", C.c_void_p), ("grad_feature", C.c_void_p), ("grad_weights", C.c_void_p),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -290,6 +307,9 @@ HASH_GRID_EXPORTS = ("lp_hash_grid_forward", "lp_hash_grid_backward_table", "lp_
 
 #: every symbol include/lightplane_hip_hash_points.h declares (and again)
 HASH_POINTS_EXPORTS = ("lp_hash_points_forward", "lp_hash_points_backward")
+
+#: every symbol include/lightplane_hip_hash_render.h declares (and again)
+HASH_RENDER_EXPORTS = ("lp_hash_render_forward", "lp_hash_render_backward")
 
 
 def _signatures():
@@ -351,6 +371,8 @@ def _signatures():
         (HASH_GRID_EXPORTS, C.c_int, (P(LpHashGridArgs), vp)),
         # the decoder on a hash grid at points (include/lightplane_hip_hash_points.h): args, stream
         (HASH_POINTS_EXPORTS, C.c_int, (P(LpHashPointsArgs), vp)),
+        # a hash-grid field rendered along rays at caller-given depths (include/lightplane_hip_hash_render.h): args, stream
+        (HASH_RENDER_EXPORTS, C.c_int, (P(LpHashRenderArgs), vp)),
     )
 
 
@@ -386,7 +408,8 @@ def lib() -> C.CDLL:
                       (30, LpRenderSamplesArgs),  # (nor 28, 29 and 31: lightplane_hip_render_samples.h)
                       (34, LpRayGridArgs),  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
                       (38, LpHashGridArgs),  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
-                      (42, LpHashPointsArgs)):  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
+                      (42, LpHashPointsArgs),  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
+                      (46, LpHashRenderArgs)):  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -1026,12 +1026,72 @@ static int check_hash_points(const char* what, const LpHashPointsArgs* args, boo
   return LP_OK;
 }
 
+// everything lp_hash_render_forward / lp_hash_render_backward check: the layout and the decoder as lp_hash_points_*, the batch, the
+// samples and the alignment as lp_render_samples_*.  `color`: the colour head takes part (forward: feature given; backward:
+// grad_feature given) -- only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
+static int check_hash_render(const char* what, const LpHashRenderArgs* args, bool backward) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_feature != nullptr : args->feature != nullptr;
+  LP_ALIGNED(*args, table);
+  LP_ALIGNED(*args, grad_table);
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, origins);
+  LP_ALIGNED(*args, directions);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, ray_length);
+  LP_ALIGNED(*args, neg_log_t);
+  LP_ALIGNED(*args, feature);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, chunk_nlt);
+  LP_ALIGNED(*args, grad_ray_length);
+  LP_ALIGNED(*args, grad_neg_log_t);
+  LP_ALIGNED(*args, grad_feature);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  if (args->n_samples < 1) return set_error(LP_EINVAL, "n_samples %d < 1", args->n_samples);
+  const LpHashGridArgs g = hash_render_view(*args);  // the layout fields and the batch n_rays x n_samples, for the one place that judges them
+  if ((rc = check_hash_layout(what, g))) return rc;
+  const int C = args->n_levels * args->features_per_level;
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, C, args->trunk, args->opacity, head_in))) return rc;
+  const int64_t n_to = mlp_numel(args->trunk) + mlp_numel(args->opacity);
+  if ((rc = check_color_head(what, args->color, head_in, n_to, color, args->color_chn, args->encoding_dim))) return rc;
+  if ((rc = check_param_count(what, n_to + mlp_numel(args->color), args->n_mlp_params, false))) return rc;
+  if (args->scaffold) {
+    if ((rc = check_shape(what, "scaffold", args->scaffold_shape))) return rc;
+    if (args->scaffold_shape.B != args->batch)
+      return set_error(LP_EINVAL, "scaffold_shape: batch %d != batch %d of the table", args->scaffold_shape.B, args->batch);
+  }
+  if (!args->table) return set_error(LP_ENULL, "table is NULL");
+  if (!args->mlp_params) return set_error(LP_ENULL, "mlp_params is NULL");
+  if (args->n_rays > 0) {  // (an empty batch has no tensors to point at)
+    const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+        {"origins", args->origins, true}, {"directions", args->directions, true}, {"grid_idx", args->grid_idx, true},
+        {"encoding", args->encoding, color}, {"depths", args->depths, true}, {"deltas", args->deltas, true},
+        {"chunk_nlt", args->chunk_nlt, backward}};
+    for (const auto& f : ptrs)
+      if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  }
+  if (backward) {
+    const int total = hash_render_backward_total_width(*args);
+    if (total > 1024) return set_error(LP_EUNSUPPORTED, "%s: sum of layer widths %d exceeds 1024", what, total);
+  }
+  return LP_OK;
+}
+
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
-// with the compositing): the top-level keys of the text stay as they are
+// with the compositing) and its hash-grid twin (lp_hash_render.hip): the top-level keys of the text stay as they are
 static const char* build_info_points_family() {
-  static char text[2048];
+  static char text[4096];
   const char* p = build_info_points();
-  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s}", (int)strlen(p) - 1, p, build_info_render_samples());
+  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s}", (int)strlen(p) - 1, p, build_info_render_samples(),
+           build_info_hash_render());
   return text;
 }
 
@@ -1093,6 +1153,7 @@ int lp_abi_sizeof(int which) {
     case 34: return (int)sizeof(LpRayGridArgs);  // (and 31, 32, 33: lightplane_hip_ray_grid.h)
     case 38: return (int)sizeof(LpHashGridArgs);  // (and 36, 37, 39: lightplane_hip_hash_grid.h)
     case 42: return (int)sizeof(LpHashPointsArgs);  // (and 40, 41, 43: lightplane_hip_hash_points.h)
+    case 46: return (int)sizeof(LpHashRenderArgs);  // (and 44, 45, 47: lightplane_hip_hash_render.h)
     default: return -1;
   }
 }
@@ -1565,6 +1626,18 @@ int lp_hash_points_backward(const LpHashPointsArgs* args, void* stream) {
   const int rc = check_hash_points("lp_hash_points_backward", args, true);
   if (rc != LP_OK) return rc;
   return hash_points_backward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_hash_render_forward(const LpHashRenderArgs* args, void* stream) {
+  const int rc = check_hash_render("lp_hash_render_forward", args, false);
+  if (rc || args->n_rays == 0) return rc;
+  return hash_render_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_hash_render_backward(const LpHashRenderArgs* args, void* stream) {
+  const int rc = check_hash_render("lp_hash_render_backward", args, true);
+  if (rc || args->n_rays == 0) return rc;
+  return hash_render_launch(*args, true, (hipStream_t)stream);
 }
 
 int lp_importance_samples_backward(const LpImportanceArgs* args, void* stream) {

@@ -1,6 +1,7 @@
 // lp_hash_levels.h -- a multiresolution hash grid as a lane sees it: level constants, the point's geometry, cell, entries, weights and
 // rows, one level's interpolation and point gradient, and the run merge of the table gradient.  Shared by the stand-alone encoding
-// (lp_hash_grid.hip) and the decoder on a hash grid at points (lp_hash_points.hip), which carries its layout as an LpHashGridArgs too.
+// (lp_hash_grid.hip), the decoder on a hash grid at points (lp_hash_points.hip) and the render along rays (lp_hash_render.hip), which
+// carry their layout as an LpHashGridArgs too.
 // (include/lightplane_hip_hash_grid.h holds the definition.)
 #pragma once
 #include "lp_host.h"
@@ -43,6 +44,16 @@ LP_DEV HgPoint hg_point(const LpHashGridArgs& a, int64_t p) {
   o.ray = point_ray(a.points, p, clamp_batch(a.grid_idx[r], a.batch));
   sample_point(o.ray, 0.0f, a.contract_coords != 0, o.x, o.y, o.z);
   o.inside = !(a.mask_out_of_bounds != 0 && !point_in_bounds(o.x, o.y, o.z));
+  return o;
+}
+
+// the same for a point formed in registers: (x, y, z) = sample_point(ray, depth, contract), `ray` with its batch element clamped
+// (lp_hash_render.hip: one ray per wave, so ray.b and with it every level's table base is wave-uniform)
+LP_DEV HgPoint hg_point_at(const Ray& ray, float x, float y, float z, bool mask_out_of_bounds) {
+  HgPoint o;
+  o.ray = ray;
+  o.x = x, o.y = y, o.z = z;
+  o.inside = !(mask_out_of_bounds && !point_in_bounds(x, y, z));
   return o;
 }
 
@@ -142,6 +153,30 @@ LP_DEV HgRow<F> hg_interp(const LpHashGridArgs& a, const HgPoint& pt, const HgLe
   return acc;
 }
 
+// the F features of level `lv` into out[c * STRIDE], c < F; F wave-uniform
+template <int F, int STRIDE>
+LP_DEV void hp_level_f(const LpHashGridArgs& g, const HgPoint& pt, const HgLevel& lv, float* out) {
+  const HgRow<F> v = hg_interp<F>(g, pt, lv);
+#pragma unroll
+  for (int c = 0; c < F; ++c) out[c * STRIDE] = v.v[c];
+}
+
+// every level's features into out[(l F + c) * STRIDE]: point-major, F dispatched by a wave-uniform switch
+template <int STRIDE>
+LP_DEV void hp_features(const LpHashGridArgs& g, const HgPoint& pt, float* out) {
+  const int F = g.features_per_level;
+  for (int l = 0; l < g.n_levels; ++l) {
+    const HgLevel lv = hg_level(g, l);
+    float* o = out + l * F * STRIDE;
+    switch (F) {
+      case 1: hp_level_f<1, STRIDE>(g, pt, lv, o); break;
+      case 2: hp_level_f<2, STRIDE>(g, pt, lv, o); break;
+      case 4: hp_level_f<4, STRIDE>(g, pt, lv, o); break;
+      default: hp_level_f<8, STRIDE>(g, pt, lv, o); break;
+    }
+  }
+}
+
 // (gx, gy, gz) += sum over the corners of (d w_k / d x) <table row, d> N_l / 2, d the gradient of the level's F features: 0 on a
 // clamped axis.  For a point that is `inside`.
 template <int F>
@@ -174,10 +209,8 @@ struct HgRun {
   int follow;  // lanes behind this one in its run: up to the next head, or to the end of the wave
 };
 
-LP_DEV HgRun hg_run(const HgCell& cell, int b, bool on, int lane) {
-  const uint32_t kxy = cell.x.i | (cell.y.i << 16), kz = cell.z.i;  // (vertex indices stay below 2^16)
-  const bool same = __shfl_up(kxy, 1, 64) == kxy && __shfl_up(kz, 1, 64) == kz && __shfl_up(b, 1, 64) == b &&
-                    __shfl_up((int)on, 1, 64) != 0;
+// `same`: this lane continues the run of the lane before it
+LP_DEV HgRun hg_run_of(bool same, bool on, int lane) {
   HgRun r;
   r.head = lane == 0 || !on || !same;
   const uint64_t heads = __ballot(r.head);
@@ -185,6 +218,22 @@ LP_DEV HgRun hg_run(const HgCell& cell, int b, bool on, int lane) {
   const uint64_t rest = lane < 63 ? heads >> (lane + 1) : (uint64_t)0;
   r.follow = rest != 0 ? __builtin_ctzll(rest) : 63 - lane;
   return r;
+}
+
+LP_DEV HgRun hg_run(const HgCell& cell, int b, bool on, int lane) {
+  const uint32_t kxy = cell.x.i | (cell.y.i << 16), kz = cell.z.i;  // (vertex indices stay below 2^16)
+  const bool same = __shfl_up(kxy, 1, 64) == kxy && __shfl_up(kz, 1, 64) == kz && __shfl_up(b, 1, 64) == b &&
+                    __shfl_up((int)on, 1, 64) != 0;
+  return hg_run_of(same, on, lane);
+}
+
+// a wave that holds ONE ray (lp_hash_render.hip): the lanes share the batch element, so there is no batch comparison; the three
+// shuffles are made by every lane
+LP_DEV HgRun hg_run_ray(const HgCell& cell, bool on, int lane) {
+  const uint32_t kxy = cell.x.i | (cell.y.i << 16), kz = cell.z.i;
+  const uint32_t pxy = __shfl_up(kxy, 1, 64), pz = __shfl_up(kz, 1, 64);
+  const int pon = __shfl_up((int)on, 1, 64);
+  return hg_run_of(pxy == kxy && pz == kz && pon != 0, on, lane);
 }
 
 // w_k d of this lane for the 8 corners of its cell go to `level` (the level's first float in the gradient table) with fp32 atomics.

@@ -27,29 +27,7 @@
 
 namespace lp {
 
-// the F features of level `lv` into out[c * STRIDE], c < F; F wave-uniform
-template <int F, int STRIDE>
-LP_DEV void hp_level_f(const LpHashGridArgs& g, const HgPoint& pt, const HgLevel& lv, float* out) {
-  const HgRow<F> v = hg_interp<F>(g, pt, lv);
-#pragma unroll
-  for (int c = 0; c < F; ++c) out[c * STRIDE] = v.v[c];
-}
-
-// every level's features into out[(l F + c) * STRIDE]
-template <int STRIDE>
-LP_DEV void hp_features(const LpHashGridArgs& g, const HgPoint& pt, float* out) {
-  const int F = g.features_per_level;
-  for (int l = 0; l < g.n_levels; ++l) {
-    const HgLevel lv = hg_level(g, l);
-    float* o = out + l * F * STRIDE;
-    switch (F) {
-      case 1: hp_level_f<1, STRIDE>(g, pt, lv, o); break;
-      case 2: hp_level_f<2, STRIDE>(g, pt, lv, o); break;
-      case 4: hp_level_f<4, STRIDE>(g, pt, lv, o); break;
-      default: hp_level_f<8, STRIDE>(g, pt, lv, o); break;
-    }
-  }
-}
+// (hp_features, the level loop of both kernels: lp_hash_levels.h)
 
 struct HpFwdArgs {
   LpHashGridArgs g;  // layout, table, points, grid_idx, flags

@@ -11,6 +11,7 @@
 #include "../../include/lightplane_hip_ray_grid.h"
 #include "../../include/lightplane_hip_hash_grid.h"
 #include "../../include/lightplane_hip_hash_points.h"
+#include "../../include/lightplane_hip_hash_render.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -186,6 +187,12 @@ int hash_points_forward_launch(const LpHashPointsArgs& a, hipStream_t stream);
 int hash_points_backward_launch(const LpHashPointsArgs& a, hipStream_t stream);
 LpHashGridArgs hash_points_view(const LpHashPointsArgs& a);       // its layout, table, points and flags as an LpHashGridArgs
 int hash_points_backward_total_width(const LpHashPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
+// a hash-grid field rendered along rays at caller-given depths, encoding + decoder + compositing in one launch: lp_hash_render.hip
+// (`a` checked by lp_api.hip; n_rays > 0)
+int hash_render_launch(const LpHashRenderArgs& a, bool backward, hipStream_t stream);
+LpHashGridArgs hash_render_view(const LpHashRenderArgs& a);       // its layout, table and flags as an LpHashGridArgs (n_pts = n_samples)
+int hash_render_backward_total_width(const LpHashRenderArgs& a);  // sum of the layer widths the backward keeps per sample (<= 1024)
+const char* build_info_hash_render();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -32,4 +32,28 @@ LP_DEV float wave_rscan(float x, int lane) {
   return x;
 }
 
+
+// The two helpers of the kernels that render one ray per wave at caller-given depths (lp_render_samples.hip, lp_hash_render.hip).
+// The ray of a sample_point() call: origin and direction of row r, batch element b, no near / far.
+LP_DEV Ray sample_ray(const float* origins, const float* directions, int64_t r, int b) {
+  Ray q;
+  load_ray_line(origins, directions, r, q);
+  q.near_t = q.far_t = 0.0f;
+  q.b = b;
+  return q;
+}
+
+// sum + p[0] + p[stride] + ... + p[63 * stride] in that order (LDS), the reads issued sixteen at a time: one dependent read per add
+// is 64 LDS latencies per call
+LP_DEV float column_sum(const float* p, int stride, float sum) {
+  for (int j0 = 0; j0 < 64; j0 += 16) {
+    float v[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = p[(j0 + q) * stride];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum += v[q];
+  }
+  return sum;
+}
+
 }  // namespace lp

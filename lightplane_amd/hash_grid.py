@@ -29,6 +29,14 @@ hash-grid renderer.  With ``feat`` the encoding above::
 
 Gradients go to ``table``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``; the backward recomputes every point and
 reads nothing the forward wrote.
+
+``hash_grid_render_samples`` (``csrc/lp_hash_render.hip``; C ABI ``lp_hash_render_forward`` / ``lp_hash_render_backward``) is that
+renderer in ONE launch, ``ray_samples | importance_samples -> hash_grid_render_samples``: sample ``s`` of ray ``r`` is evaluated at
+``depths[r, s] * direction + origin`` (formed in registers), decoded as ``hash_grid_eval_mlp`` decodes a point and composited as
+``composite_samples`` does.  No ``[R, S]`` tensor exists but the weights the caller asks for; autograd keeps the inputs and one
+``[R, ceil(S / 64)]`` buffer.  Gradients go to ``table``, ``decoder_params.mlp_params`` and ``rays.encoding``; ``depths``, ``deltas``,
+``rays.origins`` and ``rays.directions`` get NONE (``NotImplementedError`` if one of them requires one: ``.detach()`` it, or use the
+chain).  The forward and the encoding gradient are bit-reproducible; table and parameter gradients are accumulated with atomics.
 """
 from __future__ import annotations
 
@@ -39,9 +47,11 @@ import torch
 
 from . import _lib
 from .params import DecoderParams, int_list_of
+from .rays import Rays
+from .render_samples import chunks
 
 __all__ = ["HashGridLayout", "hash_grid_layout", "init_hash_grid", "hash_grid_encode", "hash_grid_eval_mlp",
-           "hash_grid_eval_mlp_opacity_only"]
+           "hash_grid_eval_mlp_opacity_only", "hash_grid_render_samples"]
 
 
 class HashGridLayout(NamedTuple):
@@ -168,6 +178,10 @@ def _check_inputs(points, table, ray_grid_idx, layout) -> None:
     assert not ray_grid_idx.is_floating_point() and not ray_grid_idx.is_complex() and ray_grid_idx.dtype != torch.bool, (
         "ray_grid_idx has to have an integer dtype")
     assert points.shape[0] * points.shape[1] < 1 << 31, f"points: {points.shape[0]} x {points.shape[1]} has to stay below 2^31"
+    _check_table(table, layout)
+
+
+def _check_table(table, layout) -> None:
     if not isinstance(layout, HashGridLayout):
         raise ValueError("layout has to be the HashGridLayout of hash_grid_layout()")
     if not torch.is_tensor(table) or table.ndim != 3 or table.shape[0] < 1 or tuple(table.shape[1:]) != (layout.entries, layout.features_per_level):
@@ -311,3 +325,160 @@ def hash_grid_eval_mlp_opacity_only(points, table, ray_grid_idx, layout: HashGri
     """``opacity [n_rays, n_pts]`` alone: the opacity of ``hash_grid_eval_mlp``, bit for bit, without the colour head -- there is no
     encoding, and the colour MLP's parameters are never read (they get exactly zero gradient)."""
     return _eval(points, table, ray_grid_idx, layout, decoder_params, None, gain, mask_out_of_bounds_samples, contract_coords, scaffold, True)
+
+
+class _RenderCfg(NamedTuple):
+    hash: _Cfg
+    dims_t: tuple
+    dims_o: tuple
+    dims_c: tuple
+    color_chn: int
+    gain: float
+    return_weights: bool
+    with_color: bool
+
+
+def _render_args(cfg: _RenderCfg, origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding,
+                 with_color: bool) -> _lib.LpHashRenderArgs:
+    lay = cfg.hash.layout
+    a = _lib.LpHashRenderArgs()
+    a.table, a.batch, a.entries = _lib.ptr(table), table.shape[0], lay.entries
+    a.features_per_level, a.n_levels = lay.features_per_level, lay.n_levels
+    for l in range(lay.n_levels):
+        a.resolution[l], a.offset[l], a.size[l], a.hashed[l] = lay.resolutions[l], lay.offsets[l], lay.sizes[l], int(lay.hashed[l])
+    a.mask_out_of_bounds, a.contract_coords = int(cfg.hash.mask), int(cfg.hash.contract)
+    a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
+    _lib.make_decoder(a, cfg.dims_t, cfg.dims_o, cfg.dims_c)
+    a.color_chn, a.gain = cfg.color_chn, cfg.gain
+    a.origins, a.directions, a.grid_idx = _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(grid_idx)
+    if with_color:
+        a.encoding, a.encoding_dim = _lib.ptr(encoding), encoding.shape[1]
+    a.n_rays, a.n_samples = depths.shape
+    a.depths, a.deltas = _lib.ptr(depths), _lib.ptr(deltas)
+    if scaffold is not None:
+        a.scaffold = _lib.ptr(scaffold)
+        a.scaffold_shape = _lib.LpGrid(*[int(v) for v in scaffold.shape], 0, None)
+    return a
+
+
+class _HashGridRender(torch.autograd.Function):
+    """(ray_length, -log T[, feature][, weights]) = render(depths, deltas; table, decoder, encoding): one forward launch; the backward
+    is one launch that recomputes every sample and fills the gradients ``needs_input_grad`` asks for (a gradient nobody asks for is a
+    NULL pointer: its work is skipped; a result nobody differentiated is a NULL upstream gradient).  Kept for it: the inputs and
+    ``chunk_nlt [R, ceil(S / 64)]``."""
+
+    @staticmethod
+    def forward(ctx, cfg: _RenderCfg, origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding):
+        dev = depths.device
+        stream = _lib.current_stream(dev)
+        origins, directions, depths, deltas, mlp_params = (
+            _lib.aligned(t.contiguous()) for t in (origins, directions, depths, deltas, mlp_params))
+        table = _lib.aligned(table.contiguous(), grid=True)
+        encoding = _lib.aligned(encoding.contiguous()) if cfg.with_color else None
+        n, s = depths.shape
+        with torch.cuda.device(dev):
+            length = torch.empty(n, device=dev, dtype=torch.float32)
+            nlt = torch.empty(n, device=dev, dtype=torch.float32)
+            feature = torch.empty(n, cfg.color_chn, device=dev, dtype=torch.float32) if cfg.with_color else None
+            weights = torch.empty(n, s, device=dev, dtype=torch.float32) if cfg.return_weights else None
+            chunk_nlt = torch.empty(n, chunks(s), device=dev, dtype=torch.float32)
+            a = _render_args(cfg, origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding, cfg.with_color)
+            a.ray_length, a.neg_log_t, a.feature, a.weights = (_lib.ptr(t) for t in (length, nlt, feature, weights))
+            a.chunk_nlt = _lib.ptr(chunk_nlt)
+            if n:  # (an empty batch has no tensors to point at)
+                _lib.check(_lib.lib().lp_hash_render_forward(ctypes.byref(a), stream), "lp_hash_render_forward")
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding, chunk_nlt)
+        return tuple(t for t in (length, nlt, feature, weights) if t is not None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_len, g_nlt, *rest):
+        cfg: _RenderCfg = ctx.cfg
+        origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding, chunk_nlt = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        rest = list(rest)
+        g_feat = rest.pop(0) if cfg.with_color else None
+        g_w = rest.pop(0) if cfg.return_weights else None
+        ups = (g_len, g_nlt, g_feat, g_w)
+        if all(g is None for g in ups) or not any(need):
+            return (None,) * 10
+        dev = depths.device
+        stream = _lib.current_stream(dev)
+        g_len, g_nlt, g_feat, g_w = (None if g is None else _lib.aligned(g.to(torch.float32).contiguous()) for g in ups)
+        with_color = g_feat is not None
+        with torch.cuda.device(dev):
+            d_table = torch.zeros_like(table) if need[7] else None
+            d_params = torch.zeros_like(mlp_params) if need[8] else None
+            d_enc = torch.empty_like(encoding) if (need[9] and encoding is not None) else None  # (written entirely)
+            a = _render_args(cfg, origins, directions, grid_idx, depths, deltas, scaffold, table, mlp_params, encoding, with_color)
+            a.chunk_nlt = _lib.ptr(chunk_nlt)
+            a.grad_ray_length, a.grad_neg_log_t, a.grad_feature, a.grad_weights = (_lib.ptr(g) for g in (g_len, g_nlt, g_feat, g_w))
+            a.grad_table, a.grad_mlp_params, a.grad_encoding = _lib.ptr(d_table), _lib.ptr(d_params), _lib.ptr(d_enc)
+            if d_enc is not None:
+                a.encoding_dim = encoding.shape[1]  # (without an upstream for the feature the kernel stores zeros: the row length)
+            if depths.shape[0]:
+                _lib.check(_lib.lib().lp_hash_render_backward(ctypes.byref(a), stream), "lp_hash_render_backward")
+        return None, None, None, None, None, None, None, d_table, d_params, d_enc
+
+
+def hash_grid_render_samples(rays: Rays, depths: torch.Tensor, deltas: torch.Tensor, table: torch.Tensor, layout: HashGridLayout,
+                             decoder_params: DecoderParams, *, gain: float = 1.0, mask_out_of_bounds_samples: bool = False,
+                             contract_coords: bool = False, scaffold: Optional[torch.Tensor] = None, return_weights: bool = False,
+                             with_color: bool = True):
+    """``(ray_length_render [R], negative_log_transmittance [R], feature_render [R, color_chn])`` of ``rays`` marched through the
+    hash-grid field ``table`` / ``layout`` / ``decoder_params`` at the caller's ``depths [R, S]`` with the interval lengths
+    ``deltas [R, S]`` (fp32: ``RaySamples.depths`` / ``.deltas`` of ``ray_samples`` or ``importance_samples``); with
+    ``return_weights=True`` a fourth result, the compositing weights ``w [R, S]``.  Any ``S >= 1`` with ``R * S < 2^31``.
+
+    Of ``rays`` the op reads ``origins``, ``directions``, ``grid_idx`` and ``encoding``.  ``table``, ``layout``, ``decoder_params``,
+    ``gain``, ``mask_out_of_bounds_samples``, ``contract_coords`` and ``scaffold`` mean what they mean in ``hash_grid_eval_mlp``.
+    ``with_color=False`` (the coarse / proposal pass that only wants weights): ``feature_render`` is ``None``, the colour MLP and
+    ``rays.encoding`` are never read in either direction, and the other results are the same bit for bit.  Differentiable with
+    respect to ``table``, ``decoder_params.mlp_params`` and ``rays.encoding``; ``depths``, ``deltas``, ``rays.origins`` and
+    ``rays.directions`` must not require a gradient (module docstring)."""
+    assert isinstance(rays, Rays), f"rays has to be a Rays object, got {type(rays).__name__}"
+    assert torch.is_tensor(depths) and depths.ndim == 2, "depths has to be a [n_rays, n_samples] tensor"
+    n, s = depths.shape
+    assert s >= 1, "depths has to have one sample per ray at least"
+    assert torch.is_tensor(deltas) and tuple(deltas.shape) == (n, s), f"deltas has to be a [{n}, {s}] tensor, as depths is"
+    assert n * s < 2 ** 31, f"depths: {n} rays x {s} samples: n_rays * n_samples has to stay below 2^31 (split the batch)"
+    for name, t in (("rays.origins", rays.origins), ("rays.directions", rays.directions)):
+        assert torch.is_tensor(t) and tuple(t.shape) == (n, 3), f"{name} has to be a [{n}, 3] tensor: one ray per row of depths"
+    assert torch.is_tensor(rays.grid_idx) and tuple(rays.grid_idx.shape) == (n,), f"rays.grid_idx has to be a [{n}] tensor"
+    _check_table(table, layout)
+    dims_t, dims_o, dims_c = (tuple(int_list_of(v)) for v in (decoder_params.n_hidden_trunk, decoder_params.n_hidden_opacity,
+                                                              decoder_params.n_hidden_color))
+    width = dims_t[0] if len(dims_t) > 1 else dims_o[0]
+    if width != layout.channels:
+        raise ValueError(f"the decoder reads {width} features, the layout has n_levels x features_per_level = {layout.channels}")
+    encoding = rays.encoding if with_color else None
+    if with_color:
+        assert torch.is_tensor(encoding) and tuple(encoding.shape) == (n, dims_c[0]), (
+            f"rays.encoding has to be a [{n}, {dims_c[0]}] tensor (the colour head's input width)")
+    if torch.is_grad_enabled():
+        for name, t in (("depths", depths), ("deltas", deltas), ("rays.origins", rays.origins), ("rays.directions", rays.directions)):
+            if t.requires_grad:
+                raise NotImplementedError(
+                    f"{name} requires a gradient, and hash_grid_render_samples produces none for depths, deltas, ray origins and "
+                    f"directions: pass {name}.detach(), or use the modular chain (ray_samples / importance_samples -> "
+                    "hash_grid_eval_mlp -> composite_samples), which differentiates with respect to them")
+    mlp_params = decoder_params.mlp_params
+    assert mlp_params.ndim == 1, "decoder_params.mlp_params has to be the flat parameter vector"
+    if scaffold is not None:
+        assert torch.is_tensor(scaffold) and scaffold.ndim == 4, "scaffold has to be a [B, D, H, W] tensor"
+    dev = depths.device
+    _lib.check_tensors(dev, {"depths": depths, "deltas": deltas, "rays.origins": rays.origins, "rays.directions": rays.directions,
+                             "table": table, "decoder_params.mlp_params": mlp_params, "rays.encoding": encoding, "scaffold": scaffold},
+                       {"rays.grid_idx": rays.grid_idx})
+    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    grid_idx = _lib.int32_index(rays.grid_idx)
+    scaffold = None if scaffold is None else _lib.aligned(scaffold.detach().contiguous())
+    cfg = _RenderCfg(_Cfg(layout, bool(mask_out_of_bounds_samples), bool(contract_coords)), dims_t, dims_o, dims_c,
+                     int(decoder_params.color_chn), float(gain), bool(return_weights), bool(with_color))
+    out = _HashGridRender.apply(cfg, rays.origins.detach(), rays.directions.detach(), grid_idx, depths.detach(), deltas.detach(), scaffold,
+                                table, mlp_params, encoding)
+    if with_color:
+        return out
+    return (out[0], out[1], None) + tuple(out[2:])
