@@ -262,6 +262,21 @@ class LpHashRenderArgs(C.Structure):  # include/lightplane_hip_hash_render.h
     ]
 
 
+LP_KPLANES_MAX_SCALES, LP_KPLANES_MAX_PLANES, LP_KPLANES_MAX_RESOLUTION = 8, 6, 4096
+
+
+class LpKPlanesArgs(C.Structure):  # include/lightplane_hip_kplanes.h
+    _fields_ = [
+        ("planes", C.c_void_p), ("grad_planes", C.c_void_p), ("points", C.c_void_p), ("times", C.c_void_p), ("grid_idx", C.c_void_p),
+        ("out_features", C.c_void_p), ("grad_features", C.c_void_p), ("grad_points", C.c_void_p),
+        ("rows", C.c_int64), ("n_rays", C.c_int64), ("n_pts", C.c_int64),
+        ("offset", C.c_int64 * LP_KPLANES_MAX_PLANES * LP_KPLANES_MAX_SCALES),
+        ("spatial", C.c_int32 * LP_KPLANES_MAX_SCALES), ("temporal", C.c_int32 * LP_KPLANES_MAX_SCALES),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("n_scales", C.c_int32), ("n_planes", C.c_int32),
+        ("time_per_point", C.c_int32), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -310,6 +325,9 @@ HASH_POINTS_EXPORTS = ("lp_hash_points_forward", "lp_hash_points_backward")
 
 #: every symbol include/lightplane_hip_hash_render.h declares (and again)
 HASH_RENDER_EXPORTS = ("lp_hash_render_forward", "lp_hash_render_backward")
+
+#: every symbol include/lightplane_hip_kplanes.h declares (and again)
+KPLANES_EXPORTS = ("lp_kplanes_forward", "lp_kplanes_backward_planes", "lp_kplanes_backward_points")
 
 
 def _signatures():
@@ -373,6 +391,8 @@ def _signatures():
         (HASH_POINTS_EXPORTS, C.c_int, (P(LpHashPointsArgs), vp)),
         # a hash-grid field rendered along rays at caller-given depths (include/lightplane_hip_hash_render.h): args, stream
         (HASH_RENDER_EXPORTS, C.c_int, (P(LpHashRenderArgs), vp)),
+        # space-time plane encoding of points (include/lightplane_hip_kplanes.h): args, stream
+        (KPLANES_EXPORTS, C.c_int, (P(LpKPlanesArgs), vp)),
     )
 
 
@@ -409,7 +429,8 @@ def lib() -> C.CDLL:
                       (34, LpRayGridArgs),  # (nor 32, 33 and 35: lightplane_hip_ray_grid.h)
                       (38, LpHashGridArgs),  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
                       (42, LpHashPointsArgs),  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
-                      (46, LpHashRenderArgs)):  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
+                      (46, LpHashRenderArgs),  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
+                      (50, LpKPlanesArgs)):  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

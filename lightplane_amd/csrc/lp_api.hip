@@ -981,6 +981,52 @@ static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mod
   return LP_OK;
 }
 
+// everything the three lp_kplanes_* entry points check.  mode: 0 forward, 1 backward_planes, 2 backward_points.  Messages begin with
+// the field where a field is at fault.  The layout is held to the rules of lightplane_hip_kplanes.h: the kernels index with it.
+static int check_kplanes(const char* what, const LpKPlanesArgs* args, int mode) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, grad_planes);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, times);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_features);
+  LP_ALIGNED(*args, grad_points);
+  if ((rc = check_point_batch(what, args->n_rays, args->n_pts, true))) return rc;
+  if (args->batch < 1) return set_error(LP_EINVAL, "batch %d < 1", args->batch);
+  const int S = args->n_scales, P = args->n_planes, C = args->channels;
+  if (P != 3 && P != 6) return set_error(LP_EINVAL, "n_planes %d is not 3 (static) or 6 (dynamic)", P);
+  if (P == 3 && args->times) return set_error(LP_EINVAL, "times given for a static layout (n_planes 3)");
+  if (args->time_per_point != 0 && args->time_per_point != 1) return set_error(LP_EINVAL, "time_per_point %d is not 0 or 1", args->time_per_point);
+  if (S < 1 || S > LP_KPLANES_MAX_SCALES) return set_error(LP_EINVAL, "n_scales %d outside [1, %d]", S, LP_KPLANES_MAX_SCALES);
+  if (C != 4 && C != 8 && C != 16 && C != 32 && C != 64) return set_error(LP_EUNSUPPORTED, "channels %d is not one of 4, 8, 16, 32, 64", C);
+  if (S * C > LP_MAX_WIDTH) return set_error(LP_EUNSUPPORTED, "n_scales %d x channels %d = %d channels > %d", S, C, S * C, LP_MAX_WIDTH);
+  int64_t end = 0;  // of the plane before
+  for (int s = 0; s < S; ++s) {
+    const int64_t n = args->spatial[s], m = args->temporal[s];
+    if (n < 2 || n > LP_KPLANES_MAX_RESOLUTION) return set_error(LP_EINVAL, "spatial[%d] = %lld outside [2, %d]", s, (long long)n, LP_KPLANES_MAX_RESOLUTION);
+    if (P == 6 && (m < 2 || m > LP_KPLANES_MAX_RESOLUTION))
+      return set_error(LP_EINVAL, "temporal[%d] = %lld outside [2, %d]", s, (long long)m, LP_KPLANES_MAX_RESOLUTION);
+    for (int j = 0; j < P; ++j) {
+      if (args->offset[s][j] < end)
+        return set_error(LP_EINVAL, "offset[%d][%d] = %lld begins before the end %lld of the plane before: offsets have to increase", s, j,
+                         (long long)args->offset[s][j], (long long)end);
+      end = args->offset[s][j] + n * (j < 3 ? n : m);
+    }
+  }
+  if (end > args->rows) return set_error(LP_EINVAL, "rows %lld < %lld, where the last plane ends", (long long)args->rows, (long long)end);
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"points", args->points, true},          {"grid_idx", args->grid_idx, true},          {"times", args->times, P == 6},
+      {"planes", args->planes, true},          {"out_features", args->out_features, mode == 0},
+      {"grad_features", args->grad_features, mode != 0}, {"grad_planes", args->grad_planes, mode == 1},
+      {"grad_points", args->grad_points, mode == 2}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
 // everything lp_hash_points_forward / lp_hash_points_backward check.  `color`: the colour head takes part (forward: color_out given;
 // backward: grad_color given) -- only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
 static int check_hash_points(const char* what, const LpHashPointsArgs* args, bool backward) {
@@ -1086,12 +1132,13 @@ static int check_hash_render(const char* what, const LpHashRenderArgs* args, boo
 }
 
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
-// with the compositing) and its hash-grid twin (lp_hash_render.hip): the top-level keys of the text stay as they are
+// with the compositing), its hash-grid twin (lp_hash_render.hip) and the space-time plane encoding at points (lp_kplanes.hip): the
+// top-level keys of the text stay as they are
 static const char* build_info_points_family() {
   static char text[4096];
   const char* p = build_info_points();
-  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s}", (int)strlen(p) - 1, p, build_info_render_samples(),
-           build_info_hash_render());
+  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s}", (int)strlen(p) - 1, p,
+           build_info_render_samples(), build_info_hash_render(), build_info_kplanes());
   return text;
 }
 
@@ -1154,6 +1201,7 @@ int lp_abi_sizeof(int which) {
     case 38: return (int)sizeof(LpHashGridArgs);  // (and 36, 37, 39: lightplane_hip_hash_grid.h)
     case 42: return (int)sizeof(LpHashPointsArgs);  // (and 40, 41, 43: lightplane_hip_hash_points.h)
     case 46: return (int)sizeof(LpHashRenderArgs);  // (and 44, 45, 47: lightplane_hip_hash_render.h)
+    case 50: return (int)sizeof(LpKPlanesArgs);  // (and 48, 49, 51: lightplane_hip_kplanes.h)
     default: return -1;
   }
 }
@@ -1614,6 +1662,24 @@ int lp_hash_grid_backward_points(const LpHashGridArgs* args, void* stream) {
   const int rc = check_hash_grid("lp_hash_grid_backward_points", args, 2);
   if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
   return hash_grid_backward_points_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_forward(const LpKPlanesArgs* args, void* stream) {
+  const int rc = check_kplanes("lp_kplanes_forward", args, 0);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return kplanes_forward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_backward_planes(const LpKPlanesArgs* args, void* stream) {
+  const int rc = check_kplanes("lp_kplanes_backward_planes", args, 1);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return kplanes_backward_planes_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_backward_points(const LpKPlanesArgs* args, void* stream) {
+  const int rc = check_kplanes("lp_kplanes_backward_points", args, 2);
+  if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
+  return kplanes_backward_points_launch(*args, (hipStream_t)stream);
 }
 
 int lp_hash_points_forward(const LpHashPointsArgs* args, void* stream) {

@@ -12,6 +12,7 @@
 #include "../../include/lightplane_hip_hash_grid.h"
 #include "../../include/lightplane_hip_hash_points.h"
 #include "../../include/lightplane_hip_hash_render.h"
+#include "../../include/lightplane_hip_kplanes.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -193,6 +194,11 @@ int hash_render_launch(const LpHashRenderArgs& a, bool backward, hipStream_t str
 LpHashGridArgs hash_render_view(const LpHashRenderArgs& a);       // its layout, table and flags as an LpHashGridArgs (n_pts = n_samples)
 int hash_render_backward_total_width(const LpHashRenderArgs& a);  // sum of the layer widths the backward keeps per sample (<= 1024)
 const char* build_info_hash_render();
+// space-time plane encoding of points: lp_kplanes.hip (`a` checked by lp_api.hip; n_rays * n_pts > 0)
+int kplanes_forward_launch(const LpKPlanesArgs& a, hipStream_t stream);
+int kplanes_backward_planes_launch(const LpKPlanesArgs& a, hipStream_t stream);
+int kplanes_backward_points_launch(const LpKPlanesArgs& a, hipStream_t stream);
+const char* build_info_kplanes();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

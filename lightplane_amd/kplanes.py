@@ -1,0 +1,201 @@
+"""Space-time plane encoding of 3-D points with a timestamp (the K-Planes field representation; HexPlane and, without the time planes,
+the Hadamard tri-plane are the same arithmetic), fused into HIP (``csrc/lp_kplanes.hip``; C ABI ``lp_kplanes_forward`` /
+``lp_kplanes_backward_planes`` / ``lp_kplanes_backward_points``).  It plugs into the march in pieces,
+``ray_samples -> kplanes_encode -> a decoder of the caller's -> composite_samples``, without a change to any other op.
+
+A **layout** (``kplanes_layout``) is computed here; the kernels read it as tables.  There are ``S = len(resolutions)`` scales; scale
+``s`` has ``n_s`` vertices on each of x, y and z.  ``time_resolution=None`` is the *static* variant, ``P = 3`` planes per scale in the
+order xy, xz, yz; an int or a length-``S`` tuple is the *dynamic* variant, ``P = 6``: xt, yt, zt follow, with ``m_s`` vertices on t.
+A plane over the axes ``(u, v)`` has ``n_u n_v`` vertices and vertex ``(i_u, i_v)`` is row ``i_u + n_u i_v``; all planes of all scales
+sit back to back (``offsets[s][j]`` is the first row of plane ``j`` of scale ``s``) in one ``[B, rows, C]`` fp32 tensor for ``B``
+scenes.
+
+Encoding of point ``p`` of row ``r`` (batch element ``ray_grid_idx[r]``, clamped) at time ``tau`` (``times[r]`` or ``times[r, n]``, in
+``[-1, 1]``): ``q = p`` or, with ``contract_coords``, the Renderer's contraction (into ``[-1, 1]^3``); with
+``mask_out_of_bounds_samples`` a point whose ``q`` leaves ``[-1, 1]^3`` has all features and all gradients exactly 0 (time never
+masks).  On an axis of ``n`` vertices ``x = clamp(fma(q, (n - 1) / 2, (n - 1) / 2), 0, n - 1)``, ``i = min(floor(x), n - 2)``,
+``f = x - i`` -- the same on every plane that holds the axis; ``tau`` goes through the same map with ``m_s``.  With ``v_j`` the bilinear
+value of plane ``j`` at its two coordinates (4 vertices, weights ``(1 - f | f)``), ``out[r, n, s C + c] = prod_j v_j[c]``: an
+elementwise product, scales concatenated scale-major, no normalisation.  Gradients go to ``planes`` (fp32 atomics; rows no point touches
+stay exactly 0) and to ``points`` (stored, bit-reproducible, zero on a clamped axis); ``times`` and ``ray_grid_idx`` get none.  No
+derivative divides by a plane value.  No host synchronisation (graph-capturable); there is no double backward and no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import _lib
+
+__all__ = ["KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode"]
+
+
+class KPlanesLayout(NamedTuple):
+    n_scales: int
+    n_planes: int
+    channels: int
+    spatial: Tuple[int, ...]
+    temporal: Tuple[int, ...]
+    offsets: Tuple[Tuple[int, ...], ...]
+    rows: int
+    out_channels: int
+
+
+def kplanes_layout(resolutions: Sequence[int] = (64, 128, 256, 512), time_resolution: Union[None, int, Sequence[int]] = None,
+                   channels: int = 32) -> KPlanesLayout:
+    """The layout of a plane field (module docstring): vertices per axis and the first row of every plane of every scale."""
+    spatial = tuple(int(n) for n in resolutions)
+    S, C, top = len(spatial), int(channels), _lib.LP_KPLANES_MAX_RESOLUTION
+    if not 1 <= S <= _lib.LP_KPLANES_MAX_SCALES:
+        raise ValueError(f"{S} resolutions: the number of scales has to be in [1, {_lib.LP_KPLANES_MAX_SCALES}]")
+    if C not in (4, 8, 16, 32, 64):
+        raise ValueError(f"channels {C} is not one of 4, 8, 16, 32, 64")
+    if S * C > _lib.LP_MAX_WIDTH:
+        raise ValueError(f"scales x channels = {S * C} channels > {_lib.LP_MAX_WIDTH}")
+    if time_resolution is None:
+        temporal = ()
+    elif isinstance(time_resolution, int):
+        temporal = (int(time_resolution),) * S
+    else:
+        temporal = tuple(int(m) for m in time_resolution)
+        if len(temporal) != S:
+            raise ValueError(f"time_resolution has {len(temporal)} entries for {S} scales")
+    for n in spatial + temporal:
+        if not 2 <= n <= top:
+            raise ValueError(f"resolution {n} outside [2, {top}]")
+    P = 6 if temporal else 3
+    offsets, row = [], 0
+    for s in range(S):
+        sizes = [spatial[s] * spatial[s]] * 3 + ([spatial[s] * temporal[s]] * 3 if temporal else [])
+        offsets.append(tuple(row + sum(sizes[:j]) for j in range(P)))
+        row += sum(sizes)
+    return KPlanesLayout(S, P, C, spatial, temporal, tuple(offsets), row, S * C)
+
+
+def init_kplanes(layout: KPlanesLayout, batch: int = 1, *, low: float = 0.1, high: float = 0.5, device=None,
+                 generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """A ``[batch, layout.rows, C]`` fp32 tensor: the space planes uniform in ``[low, high]``, the space-time planes 1 (the usual
+    initialisation: a fresh dynamic field equals its static part)."""
+    t = torch.rand(int(batch), layout.rows, layout.channels, device=device, dtype=torch.float32, generator=generator)
+    t.mul_(float(high) - float(low)).add_(float(low))
+    if layout.n_planes == 6:
+        for s in range(layout.n_scales):
+            t[:, layout.offsets[s][3]:layout.offsets[s][5] + layout.spatial[s] * layout.temporal[s]] = 1.0
+    return t
+
+
+class _Cfg(NamedTuple):
+    layout: KPlanesLayout
+    mask: bool
+    contract: bool
+
+
+def _args(cfg: _Cfg, points, times, grid_idx, batch: int) -> _lib.LpKPlanesArgs:
+    """the layout, the points, the timestamps and the flags in a fresh ``LpKPlanesArgs``"""
+    lay = cfg.layout
+    a = _lib.LpKPlanesArgs()
+    a.points, a.grid_idx, a.times = _lib.ptr(points), _lib.ptr(grid_idx), _lib.ptr(times)
+    a.time_per_point = int(times is not None and times.ndim == 2)
+    a.n_rays, a.n_pts = points.shape[0], points.shape[1]
+    a.batch, a.rows = batch, lay.rows
+    a.channels, a.n_scales, a.n_planes = lay.channels, lay.n_scales, lay.n_planes
+    for s in range(lay.n_scales):
+        a.spatial[s] = lay.spatial[s]
+        a.temporal[s] = lay.temporal[s] if lay.temporal else 0
+        for j in range(lay.n_planes):
+            a.offset[s][j] = lay.offsets[s][j]
+    a.mask_out_of_bounds, a.contract_coords = int(cfg.mask), int(cfg.contract)
+    return a
+
+
+def _call(name: str, a: _lib.LpKPlanesArgs, stream) -> None:
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(a), stream), name)
+
+
+class _KPlanesEncode(torch.autograd.Function):
+    """features = encode(points, times, planes): one launch, no atomics.  Backward: the run-merged atomic scatter into a zeroed twin of
+    the planes (when the planes ask) and the stored point gradient (when ``points`` asks) -- a kernel nobody asks for does not run."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, points, times, planes, grid_idx):
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        points, planes = _lib.aligned(points.contiguous()), _lib.aligned(planes.contiguous(), grid=True)
+        times = None if times is None else _lib.aligned(times.contiguous())
+        with torch.cuda.device(dev):
+            out = torch.empty(points.shape[0], points.shape[1], cfg.layout.out_channels, device=dev, dtype=torch.float32)
+            a = _args(cfg, points, times, grid_idx, planes.shape[0])
+            a.planes, a.out_features = _lib.ptr(planes), _lib.ptr(out)
+            if out.numel():  # (an empty batch has no tensors to point at)
+                _call("lp_kplanes_forward", a, stream)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(points, times, planes, grid_idx)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        cfg: _Cfg = ctx.cfg
+        points, times, planes, grid_idx = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if g_out is None or not (need[1] or need[3]):
+            return None, None, None, None, None
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        g_out = _lib.aligned(g_out.to(torch.float32).contiguous())
+        d_points, d_planes = None, None
+        with torch.cuda.device(dev):
+            a = _args(cfg, points, times, grid_idx, planes.shape[0])
+            a.planes, a.grad_features = _lib.ptr(planes), _lib.ptr(g_out)
+            if need[1]:
+                d_points = torch.empty_like(points)
+                a.grad_points = _lib.ptr(d_points)
+                if g_out.numel():
+                    _call("lp_kplanes_backward_points", a, stream)
+            if need[3]:
+                d_planes = torch.zeros_like(planes)
+                a.grad_planes = _lib.ptr(d_planes)
+                if g_out.numel():
+                    _call("lp_kplanes_backward_planes", a, stream)
+        return None, d_points, None, d_planes, None
+
+
+def _check_inputs(points, times, planes, ray_grid_idx, layout) -> None:
+    """what the op asks of its points, times, planes, ray_grid_idx and layout (before any device is touched)"""
+    if not isinstance(layout, KPlanesLayout):
+        raise ValueError("layout has to be the KPlanesLayout of kplanes_layout()")
+    assert torch.is_tensor(points) and points.ndim == 3 and points.shape[-1] == 3, "points has to be a [n_rays, n_pts, 3] tensor"
+    n_rays, n_pts = points.shape[0], points.shape[1]
+    assert torch.is_tensor(ray_grid_idx) and tuple(ray_grid_idx.shape) == (n_rays,), f"ray_grid_idx has to be a [{n_rays}] tensor"
+    assert not ray_grid_idx.is_floating_point() and not ray_grid_idx.is_complex() and ray_grid_idx.dtype != torch.bool, (
+        "ray_grid_idx has to have an integer dtype")
+    assert n_rays * n_pts < 1 << 31, f"points: {n_rays} x {n_pts} has to stay below 2^31"
+    if layout.n_planes == 3:
+        if times is not None:
+            raise ValueError("times has to be None for a static layout (time_resolution=None)")
+    else:
+        if not torch.is_tensor(times):
+            raise ValueError("times has to be a tensor for a dynamic layout (one timestamp per row, or one per point)")
+        assert tuple(times.shape) in ((n_rays,), (n_rays, n_pts)), f"times has to be a [{n_rays}] or a [{n_rays}, {n_pts}] tensor"
+        if times.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("times requires a gradient, and kplanes_encode produces none for the timestamps: pass times.detach()")
+    if not torch.is_tensor(planes) or planes.ndim != 3 or planes.shape[0] < 1 or tuple(planes.shape[1:]) != (layout.rows, layout.channels):
+        shape = tuple(planes.shape) if torch.is_tensor(planes) else type(planes).__name__
+        raise ValueError(f"planes has to be a [B, {layout.rows}, {layout.channels}] tensor for this layout (got {shape})")
+
+
+def kplanes_encode(points, times, planes, ray_grid_idx, layout: KPlanesLayout, *, mask_out_of_bounds_samples: bool = False,
+                   contract_coords: bool = False) -> torch.Tensor:
+    """``features [n_rays, n_pts, S C]``: the plane encoding (module docstring) of ``points [n_rays, n_pts, 3]`` at ``times``
+    (``[n_rays]`` or ``[n_rays, n_pts]``, read as it is -- no expanded copy; ``None`` for a static layout) with the
+    ``planes [B, layout.rows, C]`` of ``init_kplanes``; ``ray_grid_idx [n_rays]`` (any integer dtype): the scene of each row's points.
+    Differentiable with respect to ``planes`` and ``points``; ``times`` must not require a gradient (``.detach()`` it)."""
+    _check_inputs(points, times, planes, ray_grid_idx, layout)
+    _lib.check_tensors(points.device, {"points": points, "times": times, "planes": planes}, {"ray_grid_idx": ray_grid_idx})
+    _lib.current_stream(points.device)  # (raises for anything but a GPU: there is no CPU path)
+    grid_idx = _lib.int32_index(ray_grid_idx)
+    cfg = _Cfg(layout, bool(mask_out_of_bounds_samples), bool(contract_coords))
+    return _KPlanesEncode.apply(cfg, points, None if times is None else times.detach(), planes, grid_idx)
