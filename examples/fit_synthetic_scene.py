@@ -11,7 +11,7 @@ GPU boxes have no datasets.
                                             [--scaffold-steps 150,250] [--scaffold-size 64] [--export-pointcloud FILE.npy] [--clip-rays]
                                             [--export-mesh FILE.ply] [--mesh-size 64] [--mesh-level 1.0] [--modular]
                                             [--importance N] [--distortion-weight W] [--render-samples]
-                                            [--hash-grid] [--hash-levels 8] [--hash-features 2] [--hash-log2-size 15]
+                                            [--kplanes] [--hash-grid] [--hash-levels 8] [--hash-features 2] [--hash-log2-size 15]
                                             [--hash-base-res 4] [--hash-finest-res 64]
 
 ``--tv-weight w`` (> 0) adds ``w`` times the total variation of the three planes to the objective: its gradient is added to the
@@ -70,6 +70,10 @@ with ``--render-samples``, through ``lp.hash_grid_render_samples``: encoding, de
 tensor at all; ``--importance N`` then adds a coarse pass that only asks for the weights (``with_color=False``) --
 with a zero ray encoding (the scene's colours do not depend on the direction).  Training and held-out evaluation use that path;
 the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
+
+``--kplanes`` (with ``--modular``) fits a third student: static planes at three scales (``lp.kplanes_layout((16, 32, 64), None, 8)``,
+``lp.init_kplanes``) and a 2/2/2 x 32 decoder, rendered through ``lp.ray_samples -> lp.kplanes_eval_mlp -> lp.composite_samples`` --
+encoding and decoder in one launch, no feature tensor; the other flags do not apply (the JSON line gains ``kplanes``).
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -307,6 +311,48 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
             "render_samples": bool(fused), "importance": int(importance)}
 
 
+def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8):
+    """the fit of ``fit`` with static planes (``time_resolution=None``: the Hadamard tri-plane) + decoder as the student, through
+    ray_samples -> kplanes_eval_mlp -> composite_samples"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    lay = lp.kplanes_layout(resolutions, None, channels)
+    planes = torch.nn.Parameter(lp.init_kplanes(lay, 1, device=dev))
+    dec = lp.init_decoder_params(dev, 2, 2, 2, input_chn=lay.out_channels, hidden_chn=32, color_chn=3, opacity_init_bias=-2.0)
+    params = torch.nn.Parameter(dec.mlp_params)
+    dec = lp.DecoderParams(params, dec.n_hidden_trunk, dec.n_hidden_opacity, dec.n_hidden_color, dec.color_chn)
+    opt = torch.optim.Adam([{"params": [planes], "lr": 3e-2}, {"params": [params], "lr": 3e-3}])
+
+    def render(rays):
+        samples = lp.ray_samples(rays, num_samples)
+        enc = torch.zeros(rays.directions.shape[0], 32, device=dev)
+        opacity, color = lp.kplanes_eval_mlp(samples.points, None, planes, rays.grid_idx, lay, dec, enc, 1.0)
+        _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
+        return 1.0 - torch.exp(-nlt), rgb
+
+    losses = []
+    for it in range(steps):
+        rays = random_rays(n_rays, gen, dev)
+        with torch.no_grad():
+            tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
+        alpha, rgb = render(rays)
+        loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        if verbose and (it % 50 == 0 or it == steps - 1):
+            print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
+    rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
+    with torch.no_grad():
+        tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
+        psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
+    return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
+            "rays_per_step": n_rays, "modular": True, "kplanes": True, "resolutions": list(resolutions), "channels": channels,
+            "plane_rows": lay.rows}
+
+
 def write_ply(path, vertices, faces, normals, colors):
     """ASCII PLY: ``x y z nx ny nz red green blue`` per vertex (colours as 8-bit), ``3 i j k`` per face"""
     rgb = np.clip(np.rint(colors[:, :3] * 255.0), 0, 255).astype(np.int64)
@@ -373,7 +419,14 @@ def main(argv=None):
     ap.add_argument("--hash-log2-size", type=int, default=15)
     ap.add_argument("--hash-base-res", type=int, default=4)
     ap.add_argument("--hash-finest-res", type=int, default=64)
+    ap.add_argument("--kplanes", action="store_true",
+                    help="with --modular: fit static planes + decoder through ray_samples -> kplanes_eval_mlp -> composite_samples")
     a = ap.parse_args(argv)
+    if a.kplanes:
+        assert a.modular, "--kplanes renders through the modular march: pass --modular as well"
+        out = fit_kplanes(a.steps, a.rays, verbose=True)
+        print(json.dumps(out))
+        return out
     if a.hash_grid:
         assert a.modular, "--hash-grid renders through the modular march: pass --modular as well"
         assert a.importance == 0 or a.render_samples, "--hash-grid --importance resamples for the fused fine pass: pass --render-samples as well"

@@ -277,6 +277,22 @@ class LpKPlanesArgs(C.Structure):  # include/lightplane_hip_kplanes.h
     ]
 
 
+class LpKPlanesPointsArgs(C.Structure):  # include/lightplane_hip_kplanes_points.h
+    _fields_ = [
+        ("planes", C.c_void_p), ("grad_planes", C.c_void_p), ("points", C.c_void_p), ("times", C.c_void_p), ("grid_idx", C.c_void_p),
+        ("rows", C.c_int64), ("n_rays", C.c_int64), ("n_pts", C.c_int64),
+        ("offset", C.c_int64 * LP_KPLANES_MAX_PLANES * LP_KPLANES_MAX_SCALES),
+        ("spatial", C.c_int32 * LP_KPLANES_MAX_SCALES), ("temporal", C.c_int32 * LP_KPLANES_MAX_SCALES),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("n_scales", C.c_int32), ("n_planes", C.c_int32),
+        ("time_per_point", C.c_int32), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("color_chn", C.c_int32),
+        ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64), ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("encoding", C.c_void_p), ("encoding_dim", C.c_int32), ("gain", C.c_float),
+        ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("opacity_out", C.c_void_p), ("color_out", C.c_void_p), ("grad_opacity", C.c_void_p), ("grad_color", C.c_void_p),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p), ("grad_points", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -328,6 +344,9 @@ HASH_RENDER_EXPORTS = ("lp_hash_render_forward", "lp_hash_render_backward")
 
 #: every symbol include/lightplane_hip_kplanes.h declares (and again)
 KPLANES_EXPORTS = ("lp_kplanes_forward", "lp_kplanes_backward_planes", "lp_kplanes_backward_points")
+
+#: every symbol include/lightplane_hip_kplanes_points.h declares (and again)
+KPLANES_POINTS_EXPORTS = ("lp_kplanes_points_forward", "lp_kplanes_points_backward")
 
 
 def _signatures():
@@ -393,6 +412,8 @@ def _signatures():
         (HASH_RENDER_EXPORTS, C.c_int, (P(LpHashRenderArgs), vp)),
         # space-time plane encoding of points (include/lightplane_hip_kplanes.h): args, stream
         (KPLANES_EXPORTS, C.c_int, (P(LpKPlanesArgs), vp)),
+        # the decoder on a plane field at points (include/lightplane_hip_kplanes_points.h): args, stream
+        (KPLANES_POINTS_EXPORTS, C.c_int, (P(LpKPlanesPointsArgs), vp)),
     )
 
 
@@ -430,7 +451,8 @@ def lib() -> C.CDLL:
                       (38, LpHashGridArgs),  # (nor 36, 37 and 39: lightplane_hip_hash_grid.h)
                       (42, LpHashPointsArgs),  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
                       (46, LpHashRenderArgs),  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
-                      (50, LpKPlanesArgs)):  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
+                      (50, LpKPlanesArgs),  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
+                      (54, LpKPlanesPointsArgs)):  # (nor 52, 53 and 55: lightplane_hip_kplanes_points.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

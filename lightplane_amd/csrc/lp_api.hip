@@ -981,19 +981,11 @@ static int check_hash_grid(const char* what, const LpHashGridArgs* args, int mod
   return LP_OK;
 }
 
-// everything the three lp_kplanes_* entry points check.  mode: 0 forward, 1 backward_planes, 2 backward_points.  Messages begin with
-// the field where a field is at fault.  The layout is held to the rules of lightplane_hip_kplanes.h: the kernels index with it.
-static int check_kplanes(const char* what, const LpKPlanesArgs* args, int mode) {
+// the batch and the layout of a plane field, held to the rules of lightplane_hip_kplanes.h: the kernels index with them.  For the
+// lp_kplanes_* entry points and, through a copy of these fields, for lp_kplanes_points_*.
+static int check_kplanes_layout(const char* what, const LpKPlanesArgs& k) {
+  const LpKPlanesArgs* args = &k;
   int rc;
-  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
-  LP_ALIGNED(*args, planes);
-  LP_ALIGNED(*args, grad_planes);
-  LP_ALIGNED(*args, points);
-  LP_ALIGNED(*args, times);
-  LP_ALIGNED(*args, grid_idx);
-  LP_ALIGNED(*args, out_features);
-  LP_ALIGNED(*args, grad_features);
-  LP_ALIGNED(*args, grad_points);
   if ((rc = check_point_batch(what, args->n_rays, args->n_pts, true))) return rc;
   if (args->batch < 1) return set_error(LP_EINVAL, "batch %d < 1", args->batch);
   const int S = args->n_scales, P = args->n_planes, C = args->channels;
@@ -1017,13 +1009,78 @@ static int check_kplanes(const char* what, const LpKPlanesArgs* args, int mode) 
     }
   }
   if (end > args->rows) return set_error(LP_EINVAL, "rows %lld < %lld, where the last plane ends", (long long)args->rows, (long long)end);
+  return LP_OK;
+}
+
+// everything the three lp_kplanes_* entry points check.  mode: 0 forward, 1 backward_planes, 2 backward_points.  Messages begin with
+// the field where a field is at fault.
+static int check_kplanes(const char* what, const LpKPlanesArgs* args, int mode) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, grad_planes);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, times);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, out_features);
+  LP_ALIGNED(*args, grad_features);
+  LP_ALIGNED(*args, grad_points);
+  if ((rc = check_kplanes_layout(what, *args))) return rc;
   const struct { const char* field; const void* p; bool needed; } ptrs[] = {
-      {"points", args->points, true},          {"grid_idx", args->grid_idx, true},          {"times", args->times, P == 6},
+      {"points", args->points, true},          {"grid_idx", args->grid_idx, true},          {"times", args->times, args->n_planes == 6},
       {"planes", args->planes, true},          {"out_features", args->out_features, mode == 0},
       {"grad_features", args->grad_features, mode != 0}, {"grad_planes", args->grad_planes, mode == 1},
       {"grad_points", args->grad_points, mode == 2}};
   for (const auto& f : ptrs)
     if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
+// everything lp_kplanes_points_forward / lp_kplanes_points_backward check: the layout as lp_kplanes_*, the decoder, the scaffold and
+// the alignment as lp_hash_points_*.  `color`: the colour head takes part (forward: color_out given; backward: grad_color given) --
+// only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
+static int check_kplanes_points(const char* what, const LpKPlanesPointsArgs* args, bool backward) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_color != nullptr : args->color_out != nullptr;
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, grad_planes);
+  LP_ALIGNED(*args, points);
+  LP_ALIGNED(*args, times);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, opacity_out);
+  LP_ALIGNED(*args, color_out);
+  LP_ALIGNED(*args, grad_opacity);
+  LP_ALIGNED(*args, grad_color);
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  LP_ALIGNED(*args, grad_points);
+  const LpKPlanesArgs k = kplanes_points_view(*args);  // the layout fields, for the one place that judges them
+  if ((rc = check_kplanes_layout(what, k))) return rc;
+  const int C = args->n_scales * args->channels;
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, C, args->trunk, args->opacity, head_in))) return rc;
+  const int64_t n_to = mlp_numel(args->trunk) + mlp_numel(args->opacity);
+  if ((rc = check_color_head(what, args->color, head_in, n_to, color, args->color_chn, args->encoding_dim))) return rc;
+  if ((rc = check_param_count(what, n_to + mlp_numel(args->color), args->n_mlp_params, false))) return rc;
+  if (args->scaffold) {
+    if ((rc = check_shape(what, "scaffold", args->scaffold_shape))) return rc;
+    if (args->scaffold_shape.B != args->batch)
+      return set_error(LP_EINVAL, "scaffold_shape: batch %d != batch %d of the planes", args->scaffold_shape.B, args->batch);
+  }
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"planes", args->planes, true},  {"points", args->points, true},     {"grid_idx", args->grid_idx, true},
+      {"times", args->times, args->n_planes == 6}, {"mlp_params", args->mlp_params, true}, {"encoding", args->encoding, color},
+      {"opacity_out", args->opacity_out, !backward}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  if (backward) {
+    const int total = kplanes_points_backward_total_width(*args);
+    if (total > 1024) return set_error(LP_EUNSUPPORTED, "%s: sum of layer widths %d exceeds 1024", what, total);
+  }
   return LP_OK;
 }
 
@@ -1132,13 +1189,13 @@ static int check_hash_render(const char* what, const LpHashRenderArgs* args, boo
 }
 
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
-// with the compositing), its hash-grid twin (lp_hash_render.hip) and the space-time plane encoding at points (lp_kplanes.hip): the
-// top-level keys of the text stay as they are
+// with the compositing), its hash-grid twin (lp_hash_render.hip), the space-time plane encoding at points (lp_kplanes.hip) and the
+// decoder fused on it (lp_kplanes_points.hip): the top-level keys of the text stay as they are
 static const char* build_info_points_family() {
-  static char text[4096];
+  static char text[6144];  // (the five texts together: ~4.6 KB; lp_build_info() holds 16 KB)
   const char* p = build_info_points();
-  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s}", (int)strlen(p) - 1, p,
-           build_info_render_samples(), build_info_hash_render(), build_info_kplanes());
+  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s, \"kplanes_points\": %s}",
+           (int)strlen(p) - 1, p, build_info_render_samples(), build_info_hash_render(), build_info_kplanes(), build_info_kplanes_points());
   return text;
 }
 
@@ -1153,7 +1210,7 @@ int lp_version(void) { return LP_VERSION; }
 const char* lp_last_error(void) { return g_err; }
 
 const char* lp_build_info(void) {
-  static char info[8192];
+  static char info[16384];
   // what every translation unit reports about itself (a JSON fragment each), in the order of the text
   static const struct { const char* key; const char* (*value)(); } units[] = {
       {"test_hooks", build_info_tuned_bwd_aux}, {"tuned_bwd", build_info_tuned_bwd},          {"loop_bwd_deep", build_info_loop_deep},
@@ -1202,6 +1259,7 @@ int lp_abi_sizeof(int which) {
     case 42: return (int)sizeof(LpHashPointsArgs);  // (and 40, 41, 43: lightplane_hip_hash_points.h)
     case 46: return (int)sizeof(LpHashRenderArgs);  // (and 44, 45, 47: lightplane_hip_hash_render.h)
     case 50: return (int)sizeof(LpKPlanesArgs);  // (and 48, 49, 51: lightplane_hip_kplanes.h)
+    case 54: return (int)sizeof(LpKPlanesPointsArgs);  // (and 52, 53, 55: lightplane_hip_kplanes_points.h)
     default: return -1;
   }
 }
@@ -1680,6 +1738,18 @@ int lp_kplanes_backward_points(const LpKPlanesArgs* args, void* stream) {
   const int rc = check_kplanes("lp_kplanes_backward_points", args, 2);
   if (rc != LP_OK || args->n_rays == 0 || args->n_pts == 0) return rc;
   return kplanes_backward_points_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_points_forward(const LpKPlanesPointsArgs* args, void* stream) {
+  const int rc = check_kplanes_points("lp_kplanes_points_forward", args, false);
+  if (rc) return rc;
+  return kplanes_points_forward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_points_backward(const LpKPlanesPointsArgs* args, void* stream) {
+  const int rc = check_kplanes_points("lp_kplanes_points_backward", args, true);
+  if (rc) return rc;
+  return kplanes_points_backward_launch(*args, (hipStream_t)stream);
 }
 
 int lp_hash_points_forward(const LpHashPointsArgs* args, void* stream) {

@@ -13,6 +13,7 @@
 #include "../../include/lightplane_hip_hash_points.h"
 #include "../../include/lightplane_hip_hash_render.h"
 #include "../../include/lightplane_hip_kplanes.h"
+#include "../../include/lightplane_hip_kplanes_points.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -199,6 +200,12 @@ int kplanes_forward_launch(const LpKPlanesArgs& a, hipStream_t stream);
 int kplanes_backward_planes_launch(const LpKPlanesArgs& a, hipStream_t stream);
 int kplanes_backward_points_launch(const LpKPlanesArgs& a, hipStream_t stream);
 const char* build_info_kplanes();
+// the decoder on a plane field at points, encoding and decoder in one launch: lp_kplanes_points.hip (`a` checked by lp_api.hip)
+int kplanes_points_forward_launch(const LpKPlanesPointsArgs& a, hipStream_t stream);
+int kplanes_points_backward_launch(const LpKPlanesPointsArgs& a, hipStream_t stream);
+LpKPlanesArgs kplanes_points_view(const LpKPlanesPointsArgs& a);        // its layout, planes, points, times and flags as an LpKPlanesArgs
+int kplanes_points_backward_total_width(const LpKPlanesPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
+const char* build_info_kplanes_points();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -19,6 +19,15 @@ value of plane ``j`` at its two coordinates (4 vertices, weights ``(1 - f | f)``
 elementwise product, scales concatenated scale-major, no normalisation.  Gradients go to ``planes`` (fp32 atomics; rows no point touches
 stay exactly 0) and to ``points`` (stored, bit-reproducible, zero on a clamped axis); ``times`` and ``ray_grid_idx`` get none.  No
 derivative divides by a plane value.  No host synchronisation (graph-capturable); there is no double backward and no CPU path.
+
+**The decoder on it, in one launch.**  ``kplanes_eval_mlp`` / ``kplanes_eval_mlp_opacity_only`` (``csrc/lp_kplanes_points.hip``; C ABI
+``lp_kplanes_points_forward`` / ``lp_kplanes_points_backward``) evaluate the library's decoder on this encoding: ``t = ReLU(trunk(feat))``
+(``ReLU(feat)`` without trunk layers), ``opacity = gain softplus(opacity MLP(t)) occ``, ``colour = sigmoid(colour MLP(t +
+rays_encoding[r]))[:color_chn] occ``, ``occ`` the scaffold's nearest-neighbour value at ``q`` (1 without one) -- the decoder of
+``hash_grid_eval_mlp``.  The features ``[n_rays, n_pts, S C]`` and their gradient never reach memory: ``ray_samples -> kplanes_eval_mlp
+-> composite_samples`` is a differentiable renderer of a time-dependent field.  One autograd function that keeps its inputs only;
+gradients go to ``planes``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``, a gradient nobody asks for is not computed,
+and without an upstream colour gradient the colour head is not evaluated (its parameters get exactly 0).
 """
 from __future__ import annotations
 
@@ -28,8 +37,9 @@ from typing import NamedTuple, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
+from .params import DecoderParams, int_list_of
 
-__all__ = ["KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode"]
+__all__ = ["KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only"]
 
 
 class KPlanesLayout(NamedTuple):
@@ -92,10 +102,10 @@ class _Cfg(NamedTuple):
     contract: bool
 
 
-def _args(cfg: _Cfg, points, times, grid_idx, batch: int) -> _lib.LpKPlanesArgs:
-    """the layout, the points, the timestamps and the flags in a fresh ``LpKPlanesArgs``"""
+def _args(cfg: _Cfg, points, times, grid_idx, batch: int, a=None):
+    """the layout, the points, the timestamps and the flags in a fresh ``LpKPlanesArgs`` (or in ``a``, which has the same fields)"""
     lay = cfg.layout
-    a = _lib.LpKPlanesArgs()
+    a = _lib.LpKPlanesArgs() if a is None else a
     a.points, a.grid_idx, a.times = _lib.ptr(points), _lib.ptr(grid_idx), _lib.ptr(times)
     a.time_per_point = int(times is not None and times.ndim == 2)
     a.n_rays, a.n_pts = points.shape[0], points.shape[1]
@@ -110,7 +120,7 @@ def _args(cfg: _Cfg, points, times, grid_idx, batch: int) -> _lib.LpKPlanesArgs:
     return a
 
 
-def _call(name: str, a: _lib.LpKPlanesArgs, stream) -> None:
+def _call(name: str, a, stream) -> None:
     _lib.check(getattr(_lib.lib(), name)(ctypes.byref(a), stream), name)
 
 
@@ -199,3 +209,131 @@ def kplanes_encode(points, times, planes, ray_grid_idx, layout: KPlanesLayout, *
     grid_idx = _lib.int32_index(ray_grid_idx)
     cfg = _Cfg(layout, bool(mask_out_of_bounds_samples), bool(contract_coords))
     return _KPlanesEncode.apply(cfg, points, None if times is None else times.detach(), planes, grid_idx)
+
+
+class _EvalCfg(NamedTuple):
+    planes: _Cfg
+    dims_t: tuple
+    dims_o: tuple
+    dims_c: tuple
+    color_chn: int
+    gain: float
+    opacity_only: bool
+
+
+def _eval_args(cfg: _EvalCfg, points, times, planes, mlp_params, encoding, grid_idx, scaffold, with_color: bool) -> _lib.LpKPlanesPointsArgs:
+    a = _args(cfg.planes, points, times, grid_idx, planes.shape[0], _lib.LpKPlanesPointsArgs())
+    a.planes = _lib.ptr(planes)
+    a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
+    _lib.make_decoder(a, cfg.dims_t, cfg.dims_o, cfg.dims_c)
+    a.color_chn, a.gain = cfg.color_chn, cfg.gain
+    if with_color:
+        a.encoding, a.encoding_dim = _lib.ptr(encoding), encoding.shape[1]
+    if scaffold is not None:
+        a.scaffold = _lib.ptr(scaffold)
+        a.scaffold_shape = _lib.LpGrid(*[int(v) for v in scaffold.shape], 0, None)
+    return a
+
+
+class _KPlanesEval(torch.autograd.Function):
+    """(opacity[, colour]) = decoder(encode(points, times, planes)): one forward launch; the backward is one launch that recomputes
+    every point and fills the gradients ``needs_input_grad`` asks for (a gradient nobody asks for is a NULL pointer: its work is
+    skipped; without an upstream gradient for the colour, the colour head is not evaluated)."""
+
+    @staticmethod
+    def forward(ctx, cfg: _EvalCfg, points, times, planes, mlp_params, encoding, grid_idx, scaffold):
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        points, planes = _lib.aligned(points.contiguous()), _lib.aligned(planes.contiguous(), grid=True)
+        times = None if times is None else _lib.aligned(times.contiguous())
+        mlp_params = _lib.aligned(mlp_params.contiguous())
+        encoding = None if encoding is None else _lib.aligned(encoding.contiguous())
+        n_rays, n_pts = points.shape[0], points.shape[1]
+        with torch.cuda.device(dev):
+            opacity = torch.empty(n_rays, n_pts, device=dev, dtype=torch.float32)
+            color = None if cfg.opacity_only else torch.empty(n_rays, n_pts, cfg.color_chn, device=dev, dtype=torch.float32)
+            a = _eval_args(cfg, points, times, planes, mlp_params, encoding, grid_idx, scaffold, not cfg.opacity_only)
+            a.opacity_out, a.color_out = _lib.ptr(opacity), _lib.ptr(color)
+            if opacity.numel():  # (an empty batch has no tensors to point at)
+                _call("lp_kplanes_points_forward", a, stream)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(points, times, planes, mlp_params, encoding, grid_idx, scaffold)
+        return opacity if cfg.opacity_only else (opacity, color)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_opacity, g_color=None):
+        cfg: _EvalCfg = ctx.cfg
+        points, times, planes, mlp_params, encoding, grid_idx, scaffold = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if (g_opacity is None and g_color is None) or not any(need):
+            return (None,) * 8
+        dev = points.device
+        stream = _lib.current_stream(dev)
+        with_color = g_color is not None and not cfg.opacity_only
+        g_opacity = None if g_opacity is None else _lib.aligned(g_opacity.to(torch.float32).contiguous())
+        g_color = _lib.aligned(g_color.to(torch.float32).contiguous()) if with_color else None
+        with torch.cuda.device(dev):
+            d_points = torch.empty_like(points) if need[1] else None
+            d_planes = torch.zeros_like(planes) if need[3] else None
+            d_params = torch.zeros_like(mlp_params) if need[4] else None
+            d_enc = torch.zeros_like(encoding) if (need[5] and encoding is not None) else None
+            a = _eval_args(cfg, points, times, planes, mlp_params, encoding, grid_idx, scaffold, with_color)
+            a.grad_opacity, a.grad_color = _lib.ptr(g_opacity), _lib.ptr(g_color)
+            a.grad_points, a.grad_planes, a.grad_mlp_params = _lib.ptr(d_points), _lib.ptr(d_planes), _lib.ptr(d_params)
+            a.grad_encoding = _lib.ptr(d_enc) if with_color else None
+            if points.numel():
+                _call("lp_kplanes_points_backward", a, stream)
+        return None, d_points, None, d_planes, d_params, d_enc, None, None
+
+
+def _eval(points, times, planes, ray_grid_idx, layout, decoder_params: DecoderParams, rays_encoding, gain, mask, contract, scaffold,
+          opacity_only: bool):
+    _check_inputs(points, times, planes, ray_grid_idx, layout)
+    n_rays = points.shape[0]
+    dims_t, dims_o, dims_c = (tuple(int_list_of(v)) for v in (decoder_params.n_hidden_trunk, decoder_params.n_hidden_opacity,
+                                                              decoder_params.n_hidden_color))
+    width = dims_t[0] if len(dims_t) > 1 else dims_o[0]
+    if width != layout.out_channels:
+        raise ValueError(f"the decoder reads {width} features, the layout has n_scales x channels = {layout.out_channels}")
+    if opacity_only:
+        rays_encoding = None
+    else:
+        assert torch.is_tensor(rays_encoding) and tuple(rays_encoding.shape) == (n_rays, dims_c[0]), (
+            f"rays_encoding has to be a [{n_rays}, {dims_c[0]}] tensor (the colour head's input width)")
+    mlp_params = decoder_params.mlp_params
+    assert mlp_params.ndim == 1, "decoder_params.mlp_params has to be the flat parameter vector"
+    if scaffold is not None:
+        assert torch.is_tensor(scaffold) and scaffold.ndim == 4, "scaffold has to be a [B, D, H, W] tensor"
+    dev = points.device
+    _lib.check_tensors(dev, {"points": points, "times": times, "planes": planes, "decoder_params.mlp_params": mlp_params,
+                             "rays_encoding": rays_encoding, "scaffold": scaffold}, {"ray_grid_idx": ray_grid_idx})
+    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    grid_idx = _lib.int32_index(ray_grid_idx)
+    scaffold = None if scaffold is None else _lib.aligned(scaffold.detach().contiguous())
+    cfg = _EvalCfg(_Cfg(layout, bool(mask), bool(contract)), dims_t, dims_o, dims_c, int(decoder_params.color_chn), float(gain),
+                   opacity_only)
+    return _KPlanesEval.apply(cfg, points, None if times is None else times.detach(), planes, mlp_params, rays_encoding, grid_idx,
+                              scaffold)
+
+
+def kplanes_eval_mlp(points, times, planes, ray_grid_idx, layout: KPlanesLayout, decoder_params: DecoderParams, rays_encoding,
+                     gain: float, *, mask_out_of_bounds_samples: bool = False, contract_coords: bool = False,
+                     scaffold: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(opacity [n_rays, n_pts], colour [n_rays, n_pts, color_chn])`` of the decoder on the plane encoding of
+    ``points [n_rays, n_pts, 3]`` at ``times`` (module docstring), in one launch.  ``times``, ``planes``, ``ray_grid_idx``, ``layout``:
+    as ``kplanes_encode``; ``decoder_params``: a decoder whose trunk (without trunk layers: whose heads) reads ``layout.out_channels``
+    features; ``rays_encoding [n_rays, E]``: added to the colour head's input; ``scaffold``: ``[B, D, H, W]`` occupancy or ``None``.
+    Differentiable with respect to ``planes``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``."""
+    return _eval(points, times, planes, ray_grid_idx, layout, decoder_params, rays_encoding, gain, mask_out_of_bounds_samples,
+                 contract_coords, scaffold, False)
+
+
+def kplanes_eval_mlp_opacity_only(points, times, planes, ray_grid_idx, layout: KPlanesLayout, decoder_params: DecoderParams, gain: float,
+                                  *, mask_out_of_bounds_samples: bool = False, contract_coords: bool = False,
+                                  scaffold: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``opacity [n_rays, n_pts]`` alone: the opacity of ``kplanes_eval_mlp``, bit for bit, without the colour head -- there is no
+    encoding, and the colour MLP's parameters are never read (they get exactly zero gradient)."""
+    return _eval(points, times, planes, ray_grid_idx, layout, decoder_params, None, gain, mask_out_of_bounds_samples, contract_coords,
+                 scaffold, True)
