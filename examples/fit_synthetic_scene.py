@@ -73,11 +73,13 @@ the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
 
 ``--kplanes`` (with ``--modular``) fits a third student: static planes at three scales (``lp.kplanes_layout((16, 32, 64), None, 8)``,
 ``lp.init_kplanes``) and a 2/2/2 x 32 decoder, rendered through ``lp.ray_samples -> lp.kplanes_eval_mlp -> lp.composite_samples`` --
-encoding and decoder in one launch, no feature tensor; the other flags do not apply (the JSON line gains ``kplanes``).
+encoding and decoder in one launch, no feature tensor -- or, with ``--render-samples``, through ``lp.kplanes_render_samples``: encoding,
+decoder and compositing in one launch, no per-sample tensor; the other flags do not apply (the JSON line gains ``kplanes``).
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
 import argparse
+import dataclasses
 import json
 import math
 import os
@@ -311,9 +313,10 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
             "render_samples": bool(fused), "importance": int(importance)}
 
 
-def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8):
+def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8, fused=False):
     """the fit of ``fit`` with static planes (``time_resolution=None``: the Hadamard tri-plane) + decoder as the student, through
-    ray_samples -> kplanes_eval_mlp -> composite_samples"""
+    ray_samples -> kplanes_eval_mlp -> composite_samples or, ``fused``, through ``lp.kplanes_render_samples`` (one launch, no per-sample
+    tensors)"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -327,6 +330,10 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
     def render(rays):
         samples = lp.ray_samples(rays, num_samples)
         enc = torch.zeros(rays.directions.shape[0], 32, device=dev)
+        if fused:
+            _, nlt, rgb = lp.kplanes_render_samples(dataclasses.replace(rays, encoding=enc), None, samples.depths.detach(),
+                                                    samples.deltas.detach(), planes, lay, dec)
+            return 1.0 - torch.exp(-nlt), rgb
         opacity, color = lp.kplanes_eval_mlp(samples.points, None, planes, rays.grid_idx, lay, dec, enc, 1.0)
         _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
         return 1.0 - torch.exp(-nlt), rgb
@@ -350,7 +357,7 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
         psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
     return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
             "rays_per_step": n_rays, "modular": True, "kplanes": True, "resolutions": list(resolutions), "channels": channels,
-            "plane_rows": lay.rows}
+            "plane_rows": lay.rows, "render_samples": bool(fused)}
 
 
 def write_ply(path, vertices, faces, normals, colors):
@@ -424,7 +431,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.kplanes:
         assert a.modular, "--kplanes renders through the modular march: pass --modular as well"
-        out = fit_kplanes(a.steps, a.rays, verbose=True)
+        out = fit_kplanes(a.steps, a.rays, verbose=True, fused=a.render_samples)
         print(json.dumps(out))
         return out
     if a.hash_grid:

@@ -41,7 +41,7 @@ from .ray_grid import gather_along_rays, splat_along_rays  # noqa: E402
 from .hash_grid import (HashGridLayout, hash_grid_encode, hash_grid_eval_mlp, hash_grid_eval_mlp_opacity_only,  # noqa: E402
                         hash_grid_layout, hash_grid_render_samples, init_hash_grid)
 from .kplanes import (KPlanesLayout, init_kplanes, kplanes_encode, kplanes_eval_mlp, kplanes_eval_mlp_opacity_only,  # noqa: E402
-                      kplanes_layout)
+                      kplanes_layout, kplanes_render_samples)
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -75,7 +75,7 @@ __all__ = [
     "splat_along_rays", "gather_along_rays",
     "HashGridLayout", "hash_grid_layout", "init_hash_grid", "hash_grid_encode",
     "hash_grid_eval_mlp", "hash_grid_eval_mlp_opacity_only", "hash_grid_render_samples",
-    "KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only",
+    "KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only", "kplanes_render_samples",
 ]
 
 _NOT_PROVIDED = {

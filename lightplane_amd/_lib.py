@@ -293,6 +293,23 @@ class LpKPlanesPointsArgs(C.Structure):  # include/lightplane_hip_kplanes_points
     ]
 
 
+class LpKPlanesRenderArgs(C.Structure):  # include/lightplane_hip_kplanes_render.h
+    _fields_ = [
+        ("planes", C.c_void_p), ("grad_planes", C.c_void_p), ("times", C.c_void_p), ("rows", C.c_int64),
+        ("offset", C.c_int64 * LP_KPLANES_MAX_PLANES * LP_KPLANES_MAX_SCALES),
+        ("spatial", C.c_int32 * LP_KPLANES_MAX_SCALES), ("temporal", C.c_int32 * LP_KPLANES_MAX_SCALES),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("n_scales", C.c_int32), ("n_planes", C.c_int32),
+        ("time_per_sample", C.c_int32), ("mask_out_of_bounds", C.c_int32), ("contract_coords", C.c_int32), ("color_chn", C.c_int32),
+        ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64), ("trunk", LpMlp), ("opacity", LpMlp), ("color", LpMlp),
+        ("gain", C.c_float), ("encoding_dim", C.c_int32), ("scaffold", C.c_void_p), ("scaffold_shape", LpGrid),
+        ("origins", C.c_void_p), ("directions", C.c_void_p), ("grid_idx", C.c_void_p), ("encoding", C.c_void_p),
+        ("depths", C.c_void_p), ("deltas", C.c_void_p), ("n_rays", C.c_int64), ("n_samples", C.c_int32), ("reserved", C.c_int32),
+        ("ray_length", C.c_void_p), ("neg_log_t", C.c_void_p), ("feature", C.c_void_p), ("weights", C.c_void_p), ("chunk_nlt", C.c_void_p),
+        ("grad_ray_length", C.c_void_p), ("grad_neg_log_t", C.c_void_p), ("grad_feature", C.c_void_p), ("grad_weights", C.c_void_p),
+        ("grad_mlp_params", C.c_void_p), ("grad_encoding", C.c_void_p),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -347,6 +364,9 @@ KPLANES_EXPORTS = ("lp_kplanes_forward", "lp_kplanes_backward_planes", "lp_kplan
 
 #: every symbol include/lightplane_hip_kplanes_points.h declares (and again)
 KPLANES_POINTS_EXPORTS = ("lp_kplanes_points_forward", "lp_kplanes_points_backward")
+
+#: every symbol include/lightplane_hip_kplanes_render.h declares (and again)
+KPLANES_RENDER_EXPORTS = ("lp_kplanes_render_forward", "lp_kplanes_render_backward")
 
 
 def _signatures():
@@ -414,6 +434,8 @@ def _signatures():
         (KPLANES_EXPORTS, C.c_int, (P(LpKPlanesArgs), vp)),
         # the decoder on a plane field at points (include/lightplane_hip_kplanes_points.h): args, stream
         (KPLANES_POINTS_EXPORTS, C.c_int, (P(LpKPlanesPointsArgs), vp)),
+        # a plane field rendered along rays at caller-given depths (include/lightplane_hip_kplanes_render.h): args, stream
+        (KPLANES_RENDER_EXPORTS, C.c_int, (P(LpKPlanesRenderArgs), vp)),
     )
 
 
@@ -452,7 +474,8 @@ def lib() -> C.CDLL:
                       (42, LpHashPointsArgs),  # (nor 40, 41 and 43: lightplane_hip_hash_points.h)
                       (46, LpHashRenderArgs),  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
                       (50, LpKPlanesArgs),  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
-                      (54, LpKPlanesPointsArgs)):  # (nor 52, 53 and 55: lightplane_hip_kplanes_points.h)
+                      (54, LpKPlanesPointsArgs),  # (nor 52, 53 and 55: lightplane_hip_kplanes_points.h)
+                      (58, LpKPlanesRenderArgs)):  # (nor 56, 57 and 59: lightplane_hip_kplanes_render.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

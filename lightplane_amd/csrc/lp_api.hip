@@ -1188,14 +1188,77 @@ static int check_hash_render(const char* what, const LpHashRenderArgs* args, boo
   return LP_OK;
 }
 
+// everything lp_kplanes_render_forward / lp_kplanes_render_backward check: the layout and the decoder as lp_kplanes_points_*, the batch,
+// the samples and the alignment as lp_hash_render_*.  `color`: the colour head takes part (forward: feature given; backward:
+// grad_feature given) -- only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
+static int check_kplanes_render(const char* what, const LpKPlanesRenderArgs* args, bool backward) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  const bool color = backward ? args->grad_feature != nullptr : args->feature != nullptr;
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, grad_planes);
+  LP_ALIGNED(*args, times);
+  LP_ALIGNED(*args, mlp_params);
+  LP_ALIGNED(*args, scaffold);
+  LP_ALIGNED(*args, origins);
+  LP_ALIGNED(*args, directions);
+  LP_ALIGNED(*args, grid_idx);
+  LP_ALIGNED(*args, encoding);
+  LP_ALIGNED(*args, depths);
+  LP_ALIGNED(*args, deltas);
+  LP_ALIGNED(*args, ray_length);
+  LP_ALIGNED(*args, neg_log_t);
+  LP_ALIGNED(*args, feature);
+  LP_ALIGNED(*args, weights);
+  LP_ALIGNED(*args, chunk_nlt);
+  LP_ALIGNED(*args, grad_ray_length);
+  LP_ALIGNED(*args, grad_neg_log_t);
+  LP_ALIGNED(*args, grad_feature);
+  LP_ALIGNED(*args, grad_weights);
+  LP_ALIGNED(*args, grad_mlp_params);
+  LP_ALIGNED(*args, grad_encoding);
+  if (args->n_samples < 1) return set_error(LP_EINVAL, "n_samples %d < 1", args->n_samples);
+  const LpKPlanesArgs k = kplanes_render_view(*args);  // the layout fields and the batch n_rays x n_samples, for the one place that judges them
+  if ((rc = check_kplanes_layout(what, k))) return rc;
+  const int C = args->n_scales * args->channels;
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, C, args->trunk, args->opacity, head_in))) return rc;
+  const int64_t n_to = mlp_numel(args->trunk) + mlp_numel(args->opacity);
+  if ((rc = check_color_head(what, args->color, head_in, n_to, color, args->color_chn, args->encoding_dim))) return rc;
+  if ((rc = check_param_count(what, n_to + mlp_numel(args->color), args->n_mlp_params, false))) return rc;
+  if (args->scaffold) {
+    if ((rc = check_shape(what, "scaffold", args->scaffold_shape))) return rc;
+    if (args->scaffold_shape.B != args->batch)
+      return set_error(LP_EINVAL, "scaffold_shape: batch %d != batch %d of the planes", args->scaffold_shape.B, args->batch);
+  }
+  if (!args->planes) return set_error(LP_ENULL, "planes is NULL");
+  if (!args->mlp_params) return set_error(LP_ENULL, "mlp_params is NULL");
+  if (args->n_rays > 0) {  // (an empty batch has no tensors to point at)
+    const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+        {"origins", args->origins, true}, {"directions", args->directions, true}, {"grid_idx", args->grid_idx, true},
+        {"times", args->times, args->n_planes == 6}, {"encoding", args->encoding, color}, {"depths", args->depths, true},
+        {"deltas", args->deltas, true}, {"chunk_nlt", args->chunk_nlt, backward}};
+    for (const auto& f : ptrs)
+      if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  }
+  if (backward) {
+    const int total = kplanes_render_backward_total_width(*args);
+    if (total > 1024) return set_error(LP_EUNSUPPORTED, "%s: sum of layer widths %d exceeds 1024", what, total);
+  }
+  return LP_OK;
+}
+
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
 // with the compositing), its hash-grid twin (lp_hash_render.hip), the space-time plane encoding at points (lp_kplanes.hip) and the
-// decoder fused on it (lp_kplanes_points.hip): the top-level keys of the text stay as they are
+// decoder fused on it (lp_kplanes_points.hip) and its render along rays (lp_kplanes_render.hip): the top-level keys of the text stay as
+// they are
 static const char* build_info_points_family() {
-  static char text[6144];  // (the five texts together: ~4.6 KB; lp_build_info() holds 16 KB)
+  static char text[7168];  // (the six texts together: ~5.4 KB; lp_build_info() holds 16 KB)
   const char* p = build_info_points();
-  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s, \"kplanes_points\": %s}",
-           (int)strlen(p) - 1, p, build_info_render_samples(), build_info_hash_render(), build_info_kplanes(), build_info_kplanes_points());
+  snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s, \"kplanes_points\": %s, "
+           "\"kplanes_render\": %s}",
+           (int)strlen(p) - 1, p, build_info_render_samples(), build_info_hash_render(), build_info_kplanes(), build_info_kplanes_points(),
+           build_info_kplanes_render());
   return text;
 }
 
@@ -1260,6 +1323,7 @@ int lp_abi_sizeof(int which) {
     case 46: return (int)sizeof(LpHashRenderArgs);  // (and 44, 45, 47: lightplane_hip_hash_render.h)
     case 50: return (int)sizeof(LpKPlanesArgs);  // (and 48, 49, 51: lightplane_hip_kplanes.h)
     case 54: return (int)sizeof(LpKPlanesPointsArgs);  // (and 52, 53, 55: lightplane_hip_kplanes_points.h)
+    case 58: return (int)sizeof(LpKPlanesRenderArgs);  // (and 56, 57, 59: lightplane_hip_kplanes_render.h)
     default: return -1;
   }
 }
@@ -1762,6 +1826,18 @@ int lp_hash_points_backward(const LpHashPointsArgs* args, void* stream) {
   const int rc = check_hash_points("lp_hash_points_backward", args, true);
   if (rc != LP_OK) return rc;
   return hash_points_backward_launch(*args, (hipStream_t)stream);
+}
+
+int lp_kplanes_render_forward(const LpKPlanesRenderArgs* args, void* stream) {
+  const int rc = check_kplanes_render("lp_kplanes_render_forward", args, false);
+  if (rc != LP_OK || args->n_rays == 0) return rc;
+  return kplanes_render_launch(*args, false, (hipStream_t)stream);
+}
+
+int lp_kplanes_render_backward(const LpKPlanesRenderArgs* args, void* stream) {
+  const int rc = check_kplanes_render("lp_kplanes_render_backward", args, true);
+  if (rc != LP_OK || args->n_rays == 0) return rc;
+  return kplanes_render_launch(*args, true, (hipStream_t)stream);
 }
 
 int lp_hash_render_forward(const LpHashRenderArgs* args, void* stream) {

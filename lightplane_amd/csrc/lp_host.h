@@ -14,6 +14,7 @@
 #include "../../include/lightplane_hip_hash_render.h"
 #include "../../include/lightplane_hip_kplanes.h"
 #include "../../include/lightplane_hip_kplanes_points.h"
+#include "../../include/lightplane_hip_kplanes_render.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -206,6 +207,12 @@ int kplanes_points_backward_launch(const LpKPlanesPointsArgs& a, hipStream_t str
 LpKPlanesArgs kplanes_points_view(const LpKPlanesPointsArgs& a);        // its layout, planes, points, times and flags as an LpKPlanesArgs
 int kplanes_points_backward_total_width(const LpKPlanesPointsArgs& a);  // sum of the layer widths the backward keeps per point (<= 1024)
 const char* build_info_kplanes_points();
+// a plane field rendered along rays at caller-given depths, encoding + decoder + compositing in one launch: lp_kplanes_render.hip
+// (`a` checked by lp_api.hip; n_rays > 0)
+int kplanes_render_launch(const LpKPlanesRenderArgs& a, bool backward, hipStream_t stream);
+LpKPlanesArgs kplanes_render_view(const LpKPlanesRenderArgs& a);        // its layout, planes, times and flags as an LpKPlanesArgs (n_pts = n_samples)
+int kplanes_render_backward_total_width(const LpKPlanesRenderArgs& a);  // sum of the layer widths the backward keeps per sample (<= 1024)
+const char* build_info_kplanes_render();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -28,6 +28,15 @@ rays_encoding[r]))[:color_chn] occ``, ``occ`` the scaffold's nearest-neighbour v
 -> composite_samples`` is a differentiable renderer of a time-dependent field.  One autograd function that keeps its inputs only;
 gradients go to ``planes``, ``decoder_params.mlp_params``, ``rays_encoding`` and ``points``, a gradient nobody asks for is not computed,
 and without an upstream colour gradient the colour head is not evaluated (its parameters get exactly 0).
+
+**The render along rays, in one launch.**  ``kplanes_render_samples`` (``csrc/lp_kplanes_render.hip``; C ABI
+``lp_kplanes_render_forward`` / ``lp_kplanes_render_backward``) is that chain fused: it forms every sample's point
+``depth * direction + origin`` in registers, decodes it as ``kplanes_eval_mlp`` does and composites as ``composite_samples`` does
+(``w_s = exp(-sum_{j<s} opacity_j delta_j) (-expm1(-opacity_s delta_s))``), one wavefront per ray, so no ``[R, S]`` points, opacity or
+colour tensor exists in either direction -- it means what ``hash_grid_render_samples`` means, on the only field here that reads time.
+One autograd function that keeps its inputs and one ``chunk_nlt [R, ceil(S / 64)]`` buffer; gradients go to ``planes``,
+``decoder_params.mlp_params`` and ``rays.encoding`` (stored, bit-reproducible); ``depths``, ``deltas``, the ray origins and directions
+and ``times`` get none (the modular chain differentiates with respect to the first four).
 """
 from __future__ import annotations
 
@@ -38,8 +47,11 @@ import torch
 
 from . import _lib
 from .params import DecoderParams, int_list_of
+from .rays import Rays
+from .render_samples import chunks
 
-__all__ = ["KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only"]
+__all__ = ["KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only",
+           "kplanes_render_samples"]
 
 
 class KPlanesLayout(NamedTuple):
@@ -178,7 +190,11 @@ def _check_inputs(points, times, planes, ray_grid_idx, layout) -> None:
     if not isinstance(layout, KPlanesLayout):
         raise ValueError("layout has to be the KPlanesLayout of kplanes_layout()")
     assert torch.is_tensor(points) and points.ndim == 3 and points.shape[-1] == 3, "points has to be a [n_rays, n_pts, 3] tensor"
-    n_rays, n_pts = points.shape[0], points.shape[1]
+    _check_field(points.shape[0], points.shape[1], times, planes, ray_grid_idx, layout)
+
+
+def _check_field(n_rays: int, n_pts: int, times, planes, ray_grid_idx, layout) -> None:
+    """... of the times, planes and ray_grid_idx of ``n_rays`` rows of ``n_pts`` points (or samples)"""
     assert torch.is_tensor(ray_grid_idx) and tuple(ray_grid_idx.shape) == (n_rays,), f"ray_grid_idx has to be a [{n_rays}] tensor"
     assert not ray_grid_idx.is_floating_point() and not ray_grid_idx.is_complex() and ray_grid_idx.dtype != torch.bool, (
         "ray_grid_idx has to have an integer dtype")
@@ -337,3 +353,169 @@ def kplanes_eval_mlp_opacity_only(points, times, planes, ray_grid_idx, layout: K
     encoding, and the colour MLP's parameters are never read (they get exactly zero gradient)."""
     return _eval(points, times, planes, ray_grid_idx, layout, decoder_params, None, gain, mask_out_of_bounds_samples, contract_coords,
                  scaffold, True)
+
+
+class _RenderCfg(NamedTuple):
+    planes: _Cfg
+    dims_t: tuple
+    dims_o: tuple
+    dims_c: tuple
+    color_chn: int
+    gain: float
+    return_weights: bool
+    with_color: bool
+
+
+def _render_args(cfg: _RenderCfg, origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding,
+                 with_color: bool) -> _lib.LpKPlanesRenderArgs:
+    lay = cfg.planes.layout
+    a = _lib.LpKPlanesRenderArgs()
+    a.planes, a.batch, a.rows = _lib.ptr(planes), planes.shape[0], lay.rows
+    a.channels, a.n_scales, a.n_planes = lay.channels, lay.n_scales, lay.n_planes
+    for s in range(lay.n_scales):
+        a.spatial[s] = lay.spatial[s]
+        a.temporal[s] = lay.temporal[s] if lay.temporal else 0
+        for j in range(lay.n_planes):
+            a.offset[s][j] = lay.offsets[s][j]
+    a.times, a.time_per_sample = _lib.ptr(times), int(times is not None and times.ndim == 2)
+    a.mask_out_of_bounds, a.contract_coords = int(cfg.planes.mask), int(cfg.planes.contract)
+    a.mlp_params, a.n_mlp_params = _lib.ptr(mlp_params), mlp_params.numel()
+    _lib.make_decoder(a, cfg.dims_t, cfg.dims_o, cfg.dims_c)
+    a.color_chn, a.gain = cfg.color_chn, cfg.gain
+    a.origins, a.directions, a.grid_idx = _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(grid_idx)
+    if with_color:
+        a.encoding, a.encoding_dim = _lib.ptr(encoding), encoding.shape[1]
+    a.n_rays, a.n_samples = depths.shape
+    a.depths, a.deltas = _lib.ptr(depths), _lib.ptr(deltas)
+    if scaffold is not None:
+        a.scaffold = _lib.ptr(scaffold)
+        a.scaffold_shape = _lib.LpGrid(*[int(v) for v in scaffold.shape], 0, None)
+    return a
+
+
+class _KPlanesRender(torch.autograd.Function):
+    """(ray_length, -log T[, feature][, weights]) = render(depths, deltas; planes, times, decoder, encoding): one forward launch; the
+    backward is one launch that recomputes every sample and fills the gradients ``needs_input_grad`` asks for (a gradient nobody asks
+    for is a NULL pointer: its work is skipped; a result nobody differentiated is a NULL upstream gradient).  Kept for it: the inputs
+    and ``chunk_nlt [R, ceil(S / 64)]``."""
+
+    @staticmethod
+    def forward(ctx, cfg: _RenderCfg, origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding):
+        dev = depths.device
+        stream = _lib.current_stream(dev)
+        origins, directions, depths, deltas, mlp_params = (
+            _lib.aligned(t.contiguous()) for t in (origins, directions, depths, deltas, mlp_params))
+        times = None if times is None else _lib.aligned(times.contiguous())
+        planes = _lib.aligned(planes.contiguous(), grid=True)
+        encoding = _lib.aligned(encoding.contiguous()) if cfg.with_color else None
+        n, s = depths.shape
+        with torch.cuda.device(dev):
+            length = torch.empty(n, device=dev, dtype=torch.float32)
+            nlt = torch.empty(n, device=dev, dtype=torch.float32)
+            feature = torch.empty(n, cfg.color_chn, device=dev, dtype=torch.float32) if cfg.with_color else None
+            weights = torch.empty(n, s, device=dev, dtype=torch.float32) if cfg.return_weights else None
+            chunk_nlt = torch.empty(n, chunks(s), device=dev, dtype=torch.float32)
+            a = _render_args(cfg, origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding,
+                             cfg.with_color)
+            a.ray_length, a.neg_log_t, a.feature, a.weights = (_lib.ptr(t) for t in (length, nlt, feature, weights))
+            a.chunk_nlt = _lib.ptr(chunk_nlt)
+            if n:  # (an empty batch has no tensors to point at)
+                _call("lp_kplanes_render_forward", a, stream)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding, chunk_nlt)
+        return tuple(t for t in (length, nlt, feature, weights) if t is not None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_len, g_nlt, *rest):
+        cfg: _RenderCfg = ctx.cfg
+        origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding, chunk_nlt = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        rest = list(rest)
+        g_feat = rest.pop(0) if cfg.with_color else None
+        g_w = rest.pop(0) if cfg.return_weights else None
+        ups = (g_len, g_nlt, g_feat, g_w)
+        if all(g is None for g in ups) or not any(need):
+            return (None,) * 11
+        dev = depths.device
+        stream = _lib.current_stream(dev)
+        g_len, g_nlt, g_feat, g_w = (None if g is None else _lib.aligned(g.to(torch.float32).contiguous()) for g in ups)
+        with_color = g_feat is not None
+        with torch.cuda.device(dev):
+            d_planes = torch.zeros_like(planes) if need[8] else None
+            d_params = torch.zeros_like(mlp_params) if need[9] else None
+            d_enc = torch.empty_like(encoding) if (need[10] and encoding is not None) else None  # (written entirely)
+            a = _render_args(cfg, origins, directions, grid_idx, times, depths, deltas, scaffold, planes, mlp_params, encoding, with_color)
+            a.chunk_nlt = _lib.ptr(chunk_nlt)
+            a.grad_ray_length, a.grad_neg_log_t, a.grad_feature, a.grad_weights = (_lib.ptr(g) for g in (g_len, g_nlt, g_feat, g_w))
+            a.grad_planes, a.grad_mlp_params, a.grad_encoding = _lib.ptr(d_planes), _lib.ptr(d_params), _lib.ptr(d_enc)
+            if d_enc is not None:
+                a.encoding_dim = encoding.shape[1]  # (without an upstream for the feature the kernel stores zeros: the row length)
+            if depths.shape[0]:
+                _call("lp_kplanes_render_backward", a, stream)
+        return None, None, None, None, None, None, None, None, d_planes, d_params, d_enc
+
+
+def kplanes_render_samples(rays: Rays, times, depths: torch.Tensor, deltas: torch.Tensor, planes: torch.Tensor, layout: KPlanesLayout,
+                           decoder_params: DecoderParams, *, gain: float = 1.0, mask_out_of_bounds_samples: bool = False,
+                           contract_coords: bool = False, scaffold: Optional[torch.Tensor] = None, return_weights: bool = False,
+                           with_color: bool = True):
+    """``(ray_length_render [R], negative_log_transmittance [R], feature_render [R, color_chn])`` of ``rays`` marched through the plane
+    field ``planes`` / ``layout`` / ``decoder_params`` at the caller's ``depths [R, S]`` with the interval lengths ``deltas [R, S]``
+    (fp32: ``RaySamples.depths`` / ``.deltas`` of ``ray_samples`` or ``importance_samples``) at ``times`` (``[R]`` or ``[R, S]``, read
+    as it is -- no expanded copy; ``None`` for a static layout); with ``return_weights=True`` a fourth result, the compositing weights
+    ``w [R, S]``.  Any ``S >= 1`` with ``R * S < 2^31``.
+
+    Of ``rays`` the op reads ``origins``, ``directions``, ``grid_idx`` and ``encoding``.  ``planes``, ``layout``, ``decoder_params``,
+    ``gain``, ``mask_out_of_bounds_samples``, ``contract_coords`` and ``scaffold`` mean what they mean in ``kplanes_eval_mlp``.
+    ``with_color=False`` (the coarse / proposal pass that only wants weights): ``feature_render`` is ``None``, the colour MLP and
+    ``rays.encoding`` are never read in either direction, and the other results are the same bit for bit.  Differentiable with
+    respect to ``planes``, ``decoder_params.mlp_params`` and ``rays.encoding``; ``depths``, ``deltas``, ``rays.origins``,
+    ``rays.directions`` and ``times`` must not require a gradient (module docstring)."""
+    assert isinstance(rays, Rays), f"rays has to be a Rays object, got {type(rays).__name__}"
+    assert torch.is_tensor(depths) and depths.ndim == 2, "depths has to be a [n_rays, n_samples] tensor"
+    n, s = depths.shape
+    assert s >= 1, "depths has to have one sample per ray at least"
+    assert torch.is_tensor(deltas) and tuple(deltas.shape) == (n, s), f"deltas has to be a [{n}, {s}] tensor, as depths is"
+    assert n * s < 2 ** 31, f"depths: {n} rays x {s} samples: n_rays * n_samples has to stay below 2^31 (split the batch)"
+    for name, t in (("rays.origins", rays.origins), ("rays.directions", rays.directions)):
+        assert torch.is_tensor(t) and tuple(t.shape) == (n, 3), f"{name} has to be a [{n}, 3] tensor: one ray per row of depths"
+    if torch.is_grad_enabled():
+        for name, t in (("depths", depths), ("deltas", deltas), ("rays.origins", rays.origins), ("rays.directions", rays.directions),
+                        ("times", times)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(
+                    f"{name} requires a gradient, and kplanes_render_samples produces none for depths, deltas, ray origins and "
+                    f"directions and times: pass {name}.detach(), or use the modular chain (ray_samples / importance_samples -> "
+                    "kplanes_eval_mlp -> composite_samples), which differentiates with respect to the first four")
+    if not isinstance(layout, KPlanesLayout):
+        raise ValueError("layout has to be the KPlanesLayout of kplanes_layout()")
+    _check_field(n, s, times, planes, rays.grid_idx, layout)
+    dims_t, dims_o, dims_c = (tuple(int_list_of(v)) for v in (decoder_params.n_hidden_trunk, decoder_params.n_hidden_opacity,
+                                                              decoder_params.n_hidden_color))
+    width = dims_t[0] if len(dims_t) > 1 else dims_o[0]
+    if width != layout.out_channels:
+        raise ValueError(f"the decoder reads {width} features, the layout has n_scales x channels = {layout.out_channels}")
+    encoding = rays.encoding if with_color else None
+    if with_color:
+        assert torch.is_tensor(encoding) and tuple(encoding.shape) == (n, dims_c[0]), (
+            f"rays.encoding has to be a [{n}, {dims_c[0]}] tensor (the colour head's input width)")
+    mlp_params = decoder_params.mlp_params
+    assert mlp_params.ndim == 1, "decoder_params.mlp_params has to be the flat parameter vector"
+    if scaffold is not None:
+        assert torch.is_tensor(scaffold) and scaffold.ndim == 4, "scaffold has to be a [B, D, H, W] tensor"
+    dev = depths.device
+    _lib.check_tensors(dev, {"depths": depths, "deltas": deltas, "rays.origins": rays.origins, "rays.directions": rays.directions,
+                             "times": times, "planes": planes, "decoder_params.mlp_params": mlp_params, "rays.encoding": encoding,
+                             "scaffold": scaffold}, {"rays.grid_idx": rays.grid_idx})
+    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    grid_idx = _lib.int32_index(rays.grid_idx)
+    scaffold = None if scaffold is None else _lib.aligned(scaffold.detach().contiguous())
+    cfg = _RenderCfg(_Cfg(layout, bool(mask_out_of_bounds_samples), bool(contract_coords)), dims_t, dims_o, dims_c,
+                     int(decoder_params.color_chn), float(gain), bool(return_weights), bool(with_color))
+    out = _KPlanesRender.apply(cfg, rays.origins.detach(), rays.directions.detach(), grid_idx, None if times is None else times.detach(),
+                               depths.detach(), deltas.detach(), scaffold, planes, mlp_params, encoding)
+    if with_color:
+        return out
+    return (out[0], out[1], None) + tuple(out[2:])
