@@ -74,7 +74,9 @@ the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
 ``--kplanes`` (with ``--modular``) fits a third student: static planes at three scales (``lp.kplanes_layout((16, 32, 64), None, 8)``,
 ``lp.init_kplanes``) and a 2/2/2 x 32 decoder, rendered through ``lp.ray_samples -> lp.kplanes_eval_mlp -> lp.composite_samples`` --
 encoding and decoder in one launch, no feature tensor -- or, with ``--render-samples``, through ``lp.kplanes_render_samples``: encoding,
-decoder and compositing in one launch, no per-sample tensor; the other flags do not apply (the JSON line gains ``kplanes``).
+decoder and compositing in one launch, no per-sample tensor; of the other flags only ``--tv-weight w`` applies: after ``loss.backward()``,
+``lp.add_kplanes_reg_grad_(planes, planes.grad, layout, weights=(w, 0, 0))`` adds ``w`` times the gradient of the planes' spatial total
+variation in one sweep (the JSON line gains ``kplanes`` and, with it, ``tv_weight``, ``first_space_tv`` and ``last_space_tv``).
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -313,10 +315,11 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
             "render_samples": bool(fused), "importance": int(importance)}
 
 
-def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8, fused=False):
+def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8, fused=False,
+                tv_weight=0.0):
     """the fit of ``fit`` with static planes (``time_resolution=None``: the Hadamard tri-plane) + decoder as the student, through
     ray_samples -> kplanes_eval_mlp -> composite_samples or, ``fused``, through ``lp.kplanes_render_samples`` (one launch, no per-sample
-    tensors)"""
+    tensors); ``tv_weight`` > 0: plus that many times the planes' spatial total variation (``lp.add_kplanes_reg_grad_``)"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -338,7 +341,7 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
         _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
         return 1.0 - torch.exp(-nlt), rgb
 
-    losses = []
+    losses, tvs = [], []
     for it in range(steps):
         rays = random_rays(n_rays, gen, dev)
         with torch.no_grad():
@@ -347,6 +350,8 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
         loss = ((rgb - tgt_rgb) ** 2).mean() + 0.1 * ((alpha - tgt_alpha) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
+        if tv_weight > 0.0:
+            tvs.append(lp.add_kplanes_reg_grad_(planes.detach(), planes.grad, lay, weights=(tv_weight, 0.0, 0.0)))
         opt.step()
         losses.append(float(loss.detach()))
         if verbose and (it % 50 == 0 or it == steps - 1):
@@ -355,9 +360,12 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
     with torch.no_grad():
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
-    return {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
-            "rays_per_step": n_rays, "modular": True, "kplanes": True, "resolutions": list(resolutions), "channels": channels,
-            "plane_rows": lay.rows, "render_samples": bool(fused)}
+    out = {"first_loss": sum(losses[:5]) / 5, "last_loss": sum(losses[-5:]) / 5, "heldout_psnr_db": psnr, "steps": steps,
+           "rays_per_step": n_rays, "modular": True, "kplanes": True, "resolutions": list(resolutions), "channels": channels,
+           "plane_rows": lay.rows, "render_samples": bool(fused)}
+    if tv_weight > 0.0:
+        out.update(tv_weight=tv_weight, first_space_tv=float(tvs[0][0]), last_space_tv=float(tvs[-1][0]))
+    return out
 
 
 def write_ply(path, vertices, faces, normals, colors):
@@ -431,7 +439,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.kplanes:
         assert a.modular, "--kplanes renders through the modular march: pass --modular as well"
-        out = fit_kplanes(a.steps, a.rays, verbose=True, fused=a.render_samples)
+        out = fit_kplanes(a.steps, a.rays, verbose=True, fused=a.render_samples, tv_weight=a.tv_weight)
         print(json.dumps(out))
         return out
     if a.hash_grid:

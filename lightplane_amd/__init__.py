@@ -26,7 +26,8 @@ from .renderer import LightplaneFunction, backward_segments, forward_kernel_fami
 from .splatter import (LightplaneMLPSplatterFunction, LightplaneSplatterFunction, lightplane_mlp_splatter,  # noqa: E402
                        lightplane_splatter, mlp_splatter_kernel_family)
 from .modules import LightplaneMLPSplatter, LightplaneRenderer, LightplaneSplatter  # noqa: E402
-from .regularizers import add_grid_tv_grad_, grid_tv_loss, grid_tv_workspace_bytes  # noqa: E402
+from .regularizers import (add_grid_tv_grad_, add_kplanes_reg_grad_, grid_tv_loss, grid_tv_workspace_bytes,  # noqa: E402
+                           kplanes_reg_workspace_bytes, kplanes_regularizers)
 from .resample import grid_resample, grid_up_sample, resampled_sizes  # noqa: E402
 from .scaffold import calculate_scaffold, scaffold_opacity, scaffold_workspace_bytes  # noqa: E402
 from .points import lightplane_eval_mlp, lightplane_eval_mlp_opacity_only  # noqa: E402
@@ -76,6 +77,7 @@ __all__ = [
     "HashGridLayout", "hash_grid_layout", "init_hash_grid", "hash_grid_encode",
     "hash_grid_eval_mlp", "hash_grid_eval_mlp_opacity_only", "hash_grid_render_samples",
     "KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only", "kplanes_render_samples",
+    "kplanes_regularizers", "add_kplanes_reg_grad_", "kplanes_reg_workspace_bytes",
 ]
 
 _NOT_PROVIDED = {

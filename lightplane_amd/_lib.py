@@ -310,6 +310,17 @@ class LpKPlanesRenderArgs(C.Structure):  # include/lightplane_hip_kplanes_render
     ]
 
 
+class LpKPlanesRegArgs(C.Structure):  # include/lightplane_hip_kplanes_reg.h
+    _fields_ = [
+        ("planes", C.c_void_p), ("grad_planes", C.c_void_p), ("terms", C.c_void_p), ("grad_terms", C.c_void_p), ("rows", C.c_int64),
+        ("offset", C.c_int64 * LP_KPLANES_MAX_PLANES * LP_KPLANES_MAX_SCALES),
+        ("spatial", C.c_int32 * LP_KPLANES_MAX_SCALES), ("temporal", C.c_int32 * LP_KPLANES_MAX_SCALES),
+        ("weights", C.c_float * 3),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("n_scales", C.c_int32), ("n_planes", C.c_int32),
+        ("p", C.c_int32), ("accumulate", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -367,6 +378,9 @@ KPLANES_POINTS_EXPORTS = ("lp_kplanes_points_forward", "lp_kplanes_points_backwa
 
 #: every symbol include/lightplane_hip_kplanes_render.h declares (and again)
 KPLANES_RENDER_EXPORTS = ("lp_kplanes_render_forward", "lp_kplanes_render_backward")
+
+#: every symbol include/lightplane_hip_kplanes_reg.h declares (and again)
+KPLANES_REG_EXPORTS = ("lp_kplanes_reg_workspace_bytes", "lp_kplanes_reg_forward", "lp_kplanes_reg_backward", "lp_kplanes_reg_fused")
 
 
 def _signatures():
@@ -436,6 +450,10 @@ def _signatures():
         (KPLANES_POINTS_EXPORTS, C.c_int, (P(LpKPlanesPointsArgs), vp)),
         # a plane field rendered along rays at caller-given depths (include/lightplane_hip_kplanes_render.h): args, stream
         (KPLANES_RENDER_EXPORTS, C.c_int, (P(LpKPlanesRenderArgs), vp)),
+        # the regularisers of a plane field (include/lightplane_hip_kplanes_reg.h): args (, workspace, workspace bytes), stream
+        (KPLANES_REG_EXPORTS[:1], i64, (P(LpKPlanesRegArgs),)),
+        (KPLANES_REG_EXPORTS[1:2] + KPLANES_REG_EXPORTS[3:], C.c_int, (P(LpKPlanesRegArgs), vp, i64, vp)),
+        (KPLANES_REG_EXPORTS[2:3], C.c_int, (P(LpKPlanesRegArgs), vp)),
     )
 
 
@@ -475,7 +493,8 @@ def lib() -> C.CDLL:
                       (46, LpHashRenderArgs),  # (nor 44, 45 and 47: lightplane_hip_hash_render.h)
                       (50, LpKPlanesArgs),  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
                       (54, LpKPlanesPointsArgs),  # (nor 52, 53 and 55: lightplane_hip_kplanes_points.h)
-                      (58, LpKPlanesRenderArgs)):  # (nor 56, 57 and 59: lightplane_hip_kplanes_render.h)
+                      (58, LpKPlanesRenderArgs),  # (nor 56, 57 and 59: lightplane_hip_kplanes_render.h)
+                      (62, LpKPlanesRegArgs)):  # (nor 60, 61 and 63: lightplane_hip_kplanes_reg.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

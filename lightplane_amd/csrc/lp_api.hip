@@ -1036,6 +1036,41 @@ static int check_kplanes(const char* what, const LpKPlanesArgs* args, int mode) 
   return LP_OK;
 }
 
+// everything the lp_kplanes_reg_* entry points check: the layout as lp_kplanes_* (through a copy of its fields), p, the pointers the
+// call uses and the workspace.  want_terms: terms are written (forward, fused); want_grad: grad_planes is (backward, fused).
+static int check_kplanes_reg_layout(const char* what, const LpKPlanesRegArgs* args) {
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LpKPlanesArgs k = {};
+  k.rows = args->rows;
+  memcpy(k.offset, args->offset, sizeof(k.offset));
+  memcpy(k.spatial, args->spatial, sizeof(k.spatial));
+  memcpy(k.temporal, args->temporal, sizeof(k.temporal));
+  k.batch = args->batch, k.channels = args->channels, k.n_scales = args->n_scales, k.n_planes = args->n_planes;
+  return check_kplanes_layout(what, k);
+}
+
+static int check_kplanes_reg(const char* what, const LpKPlanesRegArgs* args, bool want_terms, bool want_grad, const void* workspace,
+                             int64_t workspace_bytes) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, grad_planes);
+  LP_ALIGNED(*args, terms);
+  LP_ALIGNED(*args, grad_terms);
+  if ((rc = check_kplanes_reg_layout(what, args))) return rc;
+  if (args->p != 1 && args->p != 2) return set_error(LP_EINVAL, "%s: p = %d, has to be 1 (|d|) or 2 (d^2)", what, args->p);
+  if (!args->planes) return set_error(LP_ENULL, "planes is NULL");
+  if (want_terms && !args->terms) return set_error(LP_ENULL, "terms is NULL");
+  if (want_grad && !args->grad_planes) return set_error(LP_ENULL, "grad_planes is NULL");
+  if (want_grad && args->grad_planes == args->planes) return set_error(LP_EINVAL, "%s: grad_planes aliases planes", what);
+  const int64_t groups = kplanes_reg_workgroups(*args);
+  if (groups > LP_MAX_WORKGROUPS)
+    return set_error(LP_EUNSUPPORTED, "%s: %lld workgroups, a launch has at most 2^31 - 1", what, (long long)groups);
+  if (want_terms)
+    return check_workspace(what, "lp_kplanes_reg_workspace_bytes", workspace, workspace_bytes, groups * 3 * (int64_t)sizeof(double), 8, LP_ENULL);
+  return LP_OK;
+}
+
 // everything lp_kplanes_points_forward / lp_kplanes_points_backward check: the layout as lp_kplanes_*, the decoder, the scaffold and
 // the alignment as lp_hash_points_*.  `color`: the colour head takes part (forward: color_out given; backward: grad_color given) --
 // only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
@@ -1253,12 +1288,12 @@ static int check_kplanes_render(const char* what, const LpKPlanesRenderArgs* arg
 // decoder fused on it (lp_kplanes_points.hip) and its render along rays (lp_kplanes_render.hip): the top-level keys of the text stay as
 // they are
 static const char* build_info_points_family() {
-  static char text[7168];  // (the six texts together: ~5.4 KB; lp_build_info() holds 16 KB)
+  static char text[7168];  // (the seven texts together: ~5.8 KB; lp_build_info() holds 16 KB)
   const char* p = build_info_points();
   snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s, \"kplanes_points\": %s, "
-           "\"kplanes_render\": %s}",
+           "\"kplanes_render\": %s, \"kplanes_reg\": %s}",
            (int)strlen(p) - 1, p, build_info_render_samples(), build_info_hash_render(), build_info_kplanes(), build_info_kplanes_points(),
-           build_info_kplanes_render());
+           build_info_kplanes_render(), build_info_kplanes_reg());
   return text;
 }
 
@@ -1324,6 +1359,7 @@ int lp_abi_sizeof(int which) {
     case 50: return (int)sizeof(LpKPlanesArgs);  // (and 48, 49, 51: lightplane_hip_kplanes.h)
     case 54: return (int)sizeof(LpKPlanesPointsArgs);  // (and 52, 53, 55: lightplane_hip_kplanes_points.h)
     case 58: return (int)sizeof(LpKPlanesRenderArgs);  // (and 56, 57, 59: lightplane_hip_kplanes_render.h)
+    case 62: return (int)sizeof(LpKPlanesRegArgs);  // (and 60, 61, 63: lightplane_hip_kplanes_reg.h)
     default: return -1;
   }
 }
@@ -1838,6 +1874,29 @@ int lp_kplanes_render_backward(const LpKPlanesRenderArgs* args, void* stream) {
   const int rc = check_kplanes_render("lp_kplanes_render_backward", args, true);
   if (rc != LP_OK || args->n_rays == 0) return rc;
   return kplanes_render_launch(*args, true, (hipStream_t)stream);
+}
+
+int64_t lp_kplanes_reg_workspace_bytes(const LpKPlanesRegArgs* args) {
+  if (check_kplanes_reg_layout("lp_kplanes_reg_workspace_bytes", args) != LP_OK) return 0;
+  return kplanes_reg_workgroups(*args) * 3 * (int64_t)sizeof(double);
+}
+
+int lp_kplanes_reg_forward(const LpKPlanesRegArgs* args, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = check_kplanes_reg("lp_kplanes_reg_forward", args, true, false, workspace, workspace_bytes);
+  if (rc != LP_OK) return rc;
+  return kplanes_reg_launch(*args, (double*)workspace, false, (hipStream_t)stream);
+}
+
+int lp_kplanes_reg_backward(const LpKPlanesRegArgs* args, void* stream) {
+  const int rc = check_kplanes_reg("lp_kplanes_reg_backward", args, false, true, nullptr, 0);
+  if (rc != LP_OK) return rc;
+  return kplanes_reg_launch(*args, nullptr, true, (hipStream_t)stream);
+}
+
+int lp_kplanes_reg_fused(const LpKPlanesRegArgs* args, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = check_kplanes_reg("lp_kplanes_reg_fused", args, true, true, workspace, workspace_bytes);
+  if (rc != LP_OK) return rc;
+  return kplanes_reg_launch(*args, (double*)workspace, true, (hipStream_t)stream);
 }
 
 int lp_hash_render_forward(const LpHashRenderArgs* args, void* stream) {

@@ -15,6 +15,7 @@
 #include "../../include/lightplane_hip_kplanes.h"
 #include "../../include/lightplane_hip_kplanes_points.h"
 #include "../../include/lightplane_hip_kplanes_render.h"
+#include "../../include/lightplane_hip_kplanes_reg.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -213,6 +214,11 @@ int kplanes_render_launch(const LpKPlanesRenderArgs& a, bool backward, hipStream
 LpKPlanesArgs kplanes_render_view(const LpKPlanesRenderArgs& a);        // its layout, planes, times and flags as an LpKPlanesArgs (n_pts = n_samples)
 int kplanes_render_backward_total_width(const LpKPlanesRenderArgs& a);  // sum of the layer widths the backward keeps per sample (<= 1024)
 const char* build_info_kplanes_render();
+// the three regularisers of a plane field: lp_kplanes_reg.hip (`a` checked by lp_api.hip; workspace != NULL: the terms into a.terms
+// through it; want_grad: the gradient into a.grad_planes, written or added as a.accumulate says; both: the fused sweep)
+int64_t kplanes_reg_workgroups(const LpKPlanesRegArgs& a);  // of the sweep; three doubles of workspace each
+int kplanes_reg_launch(const LpKPlanesRegArgs& a, double* workspace, bool want_grad, hipStream_t stream);
+const char* build_info_kplanes_reg();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

@@ -1,4 +1,5 @@
-"""Regularisers of a grid-list, fused into HIP sweeps (``csrc/lp_grid_tv.hip``; C ABI ``lp_grid_tv_*``).
+"""Regularisers of a grid-list (``csrc/lp_grid_tv.hip``; C ABI ``lp_grid_tv_*``) and of a K-Planes field (``csrc/lp_kplanes_reg.hip``;
+C ABI ``lp_kplanes_reg_*``), fused into HIP sweeps.
 
 Total variation of one grid ``x`` of shape ``[B, D, H, W, C]``, ``p`` in {1, 2} (``phi_1(d) = |d|``, ``phi_2(d) = d ** 2``)::
 
@@ -10,6 +11,16 @@ i.e. ``(g[:, 1:] - g[:, :-1]).abs().mean()`` per axis, summed -- without the ful
 for autograd, and on the layouts the kernels take: a list of ``[B, D, H, W, C]`` tensors that is never concatenated, or the flat
 ``[sum BDHW, C]`` tensor with ``grid_sizes``.  A plane ``[B, 1, H, W, C]`` gets the 2-D TV of its plane; the derivative of ``|d|``
 at 0 is 0, as ``torch.abs`` has it.  No atomics (bit-reproducible), no host synchronisation (graph-capturable).
+
+The three regularisers of a plane field ``planes [B, layout.rows, C]`` (``kplanes.py``), with plane ``j`` of scale ``s`` read as
+``X = planes[:, off : off + n_u * n_v].view(B, n_v, n_u, C)`` (xy / xz / yz: ``n_u = n_v = spatial[s]``; xt / yt / zt: ``n_u =
+spatial[s]``, ``n_v = temporal[s]``, the time axis)::
+
+    space_tv        = sum over planes of  phi_p(X[:, :, 1:] - X[:, :, :-1]).mean()  (+ the same along n_v on xy / xz / yz)
+    time_smoothness = sum over xt / yt / zt of  ((X[:, 2:] - 2 X[:, 1:-1] + X[:, :-2]) ** 2).mean()   (0 where temporal[s] == 2)
+    time_l1         = sum over xt / yt / zt of  (1 - X).abs().mean()
+
+in one sweep over the field for all scenes, scales and planes, again without atomics or host synchronisation.
 """
 from __future__ import annotations
 
@@ -20,8 +31,10 @@ import torch
 
 from . import _lib
 from .grids import GridForm
+from .kplanes import KPlanesLayout
 
-__all__ = ["grid_tv_loss", "add_grid_tv_grad_", "grid_tv_workspace_bytes"]
+__all__ = ["grid_tv_loss", "add_grid_tv_grad_", "grid_tv_workspace_bytes",
+           "kplanes_regularizers", "add_kplanes_reg_grad_", "kplanes_reg_workspace_bytes"]
 
 
 def _weights(grid_weights, n: int):
@@ -140,3 +153,128 @@ def add_grid_tv_grad_(grid, grad, weight: float = 1.0, p: int = 1, grid_sizes=No
         _lib.check(L.lp_grid_tv_fused(ctypes.byref(gl), w, nw, int(p), loss.data_ptr(), workspace.data_ptr(), ws_bytes, None,
                                       float(weight), *_grad_args(form, grads), _lib.current_stream(dev)), "lp_grid_tv_fused")
     return loss
+
+
+def _reg_args(layout: KPlanesLayout, batch: int, p: int = 2) -> _lib.LpKPlanesRegArgs:
+    """the layout, the batch and ``p`` in a fresh ``LpKPlanesRegArgs``"""
+    if not isinstance(layout, KPlanesLayout):
+        raise ValueError("layout has to be the KPlanesLayout of kplanes_layout()")
+    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
+    a = _lib.LpKPlanesRegArgs()
+    a.batch, a.rows, a.p = int(batch), layout.rows, int(p)
+    a.channels, a.n_scales, a.n_planes = layout.channels, layout.n_scales, layout.n_planes
+    for s in range(layout.n_scales):
+        a.spatial[s] = layout.spatial[s]
+        a.temporal[s] = layout.temporal[s] if layout.temporal else 0
+        for j in range(layout.n_planes):
+            a.offset[s][j] = layout.offsets[s][j]
+    return a
+
+
+def _check_planes(planes, layout) -> None:
+    if not isinstance(layout, KPlanesLayout):
+        raise ValueError("layout has to be the KPlanesLayout of kplanes_layout()")
+    if not torch.is_tensor(planes) or planes.ndim != 3 or planes.shape[0] < 1 or tuple(planes.shape[1:]) != (layout.rows, layout.channels):
+        shape = tuple(planes.shape) if torch.is_tensor(planes) else type(planes).__name__
+        raise ValueError(f"planes has to be a [B, {layout.rows}, {layout.channels}] tensor for this layout (got {shape})")
+
+
+def kplanes_reg_workspace_bytes(layout: KPlanesLayout, batch: int = 1) -> int:
+    """Bytes of device workspace one evaluation of the three terms takes for ``batch`` scenes of this layout
+    (``lp_kplanes_reg_workspace_bytes``; shapes only, no GPU)."""
+    a = _reg_args(layout, batch)
+    n = int(_lib.lib().lp_kplanes_reg_workspace_bytes(ctypes.byref(a)))
+    if n <= 0:
+        _lib.check(-1, "lp_kplanes_reg_workspace_bytes")
+    return n
+
+
+def _reg_terms(a: _lib.LpKPlanesRegArgs, entry: str, dev) -> torch.Tensor:
+    """run the entry point that writes the terms: the workspace and the ``[3]`` result are the only allocations"""
+    L = _lib.lib()
+    ws_bytes = int(L.lp_kplanes_reg_workspace_bytes(ctypes.byref(a)))
+    workspace = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+    terms = torch.empty(3, dtype=torch.float32, device=dev)
+    a.terms = terms.data_ptr()
+    _lib.check(getattr(L, entry)(ctypes.byref(a), workspace.data_ptr(), ws_bytes, _lib.current_stream(dev)), entry)
+    return terms
+
+
+class _KPlanesReg(torch.autograd.Function):
+    """terms = the three regularisers of planes: forward = one sweep + the fp64 sum of its partials; backward = one gather sweep that
+    WRITES grad_planes, scaled on the device by the upstream ``[3]`` gradient (rows of no plane, if the layout has gaps, are zero)."""
+
+    @staticmethod
+    def forward(ctx, cfg, planes):
+        layout, p = cfg
+        dev = planes.device
+        planes = _lib.aligned(planes.contiguous(), grid=True)
+        with torch.cuda.device(dev):
+            a = _reg_args(layout, planes.shape[0], p)
+            a.planes = planes.data_ptr()
+            terms = _reg_terms(a, "lp_kplanes_reg_forward", dev)
+        ctx.cfg = cfg
+        ctx.save_for_backward(planes)
+        return terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_terms):
+        layout, p = ctx.cfg
+        (planes,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        dev = planes.device
+        g_terms = _lib.aligned(g_terms.to(device=dev, dtype=torch.float32).contiguous())
+        with torch.cuda.device(dev):
+            # (planes do not overlap: they cover every row exactly when their sizes add up to it, as kplanes_layout() has it)
+            grad = torch.empty_like(planes) if _plane_rows(layout) == layout.rows else torch.zeros_like(planes)
+            a = _reg_args(layout, planes.shape[0], p)
+            a.planes, a.grad_planes, a.grad_terms = planes.data_ptr(), grad.data_ptr(), g_terms.data_ptr()
+            a.weights[0] = a.weights[1] = a.weights[2] = 1.0
+            _lib.check(_lib.lib().lp_kplanes_reg_backward(ctypes.byref(a), _lib.current_stream(dev)), "lp_kplanes_reg_backward")
+        return None, grad
+
+
+def _plane_rows(layout: KPlanesLayout) -> int:
+    """rows that belong to a plane"""
+    return sum(n * (3 * n + (3 * layout.temporal[s] if layout.n_planes == 6 else 0)) for s, n in enumerate(layout.spatial))
+
+
+def kplanes_regularizers(planes: torch.Tensor, layout: KPlanesLayout, *, p: int = 2) -> torch.Tensor:
+    """``terms [3]`` = ``(space_tv, time_smoothness, time_l1)`` of a plane field (module docstring), fp32 on the device, differentiable
+    with respect to ``planes [B, layout.rows, C]``; the caller forms the weighted sum.  ``p``: 1 or 2, the ``phi_p`` of ``space_tv``.
+    A static layout has ``time_smoothness == time_l1 == 0``.  Memory beyond the result: ``kplanes_reg_workspace_bytes`` in the forward,
+    one ``grad_planes`` in the backward."""
+    _check_planes(planes, layout)
+    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
+    _lib.check_tensors(planes.device, {"planes": planes})
+    _lib.current_stream(planes.device)  # (raises for anything but a GPU: there is no CPU path)
+    return _KPlanesReg.apply((layout, int(p)), planes)
+
+
+def add_kplanes_reg_grad_(planes: torch.Tensor, grad: torch.Tensor, layout: KPlanesLayout, *,
+                          weights: Sequence[float] = (1.0, 1.0, 1.0), p: int = 2) -> torch.Tensor:
+    """``grad += sum_k weights[k] * d term_k / d planes`` and the (unweighted) ``terms [3]``, in ONE sweep over the field, outside
+    autograd.  ``grad``: contiguous, shaped like ``planes``, not aliasing it (e.g. the parameter's ``.grad``)::
+
+        loss.backward()
+        terms = add_kplanes_reg_grad_(planes, planes.grad, layout, weights=(1e-3, 1e-2, 1e-4))
+
+    Allocates nothing but the workspace (``kplanes_reg_workspace_bytes``) and the returned tensor."""
+    _check_planes(planes, layout)
+    assert p in (1, 2), f"p has to be 1 (|d|) or 2 (d ** 2), got {p!r}"
+    w = tuple(float(v) for v in weights)
+    assert len(w) == 3, f"weights has {len(w)} entries for the three terms (space_tv, time_smoothness, time_l1)"
+    assert torch.is_tensor(grad) and grad.shape == planes.shape and grad.is_contiguous(), (
+        "grad has to be contiguous and shaped like planes")
+    assert grad.data_ptr() != planes.data_ptr(), "grad must not alias planes"
+    assert planes.is_contiguous(), "planes handed to the HIP library in place must be contiguous"
+    dev = planes.device
+    _lib.check_tensors(dev, {"planes": planes, "grad": grad})
+    _lib.current_stream(dev)  # (raises for anything but a GPU: there is no CPU path)
+    with torch.no_grad(), torch.cuda.device(dev):
+        a = _reg_args(layout, planes.shape[0], p)
+        a.planes, a.grad_planes, a.accumulate = planes.data_ptr(), grad.data_ptr(), 1
+        a.weights[0], a.weights[1], a.weights[2] = w
+        return _reg_terms(a, "lp_kplanes_reg_fused", dev)
