@@ -74,9 +74,12 @@ the other flags do not apply (the JSON line gains ``hash_grid`` and the layout).
 ``--kplanes`` (with ``--modular``) fits a third student: static planes at three scales (``lp.kplanes_layout((16, 32, 64), None, 8)``,
 ``lp.init_kplanes``) and a 2/2/2 x 32 decoder, rendered through ``lp.ray_samples -> lp.kplanes_eval_mlp -> lp.composite_samples`` --
 encoding and decoder in one launch, no feature tensor -- or, with ``--render-samples``, through ``lp.kplanes_render_samples``: encoding,
-decoder and compositing in one launch, no per-sample tensor; of the other flags only ``--tv-weight w`` applies: after ``loss.backward()``,
+decoder and compositing in one launch, no per-sample tensor; ``--tv-weight w``: after ``loss.backward()``,
 ``lp.add_kplanes_reg_grad_(planes, planes.grad, layout, weights=(w, 0, 0))`` adds ``w`` times the gradient of the planes' spatial total
 variation in one sweep (the JSON line gains ``kplanes`` and, with it, ``tv_weight``, ``first_space_tv`` and ``last_space_tv``).
+``--scaffold-steps`` / ``--scaffold-size`` / ``--scaffold-threshold`` / ``--clip-rays`` work as above: the scaffold comes from
+``lp.kplanes_calculate_scaffold`` (the planes' own lattice kernel) and goes to ``lp.kplanes_eval_mlp`` / ``lp.kplanes_render_samples``
+and to ``lp.clip_rays_to_scaffold``; the JSON line reports its occupancy.
 
 Prints one JSON line with the first / last losses and the PSNR of a held-out ray batch.
 """
@@ -316,10 +319,11 @@ def fit_hash_grid(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False,
 
 
 def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, resolutions=(16, 32, 64), channels=8, fused=False,
-                tv_weight=0.0):
+                tv_weight=0.0, scaffold_steps=(), scaffold_size=64, scaffold_threshold=1e-7, clip_rays=False):
     """the fit of ``fit`` with static planes (``time_resolution=None``: the Hadamard tri-plane) + decoder as the student, through
     ray_samples -> kplanes_eval_mlp -> composite_samples or, ``fused``, through ``lp.kplanes_render_samples`` (one launch, no per-sample
-    tensors); ``tv_weight`` > 0: plus that many times the planes' spatial total variation (``lp.add_kplanes_reg_grad_``)"""
+    tensors); ``tv_weight`` > 0: plus that many times the planes' spatial total variation (``lp.add_kplanes_reg_grad_``);
+    ``scaffold_steps`` / ``clip_rays``: as in ``fit``, with the scaffold of the planes (``lp.kplanes_calculate_scaffold``)"""
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(seed)
     torch.manual_seed(seed)
@@ -335,15 +339,26 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
         enc = torch.zeros(rays.directions.shape[0], 32, device=dev)
         if fused:
             _, nlt, rgb = lp.kplanes_render_samples(dataclasses.replace(rays, encoding=enc), None, samples.depths.detach(),
-                                                    samples.deltas.detach(), planes, lay, dec)
+                                                    samples.deltas.detach(), planes, lay, dec, scaffold=scaffold)
             return 1.0 - torch.exp(-nlt), rgb
-        opacity, color = lp.kplanes_eval_mlp(samples.points, None, planes, rays.grid_idx, lay, dec, enc, 1.0)
+        opacity, color = lp.kplanes_eval_mlp(samples.points, None, planes, rays.grid_idx, lay, dec, enc, 1.0, scaffold=scaffold)
         _, nlt, rgb = lp.composite_samples(opacity, color, samples.depths, samples.deltas)
         return 1.0 - torch.exp(-nlt), rgb
 
+    scaffold_steps = sorted(int(v) for v in scaffold_steps)
+    scaffold, occupancy = None, []
     losses, tvs = [], []
     for it in range(steps):
+        if it in scaffold_steps:
+            scaffold = lp.kplanes_calculate_scaffold(planes, lay, dec, [1, scaffold_size, scaffold_size, scaffold_size],
+                                                     threshold=scaffold_threshold)
+            occupancy.append(float(scaffold.mean()))
+            if verbose:
+                print(f"step {it:4d}  scaffold {tuple(scaffold.shape)}  occupied {occupancy[-1]:.3f}", flush=True)
         rays = random_rays(n_rays, gen, dev)
+        if clip_rays:
+            span = rays.far - rays.near
+            rays, hit = lp.clip_rays_to_scaffold(rays, scaffold)
         with torch.no_grad():
             tgt_rgb, tgt_alpha = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         alpha, rgb = render(rays)
@@ -356,7 +371,11 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
         losses.append(float(loss.detach()))
         if verbose and (it % 50 == 0 or it == steps - 1):
             print(f"step {it:4d}  loss {losses[-1]:.5f}", flush=True)
+    if clip_rays and steps > 0:
+        clip_stats = dict(mean_span_ratio=float(((rays.far - rays.near) / span).mean()), hit_fraction=float(hit.float().mean()))
     rays = random_rays(n_rays, torch.Generator().manual_seed(seed + 1), dev)
+    if clip_rays:
+        rays, _ = lp.clip_rays_to_scaffold(rays, scaffold)
     with torch.no_grad():
         tgt_rgb, _ = render_target(rays.origins, rays.directions, rays.near, rays.far, num_samples)
         psnr = -10.0 * math.log10(float(((render(rays)[1] - tgt_rgb) ** 2).mean()))
@@ -365,6 +384,11 @@ def fit_kplanes(steps=300, n_rays=8192, num_samples=96, seed=0, verbose=False, r
            "plane_rows": lay.rows, "render_samples": bool(fused)}
     if tv_weight > 0.0:
         out.update(tv_weight=tv_weight, first_space_tv=float(tvs[0][0]), last_space_tv=float(tvs[-1][0]))
+    if scaffold_steps:
+        out.update(scaffold_steps=scaffold_steps, scaffold_shape=list(scaffold.shape) if scaffold is not None else None,
+                   scaffold_threshold=scaffold_threshold, scaffold_occupancy=occupancy)
+    if clip_rays and steps > 0:
+        out.update(clip_stats)
     return out
 
 
@@ -439,7 +463,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.kplanes:
         assert a.modular, "--kplanes renders through the modular march: pass --modular as well"
-        out = fit_kplanes(a.steps, a.rays, verbose=True, fused=a.render_samples, tv_weight=a.tv_weight)
+        out = fit_kplanes(a.steps, a.rays, verbose=True, fused=a.render_samples, tv_weight=a.tv_weight, scaffold_steps=a.scaffold_steps,
+                          scaffold_size=a.scaffold_size, scaffold_threshold=a.scaffold_threshold, clip_rays=a.clip_rays)
         print(json.dumps(out))
         return out
     if a.hash_grid:

@@ -43,6 +43,7 @@ from .hash_grid import (HashGridLayout, hash_grid_encode, hash_grid_eval_mlp, ha
                         hash_grid_layout, hash_grid_render_samples, init_hash_grid)
 from .kplanes import (KPlanesLayout, init_kplanes, kplanes_encode, kplanes_eval_mlp, kplanes_eval_mlp_opacity_only,  # noqa: E402
                       kplanes_layout, kplanes_render_samples)
+from .kplanes_scaffold import kplanes_calculate_scaffold, kplanes_scaffold_opacity, kplanes_scaffold_workspace_bytes  # noqa: E402
 # The reference's sub-module import paths (`from lightplane.mlp_utils import DecoderParams`, tests/renderer_speed_benchmark.py:30)
 # exist as alias modules (re-exports only).  Two of them are named like the functions they hold, exactly as in the reference
 # (lightplane/__init__.py:8-9): load them first, then bind the FUNCTIONS to the package attributes, so that a later
@@ -78,6 +79,7 @@ __all__ = [
     "hash_grid_eval_mlp", "hash_grid_eval_mlp_opacity_only", "hash_grid_render_samples",
     "KPlanesLayout", "kplanes_layout", "init_kplanes", "kplanes_encode", "kplanes_eval_mlp", "kplanes_eval_mlp_opacity_only", "kplanes_render_samples",
     "kplanes_regularizers", "add_kplanes_reg_grad_", "kplanes_reg_workspace_bytes",
+    "kplanes_calculate_scaffold", "kplanes_scaffold_opacity", "kplanes_scaffold_workspace_bytes",
 ]
 
 _NOT_PROVIDED = {

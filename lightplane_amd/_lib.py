@@ -321,6 +321,18 @@ class LpKPlanesRegArgs(C.Structure):  # include/lightplane_hip_kplanes_reg.h
     ]
 
 
+class LpKPlanesScaffoldArgs(C.Structure):  # include/lightplane_hip_kplanes_scaffold.h
+    _fields_ = [
+        ("planes", C.c_void_p), ("times", C.c_void_p), ("rows", C.c_int64),
+        ("offset", C.c_int64 * LP_KPLANES_MAX_PLANES * LP_KPLANES_MAX_SCALES),
+        ("spatial", C.c_int32 * LP_KPLANES_MAX_SCALES), ("temporal", C.c_int32 * LP_KPLANES_MAX_SCALES),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("n_scales", C.c_int32), ("n_planes", C.c_int32),
+        ("n_times", C.c_int32), ("dilate", C.c_int32),
+        ("mlp_params", C.c_void_p), ("n_mlp_params", C.c_int64), ("trunk", LpMlp), ("opacity", LpMlp),
+        ("gain", C.c_float), ("threshold", C.c_float), ("shape", LpGrid),
+    ]
+
+
 _LIB = None
 LIB_PATH = os.environ.get("LIGHTPLANE_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblightplane_hip.so")
 
@@ -381,6 +393,9 @@ KPLANES_RENDER_EXPORTS = ("lp_kplanes_render_forward", "lp_kplanes_render_backwa
 
 #: every symbol include/lightplane_hip_kplanes_reg.h declares (and again)
 KPLANES_REG_EXPORTS = ("lp_kplanes_reg_workspace_bytes", "lp_kplanes_reg_forward", "lp_kplanes_reg_backward", "lp_kplanes_reg_fused")
+
+#: every symbol include/lightplane_hip_kplanes_scaffold.h declares (and again)
+KPLANES_SCAFFOLD_EXPORTS = ("lp_kplanes_scaffold_workspace_bytes", "lp_kplanes_scaffold_opacity", "lp_kplanes_scaffold_build")
 
 
 def _signatures():
@@ -454,6 +469,10 @@ def _signatures():
         (KPLANES_REG_EXPORTS[:1], i64, (P(LpKPlanesRegArgs),)),
         (KPLANES_REG_EXPORTS[1:2] + KPLANES_REG_EXPORTS[3:], C.c_int, (P(LpKPlanesRegArgs), vp, i64, vp)),
         (KPLANES_REG_EXPORTS[2:3], C.c_int, (P(LpKPlanesRegArgs), vp)),
+        # occupancy scaffold of a plane field (include/lightplane_hip_kplanes_scaffold.h): args, result (, workspace, workspace bytes), stream
+        (KPLANES_SCAFFOLD_EXPORTS[:1], i64, (P(LpKPlanesScaffoldArgs),)),
+        (KPLANES_SCAFFOLD_EXPORTS[1:2], C.c_int, (P(LpKPlanesScaffoldArgs), vp, vp)),
+        (KPLANES_SCAFFOLD_EXPORTS[2:], C.c_int, (P(LpKPlanesScaffoldArgs), vp, vp, i64, vp)),
     )
 
 
@@ -494,7 +513,8 @@ def lib() -> C.CDLL:
                       (50, LpKPlanesArgs),  # (nor 48, 49 and 51: lightplane_hip_kplanes.h)
                       (54, LpKPlanesPointsArgs),  # (nor 52, 53 and 55: lightplane_hip_kplanes_points.h)
                       (58, LpKPlanesRenderArgs),  # (nor 56, 57 and 59: lightplane_hip_kplanes_render.h)
-                      (62, LpKPlanesRegArgs)):  # (nor 60, 61 and 63: lightplane_hip_kplanes_reg.h)
+                      (62, LpKPlanesRegArgs),  # (nor 60, 61 and 63: lightplane_hip_kplanes_reg.h)
+                      (66, LpKPlanesScaffoldArgs)):  # (nor 64, 65 and 67: lightplane_hip_kplanes_scaffold.h)
         if L.lp_abi_sizeof(which) != C.sizeof(st):
             raise LightplaneHipError(
                 f"ABI mismatch: sizeof({st.__name__}) is {C.sizeof(st)} in the ctypes binding but "

@@ -20,9 +20,9 @@ OUT = os.path.join(PKG, "liblightplane_hip.so")
 SOURCES = ["lp_renderer_loop.hip", "lp_renderer_loop_stream.hip", "lp_renderer_loop_dump.hip", "lp_renderer_mfma_bwd.hip", "lp_renderer_mfma_bwd_dump.hip", "lp_renderer_mfma_bwd_c32.hip", "lp_renderer_mfma_bwd_aux.hip", "lp_renderer_mfma_bwd_tm.hip",
            "lp_splatter_mlp_loop.hip", "lp_splatter_mlp_loop_dump.hip", "lp_renderer_mfma.hip", "lp_renderer_loop_shallow.hip", "lp_renderer_loop_shallow_dump.hip",
            "lp_renderer_generic.hip", "lp_splatter.hip", "lp_splatter_mlp.hip", "lp_splatter_mlp_dump.hip", "lp_splatter_mlp_loop_shallow.hip",
-           "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_grid_tv.hip", "lp_grid_resample.hip", "lp_scaffold.hip", "lp_points.hip", "lp_render_samples.hip", "lp_point_grid.hip", "lp_ray_grid.hip", "lp_hash_grid.hip", "lp_hash_points.hip", "lp_hash_render.hip", "lp_kplanes_render.hip", "lp_kplanes_points.hip", "lp_kplanes.hip", "lp_kplanes_reg.hip", "lp_ray_clip.hip", "lp_mesh.hip", "lp_composite.hip", "lp_importance.hip", "lp_ray_losses.hip", "lp_api.hip"]
+           "lp_splatter_mlp_loop_shallow_dump.hip", "lp_ray_embedding.hip", "lp_grid_tv.hip", "lp_grid_resample.hip", "lp_scaffold.hip", "lp_points.hip", "lp_render_samples.hip", "lp_point_grid.hip", "lp_ray_grid.hip", "lp_hash_grid.hip", "lp_hash_points.hip", "lp_hash_render.hip", "lp_kplanes_render.hip", "lp_kplanes_points.hip", "lp_kplanes.hip", "lp_kplanes_reg.hip", "lp_kplanes_scaffold.hip", "lp_ray_clip.hip", "lp_mesh.hip", "lp_composite.hip", "lp_importance.hip", "lp_ray_losses.hip", "lp_api.hip"]
 PUBLIC_HEADERS = [os.path.join("..", "..", "include", name) for name in ("lightplane_hip.h", "lightplane_hip_samples.h", "lightplane_hip_importance.h", "lightplane_hip_losses.h",
-                                                                          "lightplane_hip_render_samples.h", "lightplane_hip_ray_grid.h", "lightplane_hip_hash_grid.h", "lightplane_hip_hash_points.h", "lightplane_hip_hash_render.h", "lightplane_hip_kplanes.h", "lightplane_hip_kplanes_points.h", "lightplane_hip_kplanes_render.h", "lightplane_hip_kplanes_reg.h")]
+                                                                          "lightplane_hip_render_samples.h", "lightplane_hip_ray_grid.h", "lightplane_hip_hash_grid.h", "lightplane_hip_hash_points.h", "lightplane_hip_hash_render.h", "lightplane_hip_kplanes.h", "lightplane_hip_kplanes_points.h", "lightplane_hip_kplanes_render.h", "lightplane_hip_kplanes_reg.h", "lightplane_hip_kplanes_scaffold.h")]
 # every header of this directory (the rule of source_hash()) and the public ones: a change to any of them recompiles everything
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + PUBLIC_HEADERS
 FLAGS = [
@@ -74,6 +74,8 @@ FILE_FLAGS = {
     "lp_kplanes_points.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # ... and the render along rays on it: the gather, the decoder and the compositing scan of the chain it replaces
     "lp_kplanes_render.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # ... and the occupancy scaffold on it: the same folds and products on a lattice
+    "lp_kplanes_scaffold.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -1119,6 +1119,44 @@ static int check_kplanes_points(const char* what, const LpKPlanesPointsArgs* arg
   return LP_OK;
 }
 
+// shape and dilation of a plane field's scaffold: all lp_kplanes_scaffold_workspace_bytes() looks at
+static int check_kplanes_scaffold_shape(const char* what, const LpKPlanesScaffoldArgs* args) {
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  if (int rc = check_shape(what, "scaffold", args->shape)) return rc;
+  if (args->dilate < 0) return set_error(LP_EINVAL, "%s: dilate = %d, has to be >= 0", what, args->dilate);
+  if ((int64_t)args->shape.B * args->shape.D * args->shape.H * args->shape.W >= ((int64_t)1 << 31))
+    return set_error(LP_EUNSUPPORTED, "%s: scaffold shape [%d,%d,%d,%d] has 2^31 points or more", what, args->shape.B, args->shape.D,
+                     args->shape.H, args->shape.W);
+  return LP_OK;
+}
+
+// everything lp_kplanes_scaffold_opacity / lp_kplanes_scaffold_build share: the layout as lp_kplanes_* (through a copy of its fields),
+// the decoder as lp_scaffold_*, the timestamps and the lattice.  Messages begin with the field where a field is at fault.
+static int check_kplanes_scaffold(const char* what, const LpKPlanesScaffoldArgs* args, const float* out) {
+  int rc;
+  if (!args) return set_error(LP_ENULL, "%s: args is NULL", what);
+  LP_ALIGNED(*args, planes);
+  LP_ALIGNED(*args, times);
+  LP_ALIGNED(*args, mlp_params);
+  if ((rc = check_aligned("scaffold / opacity (the result)", out))) return rc;
+  const LpKPlanesArgs k = kplanes_scaffold_view(*args);  // the layout fields, for the one place that judges them
+  if ((rc = check_kplanes_layout(what, k))) return rc;
+  if ((rc = check_kplanes_scaffold_shape(what, args))) return rc;
+  if (args->shape.B != args->batch)
+    return set_error(LP_EINVAL, "shape: scaffold batch %d != batch %d of the planes", args->shape.B, args->batch);
+  if (args->n_planes == 6 && args->n_times < 1) return set_error(LP_EINVAL, "n_times %d < 1 for a dynamic layout", args->n_times);
+  if (args->threshold != args->threshold) return set_error(LP_EINVAL, "%s: threshold is NaN", what);
+  int head_in;
+  if ((rc = check_trunk_and_opacity(what, args->n_scales * args->channels, args->trunk, args->opacity, head_in))) return rc;
+  if ((rc = check_param_count(what, mlp_numel(args->trunk) + mlp_numel(args->opacity), args->n_mlp_params, false))) return rc;
+  const struct { const char* field; const void* p; bool needed; } ptrs[] = {
+      {"planes", args->planes, true}, {"times", args->times, args->n_planes == 6}, {"mlp_params", args->mlp_params, true},
+      {"the result pointer", out, true}};
+  for (const auto& f : ptrs)
+    if (f.needed && !f.p) return set_error(LP_ENULL, "%s is NULL", f.field);
+  return LP_OK;
+}
+
 // everything lp_hash_points_forward / lp_hash_points_backward check.  `color`: the colour head takes part (forward: color_out given;
 // backward: grad_color given) -- only then are the colour MLP and the encoding looked at.  Messages begin with the field at fault.
 static int check_hash_points(const char* what, const LpHashPointsArgs* args, bool backward) {
@@ -1285,15 +1323,15 @@ static int check_kplanes_render(const char* what, const LpKPlanesRenderArgs* arg
 
 // the "points" entry of lp_build_info() also reports the render at given depths (lp_render_samples.hip is the decoder at points fused
 // with the compositing), its hash-grid twin (lp_hash_render.hip), the space-time plane encoding at points (lp_kplanes.hip) and the
-// decoder fused on it (lp_kplanes_points.hip) and its render along rays (lp_kplanes_render.hip): the top-level keys of the text stay as
-// they are
+// decoder fused on it (lp_kplanes_points.hip), its render along rays (lp_kplanes_render.hip), its regularisers and its occupancy
+// scaffold (lp_kplanes_scaffold.hip): the top-level keys of the text stay as they are
 static const char* build_info_points_family() {
-  static char text[7168];  // (the seven texts together: ~5.8 KB; lp_build_info() holds 16 KB)
+  static char text[8192];  // (the eight texts together: ~6.6 KB; lp_build_info() holds 16 KB)
   const char* p = build_info_points();
   snprintf(text, sizeof(text), "%.*s, \"render_samples\": %s, \"hash_render\": %s, \"kplanes\": %s, \"kplanes_points\": %s, "
-           "\"kplanes_render\": %s, \"kplanes_reg\": %s}",
+           "\"kplanes_render\": %s, \"kplanes_reg\": %s, \"kplanes_scaffold\": %s}",
            (int)strlen(p) - 1, p, build_info_render_samples(), build_info_hash_render(), build_info_kplanes(), build_info_kplanes_points(),
-           build_info_kplanes_render(), build_info_kplanes_reg());
+           build_info_kplanes_render(), build_info_kplanes_reg(), build_info_kplanes_scaffold());
   return text;
 }
 
@@ -1360,6 +1398,7 @@ int lp_abi_sizeof(int which) {
     case 54: return (int)sizeof(LpKPlanesPointsArgs);  // (and 52, 53, 55: lightplane_hip_kplanes_points.h)
     case 58: return (int)sizeof(LpKPlanesRenderArgs);  // (and 56, 57, 59: lightplane_hip_kplanes_render.h)
     case 62: return (int)sizeof(LpKPlanesRegArgs);  // (and 60, 61, 63: lightplane_hip_kplanes_reg.h)
+    case 66: return (int)sizeof(LpKPlanesScaffoldArgs);  // (and 64, 65, 67: lightplane_hip_kplanes_scaffold.h)
     default: return -1;
   }
 }
@@ -1973,6 +2012,31 @@ int lp_scaffold_build(const LpScaffoldArgs* args, float* scaffold, void* workspa
       return set_error(LP_EINVAL, "lp_scaffold_build: the workspace overlaps the result");
   }
   return scaffold_launch(a, scaffold, workspace, true, (hipStream_t)stream);
+}
+
+int64_t lp_kplanes_scaffold_workspace_bytes(const LpKPlanesScaffoldArgs* args) {
+  const int rc = check_kplanes_scaffold_shape("lp_kplanes_scaffold_workspace_bytes", args);
+  if (rc) return rc;
+  return scaffold_workspace_bytes(args->shape, args->dilate);
+}
+
+int lp_kplanes_scaffold_opacity(const LpKPlanesScaffoldArgs* args, float* opacity, void* stream) {
+  const int rc = check_kplanes_scaffold("lp_kplanes_scaffold_opacity", args, opacity);
+  if (rc) return rc;
+  return kplanes_scaffold_launch(*args, opacity, nullptr, false, (hipStream_t)stream);
+}
+
+int lp_kplanes_scaffold_build(const LpKPlanesScaffoldArgs* args, float* scaffold, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* what = "lp_kplanes_scaffold_build";
+  int rc = check_kplanes_scaffold(what, args, scaffold);
+  if (rc) return rc;
+  const int64_t need = scaffold_workspace_bytes(args->shape, args->dilate);
+  if (need > 0) {
+    if ((rc = check_workspace(what, "lp_kplanes_scaffold_workspace_bytes", workspace, workspace_bytes, need, 16, LP_EINVAL))) return rc;
+    const uintptr_t w0 = (uintptr_t)workspace, s0 = (uintptr_t)scaffold;
+    if (w0 < s0 + (uintptr_t)need * 4 && s0 < w0 + (uintptr_t)need) return set_error(LP_EINVAL, "%s: the workspace overlaps the result", what);
+  }
+  return kplanes_scaffold_launch(*args, scaffold, workspace, true, (hipStream_t)stream);
 }
 
 int64_t lp_mesh_workspace_bytes(const LpMeshArgs* args) {

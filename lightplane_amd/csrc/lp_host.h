@@ -16,6 +16,7 @@
 #include "../../include/lightplane_hip_kplanes_points.h"
 #include "../../include/lightplane_hip_kplanes_render.h"
 #include "../../include/lightplane_hip_kplanes_reg.h"
+#include "../../include/lightplane_hip_kplanes_scaffold.h"
 #include "lp_launch.h"
 
 namespace lp {
@@ -145,6 +146,9 @@ const char* build_info_grid_resample();
 // 0 / 1 floats through one byte per point of `workspace`)
 int64_t scaffold_workspace_bytes(const LpGrid& shape, int dilate);
 int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool occupancy, hipStream_t stream);
+// its three dilation passes (W, H, D) for another lattice kernel: occupancy bytes in `workspace` -> 0 / 1 floats in `out`, whose first
+// quarter is the second byte buffer (dilate > 0)
+int scaffold_dilate_launch(uint8_t* workspace, float* out, const LpGrid& shape, int dilate, hipStream_t stream);
 const char* build_info_scaffold();
 // the decoder at arbitrary points: lp_points.hip (`a` normalised and checked by lp_api.hip)
 int points_forward_launch(const LpPointsArgs& a, hipStream_t stream);
@@ -219,6 +223,11 @@ const char* build_info_kplanes_render();
 int64_t kplanes_reg_workgroups(const LpKPlanesRegArgs& a);  // of the sweep; three doubles of workspace each
 int kplanes_reg_launch(const LpKPlanesRegArgs& a, double* workspace, bool want_grad, hipStream_t stream);
 const char* build_info_kplanes_reg();
+// occupancy scaffold of a plane field over a set of timestamps: lp_kplanes_scaffold.hip (`a` checked by lp_api.hip; occupancy and
+// workspace as scaffold_launch)
+int kplanes_scaffold_launch(const LpKPlanesScaffoldArgs& a, float* out, void* workspace, bool occupancy, hipStream_t stream);
+LpKPlanesArgs kplanes_scaffold_view(const LpKPlanesScaffoldArgs& a);  // its layout, planes and times as an LpKPlanesArgs (no points)
+const char* build_info_kplanes_scaffold();
 int hash_randn_launch(const int32_t* x1, const int32_t* x2, float* out, int64_t n, int32_t seed,
                       hipStream_t stream);
 

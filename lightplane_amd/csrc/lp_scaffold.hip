@@ -106,6 +106,24 @@ static int64_t scaffold_points(const LpGrid& s) { return (int64_t)s.B * s.D * s.
 // one byte per lattice point when there is a dilation to do, nothing otherwise
 int64_t scaffold_workspace_bytes(const LpGrid& shape, int dilate) { return dilate > 0 ? scaffold_points(shape) : 0; }
 
+// The three passes of the dilation: occupancy bytes in `ws` -> dilate(.) as 0 / 1 floats in `out` (dilate > 0).
+int scaffold_dilate_launch(uint8_t* ws, float* out, const LpGrid& shape, int dilate, hipStream_t stream) {
+  const int64_t n_points = scaffold_points(shape);
+  uint8_t* const ob = reinterpret_cast<uint8_t*>(out);  // the first quarter of the result as the second byte buffer
+  int rc;
+  unsigned dblocks;
+  if ((rc = launch_blocks("lp_scaffold", n_points, SC_DIL_THREADS, dblocks))) return rc;
+  const dim3 dgr(dblocks), dbl(SC_DIL_THREADS);
+  const int W = shape.W, H = shape.H, D = shape.D;
+  hipLaunchKernelGGL((scaffold_dilate<false>), dgr, dbl, 0, stream, ws, (void*)ob, n_points, W, (int64_t)1, dilate < W ? dilate : W);
+  if ((rc = check_launch("scaffold_dilate (W)"))) return rc;
+  hipLaunchKernelGGL((scaffold_dilate<false>), dgr, dbl, 0, stream, ob, (void*)ws, n_points, H, (int64_t)W, dilate < H ? dilate : H);
+  if ((rc = check_launch("scaffold_dilate (H)"))) return rc;
+  // (the float pass reads the workspace, never the tensor it overwrites)
+  hipLaunchKernelGGL((scaffold_dilate<true>), dgr, dbl, 0, stream, ws, (void*)out, n_points, D, (int64_t)H * W, dilate < D ? dilate : D);
+  return check_launch("scaffold_dilate (D)");
+}
+
 // `a` normalised and checked by lp_api.hip.  occupancy == false: out = the raw opacity lattice (workspace unused).
 // occupancy == true: out = dilate(opacity > threshold) as 0 / 1 floats, through `workspace` when a.dilate > 0.
 int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool occupancy, hipStream_t stream) {
@@ -131,23 +149,10 @@ int scaffold_launch(const LpScaffoldArgs& a, float* out, void* workspace, bool o
     hipLaunchKernelGGL((scaffold_lattice<SC_OCC_FLOAT>), gr, bl, lds, stream, s);
     return check_launch("scaffold_lattice");
   }
-  uint8_t* const ws = static_cast<uint8_t*>(workspace);
-  uint8_t* const ob = reinterpret_cast<uint8_t*>(out);  // the first quarter of the result as the second byte buffer
-  s.out = ws;
+  s.out = workspace;
   hipLaunchKernelGGL((scaffold_lattice<SC_OCC_BYTE>), gr, bl, lds, stream, s);
-  int rc = check_launch("scaffold_lattice");
-  if (rc) return rc;
-  unsigned dblocks;
-  if ((rc = launch_blocks("lp_scaffold", s.n_points, SC_DIL_THREADS, dblocks))) return rc;
-  const dim3 dgr(dblocks), dbl(SC_DIL_THREADS);
-  const int W = a.shape.W, H = a.shape.H, D = a.shape.D;
-  hipLaunchKernelGGL((scaffold_dilate<false>), dgr, dbl, 0, stream, ws, (void*)ob, s.n_points, W, (int64_t)1, a.dilate < W ? a.dilate : W);
-  if ((rc = check_launch("scaffold_dilate (W)"))) return rc;
-  hipLaunchKernelGGL((scaffold_dilate<false>), dgr, dbl, 0, stream, ob, (void*)ws, s.n_points, H, (int64_t)W, a.dilate < H ? a.dilate : H);
-  if ((rc = check_launch("scaffold_dilate (H)"))) return rc;
-  // (the float pass reads the workspace, never the tensor it overwrites)
-  hipLaunchKernelGGL((scaffold_dilate<true>), dgr, dbl, 0, stream, ws, (void*)out, s.n_points, D, (int64_t)H * W, a.dilate < D ? a.dilate : D);
-  return check_launch("scaffold_dilate (D)");
+  if (int rc = check_launch("scaffold_lattice")) return rc;
+  return scaffold_dilate_launch(static_cast<uint8_t*>(workspace), out, a.shape, a.dilate, stream);
 }
 
 const char* build_info_scaffold() {
